@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the LAV full-agent forward on MI355X (BASELINE.json metric: frames/s, 32k-point LiDAR + 3 cams).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1: one replica per GPU)
 
 One step = one pass of lav_amd.frame.FramePipeline.step - everything LAVAgent.run_step does on the GPU for
@@ -11,8 +11,13 @@ temporal stacking, pillar scatter, BEV backbone + heads, detection decode, ResNe
 Inference is a closed loop with per-vehicle state: it does not shard, so N > 1 runs N independent replicas
 ("replicas only") and reports the aggregate frames/s.
 
-Prints ONE JSON line (rank 0) with `roofline` for the pillar point-net/scatter kernel (HIP events recorded by
-the library on its launch stream) and `cpu_baseline` (the oracle's full frame on the host cores, N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps, reads the health counters the timed frames
+left on the device and prints the headline figure.  `--dump-outputs DIR` also writes what the last timed step returned to its
+caller, one DIR/<name>.npy per array (the inputs are seeded: two builds can be compared output for output).  `--full` adds
+everything else: the plans of --plan-check-frames more frames recomputed on the step path, `roofline` for the pillar
+point-net/scatter kernel (HIP events recorded by the library on its launch stream) and the other isolated kernels, forced-N,
+sensor-upload, chain-only and per-graph frames, the exact-fp32 child run, the two training lines and `cpu_baseline` (the
+oracle's full frame on the host cores, N=1 only).
 """
 import argparse
 import ctypes
@@ -78,6 +83,30 @@ def synthetic_inputs(device, n_ticks=4, n_points=32768):
 def pose(i):
     """EKF pose stream: gentle forward motion, 0.05 rad / 5 frames of yaw."""
     return np.array([0.2 * i, 0.02 * i]), 0.01 * i
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: every array of one step's result as path/<name>.npy - the tensors in float32, the detections of class c as
+    det_c<c>.npy, float64 rows (x, y, w, h, cos, sin) in the order step() lists them.  lidar_points holds the points that are
+    present, in order: the pipelines mark an absent point (ego-box removal, tick padding, a history sweep not yet recorded) with
+    x = NaN instead of compacting the stack, where the reference drops the row."""
+    arrays = {}
+    for k, v in out.items():
+        if k == "det":
+            for c, rows in enumerate(v):
+                arrays[f"det_c{c}"] = np.asarray(rows, np.float64).reshape(-1, 6)
+        else:
+            arrays[k] = v.detach().float().cpu().numpy()
+    arrays["lidar_points"] = arrays["lidar_points"][~np.isnan(arrays["lidar_points"][:, 0])]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes of outputs, more than the {DUMP_LIMIT_BYTES} allowed")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def cpu_baseline(sds, host, budget_s=20.0):
@@ -151,7 +180,7 @@ def train_bench(args):
         if base % world:
             raise SystemExit(f"BASELINE's global batch {base} does not divide over {world} ranks (use --batch)")
         per, scaling = base // world, "strong"
-    steps = args.steps if args.steps != 100 else 10
+    steps = args.steps if args.steps is not None else 10
     warmup = min(args.warmup, 3)
     cfg = TrainConfig(log_every=args.log_every)
     dt, info, (rank, world) = train_loop(what, per * world, steps, warmup, cfg=cfg, profile_steps=2)
@@ -299,12 +328,17 @@ def cpu_train_baseline(what, budget_batch=16, steps=6):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 100 in infer mode, 10 in the training modes)")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the short train_full / train_bev runs appended to the inference line")
-    ap.add_argument("--no-variants", action="store_true", help="skip the exact-fp32 child run of the frame")
-    ap.add_argument("--plan-check-frames", type=int, default=40, help="frames after the timed ones whose plan is recomputed on the step-per-launch path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="infer mode: write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="infer mode: after the headline figure also run the plan check, isolated-kernel rooflines, frame variants, "
+                         "the exact-fp32 child run, the training lines and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the short train_full / train_bev runs appended to the inference line")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the exact-fp32 child run of the frame")
+    ap.add_argument("--plan-check-frames", type=int, default=40, help="with --full: frames after the timed ones whose plan is recomputed on the step-per-launch path")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from Python instead of replaying HIP graphs")
     ap.add_argument("--mode", default="infer", choices=["infer", "train_full", "train_bev"],
                     help="infer: BASELINE metric (i) frames/s; train_full / train_bev: metric (ii) samples/s, data parallel")
@@ -313,7 +347,11 @@ def main():
     ap.add_argument("--cpu-train-baseline", action="store_true", help="training modes: add a bounded CPU run of the same step as cpu_baseline")
     args = ap.parse_args()
     if args.mode != "infer":
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: infer mode only")
         return train_bench(args)
+    if args.steps is None:
+        args.steps = 100
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -342,7 +380,7 @@ def main():
     if not args.eager:
         pipe.precapture(cmds=[3], max_others=8)   # no HIP-graph capture inside the timed region, whatever the detections do
     # fill the 15-frame history + warm up (untimed); profiling is armed here so its event pools are created now
-    if args.eager:
+    if args.eager and args.full:
         lib.lav_profile_enable(min(65000, 200 * args.steps))
     i = 0
     # the agent stacks the sweeps of frames t, t-5 and t-10: the first frame whose three sweeps all exist is the 16th,
@@ -375,9 +413,11 @@ def main():
         health["last_plan_launch"] = h1["last_plan_launch"]
     host_finite = all(bool(torch.isfinite(out[k]).all()) for k in ("ego_plan_locs", "ego_cast_locs", "ego_embd", "pred_bra", "pred_bev")) \
         and bool(torch.isfinite(out["other_cast_locs"]).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)     # before any further frame: the graphs' output buffers are rewritten by the next one
     # finite is not yet right: more frames (untimed, --plan-check-frames), each plan recomputed on the step-per-launch path and compared
     plan_dev = None
-    if hasattr(pipe, "plan_deviation"):
+    if args.full and hasattr(pipe, "plan_deviation"):
         plan_dev = 0.0
         for _ in range(args.plan_check_frames):
             o = step(i); i += 1
@@ -396,7 +436,7 @@ def main():
     lib.lav_profile_enable(0)
 
     n_pts = int(out["lidar_points"].shape[0])
-    per_frame_us = {k: round(v[0] / args.steps * 1e3, 1) for k, v in prof.items()} if args.eager else None
+    per_frame_us = {k: round(v[0] / args.steps * 1e3, 1) for k, v in prof.items()} if args.eager and args.full else None
 
     def pillar_micro(n_per_sweep, reps=100, batch=1):
         """BASELINE.json config #2 in isolation: back-to-back pillar launches on one synthetic cloud, so the
@@ -566,20 +606,20 @@ def main():
                                               f"{n_c} crop(s): every output value written once + the map region under the crop read once (crop pitch ~ map pitch)")
         return outm
 
-    micro = {"config2_32768pts": pillar_micro(10923), "agent_196608pts": pillar_micro(65536)} if rank == 0 else None
+    micro = {"config2_32768pts": pillar_micro(10923), "agent_196608pts": pillar_micro(65536)} if rank == 0 and args.full else None
     if micro is not None:
         try:   # sixteen config-#2 clouds in one call: the same kernels with the launch chain paid once
             micro["config2_batch16_one_call"] = dict(pillar_micro(10923, reps=30, batch=16), clouds=16,
                                                      note="16 clouds of 32 769 points, one lav_pillar_scatter call: the kernel pair's throughput regime - not BASELINE config #2, which is ONE cloud (roofline.frac)")
         except Exception as e:   # never lose the headline line to a side measurement
             micro["config2_batch16_one_call"] = dict(error=repr(e)[:200])
-    conv_roof = conv_micro() if rank == 0 else None
+    conv_roof = conv_micro() if rank == 0 and args.full else None
     # roofline of the dominant pillar kernel at the frame's own size (196 608 points).  The frame loop replays HIP
     # graphs (kernels inside a graph cannot carry event pairs), so the figure comes from the back-to-back launches
     # above on the same library stream: pure kernel time, no launch gaps.
     roofline = None
-    glue = glue_micro() if rank == 0 else None
-    if rank == 0:
+    glue = glue_micro() if rank == 0 and args.full else None
+    if micro is not None:
         # The north-star figure: fraction of the HBM roof (algorithmic bytes 4 (N D + C ny nx)) of the pillar kernel,
         # at BASELINE config #2 (32 768-point sweep); the frame's own 196 608-point stack and the matrix-pipe term of the fused
         # PointNet (max(bytes / 8 TB/s, flops / 157.3 TFLOP/s) is the binding roof) are carried beside it.
@@ -677,13 +717,13 @@ def main():
                     note="float32 camera tensors (7.0 MB per frame: an upper bound - the agent itself uploads uint8 images, 3.2 MB); pinned host memory",
                     copy_launches_per_frame=per_frame)
     uploads = None
-    if rank == 0 and world == 1 and not args.eager:
+    if args.full and rank == 0 and world == 1 and not args.eager:
         try:
             uploads = upload_frames()
         except Exception as e:   # never lose the headline line to a side measurement
             uploads = dict(error=repr(e)[:200])
     forced = None
-    if rank == 0 and world == 1 and not args.eager:
+    if args.full and rank == 0 and world == 1 and not args.eager:
         forced = {f"others_{k}": forced_frames(k) for k in (0, 4)}
         pipe.set_forced_others(None)
 
@@ -724,7 +764,7 @@ def main():
             pipe.ring.copy_(state[0]); pipe.b_prev.copy_(state[1])
         return res
     chain_ms = graphs_ms = None
-    if rank == 0 and world == 1 and not args.eager:
+    if args.full and rank == 0 and world == 1 and not args.eager:
         chain_ms = chain_only()
         graphs_ms = graph_times()
 
@@ -733,7 +773,7 @@ def main():
         a child run of this script, inference line only."""
         import subprocess
         env = dict(os.environ, LAV_CONV_PRECISION="f32")
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "40", "--warmup", "16", "--no-train", "--no-cpu-baseline", "--no-variants"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "40", "--warmup", "16"]
         try:
             r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
             line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -743,7 +783,7 @@ def main():
             return dict(error=repr(e)[:200])
 
     training = None
-    if world > 1 and not args.no_train:
+    if args.full and world > 1 and not args.no_train:
         # the data-parallel training lines of this N: every rank runs a child; this process's group and frame memory go first
         import torch.distributed as dist
         dist.barrier()
@@ -777,13 +817,13 @@ def main():
         res["valid"] = not bad
         if bad:
             res["invalid_reason"] = "; ".join(bad)
-        if world == 1 and not args.eager and not args.no_variants:
+        if args.full and world == 1 and not args.eager and not args.no_variants:
             res["frame_fp32_kernels"] = f32_frame()
-        if world == 1 and not args.no_train:
+        if args.full and world == 1 and not args.no_train:
             res["training"] = training_lines(with_cpu=not args.no_cpu_baseline)
         elif training is not None:
             res["training"] = training
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(sds, host)
         else:
             res["cpu_baseline"] = None
