@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 28
+#define LAV_ABI_VERSION 29
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -526,6 +526,16 @@ int lav_bn_train_backward_amax(const float *x, const float *y, const float *dy, 
                                const float *save_mean, const float *save_rstd, int relu_pre, int relu_post, float *dx, float *dres,
                                float *dgamma, float *dbeta, float *amax_dx, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The same pair with Dropout2d's per-(sample, channel) multiplier (ABI 29): y = relu_post(chmask[b][c] * BN(x) + residual), and its backward
+ * (the residual's gradient dres = the relu_post-masked dy, the normalisation's gradient chmask * dres).  chmask [batch][channels] on the
+ * device ({0, 1 / (1 - p)}, drawn by the caller); relu_pre is not offered.  Two launches each way, sums in a fixed order, as above. */
+int lav_bn_train_forward_mask(const float *x, const float *residual, const float *chmask, float *y, int batch, int channels, long plane,
+                              const float *gamma, const float *beta, double eps, int relu_post, float *save_mean, float *save_var,
+                              float *save_rstd, float *amax_y, void *workspace, size_t workspace_bytes, void *stream);
+int lav_bn_train_backward_mask(const float *x, const float *y, const float *dy, const float *chmask, int batch, int channels, long plane,
+                               const float *gamma, const float *save_mean, const float *save_rstd, int relu_post, float *dx, float *dres,
+                               float *dgamma, float *dbeta, float *amax_dx, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Weight gradient of a 3x3, padding-1 convolution of stride 1 or 2, or of a 7x7, padding-3, stride-2 convolution (round 5): the weight half of torch.autograd's convolution backward for
  * the stage convolutions of ConvBackbone (team_code_v2/models/lidar.py:57-108) and the four heads' first convolutions (lidar.py:147-161)
  * inside LAV.train_lidar's backward (lav/lav_final_v2.py:140-259), which the reference runs on cuDNN (here: MIOpen's igemm_wrw).
@@ -629,6 +639,35 @@ int lav_conv1d_pair(int batch, int channels, int h, int w, int d_a, int d_b, con
  * x [batch][channels][h][w] (h, w even); y [batch][out_c_total][h/2][w/2]. */
 int lav_pool_affine(const float *x, int batch, int channels, int h, int w, const float *scale, const float *shift, int relu,
                     float *y, int out_c_total, int out_c_offset, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Train mode of ERFNet's factorised convolution pairs (ABI 29; csrc/conv_pair_train.hip): one pair of a non_bottleneck_1d is
+ *     t = relu(conv3x1_d(x) + ba),   z = conv1x3_d(t) + bb          (padding d, dilation d along the kernel's axis)
+ * x, t, z [batch][channels][h][w]; wa = conv3x1.weight [channels][channels][3][1], wb = conv1x3.weight [channels][channels][1][3]
+ * (PyTorch layouts, no repack), ba / bb [channels].  (channels, w) in {(16, 128), (64, 64), (128, 32)} (lav_pair_train_supported),
+ * any batch and h.  float32 FMA arithmetic; every sum in a fixed order, no atomics: bit-reproducible.
+ *     forward:  one launch; writes t (for the backward) and z.
+ *     backward: dt = [t > 0] * conv1x3_d^T(dz) (written to dt, scratch of x's size), dx = conv3x1_d^T(dt),
+ *               dwb / dbb from (dz, t), dwa / dba from (dt, x): per-row-group partial sums in the workspace
+ *               (lav_pair_train_workspace_bytes) reduced in group order.  Six launches.
+ * ------------------------------------------------------------------------------------------ */
+int lav_pair_train_supported(int channels, int width);
+size_t lav_pair_train_workspace_bytes(int batch, int channels, int h);
+int lav_pair_train_forward(const float *x, const float *wa, const float *ba, const float *wb, const float *bb, int batch, int channels,
+                           int h, int w, int dil, float *t, float *z, void *stream);
+int lav_pair_train_backward(const float *x, const float *t, const float *dz, const float *wa, const float *wb, int batch, int channels,
+                            int h, int w, int dil, float *dt, float *dx, float *dwa, float *dba, float *dwb, float *dbb, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
+/* Pixel-wise softmax cross-entropy with mean reduction, F.cross_entropy(logits [batch][classes][plane], labels [batch][plane] int64)
+ * for classes <= 8 (ABI 29): loss[0] (device float) = mean over batch * plane of logsumexp - logit[label], dlogits = (softmax - onehot) /
+ * (batch * plane).  Per-workgroup float64 partials summed in a fixed order by a second launch.  Labels must lie in [0, classes): the
+ * launch does not check them (F.cross_entropy raises on others; here such a pixel would only be kept from reading past its classes -
+ * it adds no loss but still counts in the mean).  lav_amd.train.hipnn.seg_cross_entropy checks the range before the launch.
+ * workspace: lav_seg_xent_workspace_bytes() bytes. */
+size_t lav_seg_xent_workspace_bytes(void);
+int lav_seg_xent_forward(const float *logits, const long long *labels, int batch, int classes, long plane, float *loss, float *dlogits,
+                         void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

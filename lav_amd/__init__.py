@@ -12,7 +12,8 @@ from .resnet import ResNet, resnet18  # noqa: F401
 from .bev_planner import BEVPlanner  # noqa: F401
 from .uniplanner import UniPlanner  # noqa: F401
 from .model_inference import CoordConverter, InferModel, crop_feature, extract_peak, transform_points  # noqa: F401
+from .rgb import RGBSegmentationModel  # noqa: F401
 
 __all__ = ["DynamicPointNet", "PointPillarNet", "ConvBackbone", "Head", "LiDARModel", "ResNet", "resnet18",
            "BEVPlanner", "UniPlanner", "CoordConverter", "InferModel", "crop_feature", "extract_peak",
-           "transform_points"]
+           "transform_points", "RGBSegmentationModel"]

@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LAV_AMD_LIB") or os.path.join(HERE, "liblav_amd.so")   # LAV_AMD_LIB: A/B a second build
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 MAX_CAM = 4
 
 
@@ -107,6 +107,14 @@ SIGNATURES = {
     "lav_gru_seq_backward_workspace_bytes": (_Z, [_I, _I]),
     "lav_gru_seq_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "lav_bn_train_workspace_bytes": (_Z, [_I]),
+    "lav_bn_train_forward_mask": (_I, [_P, _P, _P, _P, _I, _I, C.c_long, _P, _P, C.c_double, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "lav_bn_train_backward_mask": (_I, [_P, _P, _P, _P, _I, _I, C.c_long, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "lav_pair_train_supported": (_I, [_I, _I]),
+    "lav_pair_train_workspace_bytes": (_Z, [_I, _I, _I]),
+    "lav_pair_train_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "lav_pair_train_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "lav_seg_xent_workspace_bytes": (_Z, []),
+    "lav_seg_xent_forward": (_I, [_P, _P, _I, _I, C.c_long, _P, _P, _P, _Z, _P]),
     "lav_bn_train_forward": (_I, [_P, _P, _P, _I, _I, C.c_long, _P, _P, C.c_double, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "lav_bn_train_backward": (_I, [_P, _P, _P, _I, _I, C.c_long, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "lav_bn_train_amax_count": (_I, [_I, _I, C.c_long]),

@@ -102,11 +102,13 @@ __device__ __forceinline__ void channel_sums(const BnGeom &g, int c, const doubl
     for (int s = 0; s < g.S; ++s) { a += partial[2 * ((long)c * g.S + s)]; b += partial[2 * ((long)c * g.S + s) + 1]; }
 }
 
-template <bool VEC>
+// MASK: y = relu_post(chmask[b][c] * BN(x) + residual) - Dropout2d's per-(sample, channel) multiplier applied before the residual add
+template <bool VEC, bool MASK = false>
 __global__ __launch_bounds__(256) void k_bn_apply(BnGeom g, const float *__restrict__ x, const float *__restrict__ res, float *__restrict__ y,
                                                   const float *__restrict__ gamma, const float *__restrict__ beta, double eps, int relu_pre,
                                                   int relu_post, const double *__restrict__ partial, float *__restrict__ save_mean,
-                                                  float *__restrict__ save_var, float *__restrict__ save_rstd, float *__restrict__ amax) {
+                                                  float *__restrict__ save_var, float *__restrict__ save_rstd, float *__restrict__ amax,
+                                                  const float *__restrict__ chmask = nullptr) {
     const int c = blockIdx.x, s = blockIdx.y;
     double a, b;
     channel_sums(g, c, partial, a, b);
@@ -116,14 +118,18 @@ __global__ __launch_bounds__(256) void k_bn_apply(BnGeom g, const float *__restr
     if (s == 0 && threadIdx.x == 0) { save_mean[c] = mean; save_var[c] = (float)var_d; save_rstd[c] = rstd; }
     const float ga = gamma[c], be = beta[c];
     float am = 0.f;
+    float m = 1.f;
     auto one = [&](float v, float r) {
         const float t = relu_pre ? fmaxf(v, 0.f) : v;
-        float o = fmaf((t - mean) * rstd, ga, be) + r;
+        float o;
+        if constexpr (MASK) o = m * fmaf((t - mean) * rstd, ga, be) + r;
+        else o = fmaf((t - mean) * rstd, ga, be) + r;
         o = relu_post ? fmaxf(o, 0.f) : o;
         am = fmaxf(am, lav::finite_abs(o));
         return o;
     };
     for_slice<VEC>(g, c, s, [&](long at) {
+        if constexpr (MASK) m = chmask[at / g.HW];        // (b * C + c: the plane's index; a float4 never spans two planes)
         if constexpr (VEC) {
             const float4 v = *reinterpret_cast<const float4 *>(x + at);
             float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -136,15 +142,19 @@ __global__ __launch_bounds__(256) void k_bn_apply(BnGeom g, const float *__restr
     if (amax) block_absmax_out(am, amax, (long)c * g.S + s);   // (kernel-uniform)
 }
 
-template <bool VEC>
+// MASK: the normalisation's gradient is chmask[b][c] * g (g = the relu_post-masked dy, which is also the residual's gradient)
+template <bool VEC, bool MASK = false>
 __global__ __launch_bounds__(256) void k_bn_bwd_sums(BnGeom g, const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ dy,
                                                      const float *__restrict__ save_mean, const float *__restrict__ save_rstd, int relu_pre,
-                                                     int relu_post, float *__restrict__ dres, double *__restrict__ partial) {
+                                                     int relu_post, float *__restrict__ dres, double *__restrict__ partial,
+                                                     const float *__restrict__ chmask = nullptr) {
     __shared__ double lds[8];
     const int c = blockIdx.x, s = blockIdx.y;
     const float mean = save_mean[c], rstd = save_rstd[c];
     double sg = 0.0, sgx = 0.0;
     for_slice<VEC>(g, c, s, [&](long at) {
+        float m = 1.f;
+        if constexpr (MASK) m = chmask[at / g.HW];
         if constexpr (VEC) {
             const float4 xv = *reinterpret_cast<const float4 *>(x + at);
             float4 gv = *reinterpret_cast<const float4 *>(dy + at);
@@ -153,6 +163,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_sums(BnGeom g, const float *__re
                 gv.x = yv.x > 0.f ? gv.x : 0.f; gv.y = yv.y > 0.f ? gv.y : 0.f; gv.z = yv.z > 0.f ? gv.z : 0.f; gv.w = yv.w > 0.f ? gv.w : 0.f;
             }
             if (dres) *reinterpret_cast<float4 *>(dres + at) = gv;
+            if constexpr (MASK) { gv.x *= m; gv.y *= m; gv.z *= m; gv.w *= m; }
             const float xe[4] = {xv.x, xv.y, xv.z, xv.w}, ge[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -164,6 +175,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_sums(BnGeom g, const float *__re
             float gg = dy[at];
             if (relu_post) gg = y[at] > 0.f ? gg : 0.f;
             if (dres) dres[at] = gg;
+            if constexpr (MASK) gg *= m;
             const float t = relu_pre ? fmaxf(x[at], 0.f) : x[at];
             sg += (double)gg;
             sgx += (double)gg * (double)((t - mean) * rstd);
@@ -177,21 +189,22 @@ __global__ __launch_bounds__(256) void k_bn_bwd_sums(BnGeom g, const float *__re
 }
 
 // g_src: the gradient after the relu_post mask (dres when the forward had a residual, else dy with the mask applied here)
-template <bool VEC>
+template <bool VEC, bool MASK = false>
 __global__ __launch_bounds__(256) void k_bn_bwd_apply(BnGeom g, const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ g_src,
                                                       int mask_here, const float *__restrict__ gamma, const float *__restrict__ save_mean,
                                                       const float *__restrict__ save_rstd, int relu_pre, const double *__restrict__ partial,
                                                       float *__restrict__ dx, float *__restrict__ dgamma, float *__restrict__ dbeta,
-                                                      float *__restrict__ amax) {
+                                                      float *__restrict__ amax, const float *__restrict__ chmask = nullptr) {
     const int c = blockIdx.x, s = blockIdx.y;
     double a, b;
     channel_sums(g, c, partial, a, b);
     if (s == 0 && threadIdx.x == 0) { dbeta[c] = (float)a; dgamma[c] = (float)b; }
     const float mean = save_mean[c], rstd = save_rstd[c];
     const float k0 = gamma[c] * rstd, mg = (float)(a / (double)g.N), mgx = (float)(b / (double)g.N);
-    float am = 0.f;
+    float am = 0.f, m = 1.f;
     auto one = [&](float xv, float gv, float yv) {
         if (mask_here) gv = yv > 0.f ? gv : 0.f;
+        if constexpr (MASK) gv *= m;
         const float t = relu_pre ? fmaxf(xv, 0.f) : xv;
         float o = k0 * (gv - mg - (t - mean) * rstd * mgx);
         o = (relu_pre && !(xv > 0.f)) ? 0.f : o;
@@ -199,6 +212,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(BnGeom g, const float *__r
         return o;
     };
     for_slice<VEC>(g, c, s, [&](long at) {
+        if constexpr (MASK) m = chmask[at / g.HW];
         if constexpr (VEC) {
             const float4 xv = *reinterpret_cast<const float4 *>(x + at);
             const float4 gv = *reinterpret_cast<const float4 *>(g_src + at);
@@ -300,6 +314,62 @@ extern "C" int lav_bn_train_backward_amax(const float *x, const float *y, const 
     } else {
         hipLaunchKernelGGL(k_bn_bwd_sums<false>, grid, dim3(256), 0, st, g, x, y, dy, save_mean, save_rstd, relu_pre, relu_post, dres, partial);
         hipLaunchKernelGGL(k_bn_bwd_apply<false>, grid, dim3(256), 0, st, g, x, y, g_src, mask_here, gamma, save_mean, save_rstd, relu_pre, partial, dx, dgamma, dbeta, amax_dx);
+    }
+    timer_end(tok, st);
+    LAV_LAUNCH_CHECK();
+    return LAV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- with a per-(sample, channel) multiplier
+// (ABI 29) y = relu_post(chmask[b][c] * BN(x) + residual): non_bottleneck_1d's bn2 -> Dropout2d -> (+ x) -> ReLU in the two launches of
+// lav_bn_train_forward; the backward's normalisation gradient is chmask * (the masked dy).  chmask [batch][channels] (device float32).
+extern "C" int lav_bn_train_forward_mask(const float *x, const float *residual, const float *chmask, float *y, int batch, int channels, long hw,
+                                         const float *gamma, const float *beta, double eps, int relu_post, float *save_mean, float *save_var,
+                                         float *save_rstd, float *amax_y, void *workspace, size_t workspace_bytes, void *stream) {
+    LAV_REQUIRE(x && chmask && y && gamma && beta && save_mean && save_var && save_rstd && workspace, "lav_bn_train_forward_mask: null pointer");
+    LAV_REQUIRE(workspace_bytes >= lav_bn_train_workspace_bytes(channels), "lav_bn_train_forward_mask: workspace smaller than lav_bn_train_workspace_bytes");
+    BnGeom g;
+    if (int rc = geometry(g, batch, channels, hw, "lav_bn_train_forward_mask")) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double *partial = static_cast<double *>(workspace);
+    const dim3 grid((unsigned)g.C, (unsigned)g.S);
+    const int tok = timer_begin("bn_train_fwd", st);
+    if (vec_ok(hw, {x, y, residual})) {
+        hipLaunchKernelGGL(k_bn_stats<true>, grid, dim3(256), 0, st, g, x, 0, partial);
+        hipLaunchKernelGGL((k_bn_apply<true, true>), grid, dim3(256), 0, st, g, x, residual, y, gamma, beta, eps, 0, relu_post, partial, save_mean, save_var,
+                           save_rstd, amax_y, chmask);
+    } else {
+        hipLaunchKernelGGL(k_bn_stats<false>, grid, dim3(256), 0, st, g, x, 0, partial);
+        hipLaunchKernelGGL((k_bn_apply<false, true>), grid, dim3(256), 0, st, g, x, residual, y, gamma, beta, eps, 0, relu_post, partial, save_mean, save_var,
+                           save_rstd, amax_y, chmask);
+    }
+    timer_end(tok, st);
+    LAV_LAUNCH_CHECK();
+    return LAV_OK;
+}
+
+extern "C" int lav_bn_train_backward_mask(const float *x, const float *y, const float *dy, const float *chmask, int batch, int channels, long hw,
+                                          const float *gamma, const float *save_mean, const float *save_rstd, int relu_post, float *dx, float *dres,
+                                          float *dgamma, float *dbeta, float *amax_dx, void *workspace, size_t workspace_bytes, void *stream) {
+    LAV_REQUIRE(x && dy && chmask && gamma && save_mean && save_rstd && dx && dgamma && dbeta && workspace, "lav_bn_train_backward_mask: null pointer");
+    LAV_REQUIRE(!relu_post || y, "lav_bn_train_backward_mask: relu_post needs the forward output y");
+    LAV_REQUIRE(workspace_bytes >= lav_bn_train_workspace_bytes(channels), "lav_bn_train_backward_mask: workspace smaller than lav_bn_train_workspace_bytes");
+    BnGeom g;
+    if (int rc = geometry(g, batch, channels, hw, "lav_bn_train_backward_mask")) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double *partial = static_cast<double *>(workspace);
+    const dim3 grid((unsigned)g.C, (unsigned)g.S);
+    const float *g_src = dres ? dres : dy;
+    const int mask_here = relu_post && !dres;
+    const int tok = timer_begin("bn_train_bwd", st);
+    if (vec_ok(hw, {x, y, dy, dx, dres})) {
+        hipLaunchKernelGGL((k_bn_bwd_sums<true, true>), grid, dim3(256), 0, st, g, x, y, dy, save_mean, save_rstd, 0, relu_post, dres, partial, chmask);
+        hipLaunchKernelGGL((k_bn_bwd_apply<true, true>), grid, dim3(256), 0, st, g, x, y, g_src, mask_here, gamma, save_mean, save_rstd, 0, partial, dx, dgamma,
+                           dbeta, amax_dx, chmask);
+    } else {
+        hipLaunchKernelGGL((k_bn_bwd_sums<false, true>), grid, dim3(256), 0, st, g, x, y, dy, save_mean, save_rstd, 0, relu_post, dres, partial, chmask);
+        hipLaunchKernelGGL((k_bn_bwd_apply<false, true>), grid, dim3(256), 0, st, g, x, y, g_src, mask_here, gamma, save_mean, save_rstd, 0, partial, dx, dgamma,
+                           dbeta, amax_dx, chmask);
     }
     timer_end(tok, st);
     LAV_LAUNCH_CHECK();

@@ -1,7 +1,7 @@
-"""Recorded routes -> training batches: the loaders behind `train_bev_v2.py` ('temporal_bev') and `train_full_v2.py`
-('temporal_lidar_painted'), and their single-frame variants ('bev', 'lidar', 'lidar_painted').
+"""Recorded routes -> training batches: the loaders behind `train_bev_v2.py` ('temporal_bev'), `train_full_v2.py`
+('temporal_lidar_painted') and `train_seg.py` ('seg'), and the single-frame variants ('bev', 'lidar', 'lidar_painted').
 
-Follows lav/utils/datasets/{basic,bev,temporal_bev,lidar,lidar_painted,temporal_lidar_painted}_dataset.py and
+Follows lav/utils/datasets/{basic,bev,temporal_bev,lidar,lidar_painted,temporal_lidar_painted,seg}_dataset.py and
 lav/utils/point_painting.py: same LMDB keys, same arithmetic (float32 reads, float64 geometry), same tuple layout, and the
 same ORDER of random draws (torch.rand for the crop jitter / rotation, np.random for the stacked sweeps' pose jitter and
 the point shuffle), so that a seeded reference loader and a seeded loader of this module return the same sample
@@ -9,8 +9,10 @@ the point shuffle), so that a seeded reference loader and a seeded loader of thi
 Routes are read with lav_amd.data.lmdb_ro (no liblmdb here), images with lav_amd.data.image (no OpenCV here).
 
 Differences from the reference, all deliberate: route directories are visited in sorted order (the reference takes
-`glob` order, which is file-system dependent); the 'rgb' / 'seg' / 'bra' loaders (camera-model training, outside the two
-trainers this repository mirrors) are not provided.
+`glob` order, which is file-system dependent); the 'seg' loader applies no image augmentation (the reference's
+`augment(0.5)` - blur, noise, pixel dropout, colour, contrast, grayscale and elastic warps - is built on imgaug, which this
+build does not have: its samples are the reference's with the augmenter as the identity); the 'rgb' and 'bra' loaders (the
+brake net's trainer is outside this repository's scope) are not provided.
 """
 from __future__ import annotations
 
@@ -406,8 +408,31 @@ class TemporalLiDARPaintedDataset(LiDARPaintedDataset):
         return padded, num_points, heat, size, ori_map, bev, -ego_locs, cmd, -nxp, bra, -p_locs, p_oris, p_typs, n
 
 
+def filter_sem(sem: np.ndarray, labels) -> np.ndarray:
+    """CARLA class ids -> training labels: 0 for every class outside `labels`, i + 1 for labels[i] (lav/utils/__init__.py:3-8)."""
+    out = np.zeros_like(sem)
+    for i, label in enumerate(labels):
+        out[sem == label] = i + 1
+    return out
+
+
+class SegmentationDataset(RouteFrames):
+    """'seg' (seg_dataset.py): one sample per (frame, camera), index = frame * len(camera_yaws) + camera.  Returns the camera's
+    image as (H, W, 3) uint8 RGB and its labels filter_sem(sem, seg_channels) as (H, W) uint8."""
+
+    def __len__(self):
+        return self.num_frames * len(self.camera_yaws)
+
+    def __getitem__(self, idx):
+        frame, cam = divmod(idx, len(self.camera_yaws))
+        txn, index = self.txn_map[frame], self.idx_map[frame]
+        rgb = image.imdecode(np.frombuffer(txn.get(f"rgb_{cam}_{index:05d}".encode()), np.uint8), image.IMREAD_COLOR)
+        sem = image.imdecode(np.frombuffer(txn.get(f"sem_{cam}_{index:05d}".encode()), np.uint8), image.IMREAD_GRAYSCALE)
+        return np.ascontiguousarray(rgb[..., ::-1]), filter_sem(sem, self.seg_channels)
+
+
 LOADERS = {"bev": BEVDataset, "temporal_bev": TemporalBEVDataset, "lidar": LiDARDataset, "lidar_painted": LiDARPaintedDataset,
-           "temporal_lidar_painted": TemporalLiDARPaintedDataset}
+           "temporal_lidar_painted": TemporalLiDARPaintedDataset, "seg": SegmentationDataset}
 
 
 def get_data_loader(data_type, args, rank: int = 0, world: int = 1):
@@ -417,7 +442,7 @@ def get_data_loader(data_type, args, rank: int = 0, world: int = 1):
     batch_size / world."""
     if data_type not in LOADERS:
         raise NotImplementedError(f"data loader {data_type!r}: this build provides {sorted(LOADERS)} (the camera-model loaders "
-                                  "'rgb', 'seg', 'bra' belong to trainers outside its scope)")
+                                  "'rgb' and 'bra' belong to the brake net's trainer, outside its scope)")
     dataset = LOADERS[data_type](args.config_path, seed=args.seed)
     common = dict(num_workers=args.num_workers, drop_last=True, pin_memory=torch.cuda.is_available())
     if world > 1:

@@ -1,5 +1,6 @@
 """Writes a small synthetic route in the data collector's LMDB layout (the keys lav/utils/datasets reads: `len`, `town`,
-and per frame t `id_`, `loc_`, `ori_`, `bbox_`, `type_`, `nxp_`, `cmd_`, `bra_`, `lidar_`, `lidar_sem_`, `map_{0..11}_`).
+and per frame t `id_`, `loc_`, `ori_`, `bbox_`, `type_`, `nxp_`, `cmd_`, `bra_`, `lidar_`, `lidar_sem_`, `map_{0..11}_`; with
+cameras=N also `rgb_{0..N-1}_` (colour PNG) and `sem_{0..N-1}_` (grayscale PNG of CARLA class ids), what the 'seg' loader reads).
 No recorded data ships with the reference (Git-LFS pointers), so this is what the loader tests and a no-download smoke
 run of the trainers read:
 
@@ -16,8 +17,28 @@ import numpy as np
 from . import image, lmdb_ro
 
 
-def make_route(path: str, seed: int = 0, frames: int = 40, points: int = 2500, town: str = "Town01", sem_channels: int = 4) -> None:
+def camera_images(r, cameras: int, hw=(72, 64)):
+    """{key stem: PNG bytes} of one frame's `cameras` images: an RGB picture and its class-id map, blocks of CARLA classes (road,
+    lane marks, vehicles, pedestrians, ...) with the colour of each block a noisy function of its class."""
+    H, W = hw
+    out = {}
+    classes = np.array([0, 1, 4, 6, 7, 8, 10, 12], np.uint8)
+    palette = r.integers(0, 256, (len(classes), 3))
+    for c in range(cameras):
+        cells = r.integers(0, len(classes), (H // 8 + 1, W // 8 + 1))
+        k = np.kron(cells, np.ones((8, 8), np.int64))[:H, :W]
+        sem = classes[k]
+        rgb = np.clip(palette[k] + r.normal(0, 12, (H, W, 3)), 0, 255).astype(np.uint8)
+        out[f"rgb_{c}"] = image.imencode_png(rgb)
+        out[f"sem_{c}"] = image.imencode_png(sem)
+    return out
+
+
+def make_route(path: str, seed: int = 0, frames: int = 40, points: int = 2500, town: str = "Town01", sem_channels: int = 4,
+               cameras: int = 0) -> None:
+    """cameras > 0: also per-frame camera images (own random stream: the other records are the same as without them)."""
     r = np.random.default_rng(seed)
+    rc = np.random.default_rng([seed, 7919])
     items = {b"len": str(frames).encode(), b"town": town.encode()}
     f32 = lambda a: np.asarray(a, np.float32).tobytes()
     # actors: ego (id 100, vehicle) drives a gentle arc; vehicles / pedestrians around it, some leave early
@@ -67,15 +88,18 @@ def make_route(path: str, seed: int = 0, frames: int = 40, points: int = 2500, t
             maps[1 if typ[k] == 1 else 2][m] = 255
         for ch in range(12):
             items[f"map_{ch}_{t:05d}".encode()] = image.imencode_png(maps[ch])
+        for stem, png in camera_images(rc, cameras).items():
+            items[f"{stem}_{t:05d}".encode()] = png
         pos = pos + speed[:, None] * np.stack([np.cos(np.deg2rad(ang)), np.sin(np.deg2rad(ang))], 1)
     lmdb_ro.write(path, items.items())
 
 
-def make_dataset(data_dir: str, routes: int = 2, frames: int = 40, seed: int = 0, points: int = 2500) -> None:
+def make_dataset(data_dir: str, routes: int = 2, frames: int = 40, seed: int = 0, points: int = 2500, cameras: int = 0) -> None:
     os.makedirs(data_dir, exist_ok=True)
     towns = ["Town01", "Town03", "Town02", "Town06"]
     for i in range(routes):
-        make_route(os.path.join(data_dir, f"route_{i:03d}"), seed=seed + i, frames=frames, points=points, town=towns[i % len(towns)])
+        make_route(os.path.join(data_dir, f"route_{i:03d}"), seed=seed + i, frames=frames, points=points, town=towns[i % len(towns)],
+                   cameras=cameras)
 
 
 if __name__ == "__main__":
@@ -85,6 +109,7 @@ if __name__ == "__main__":
     ap.add_argument("--frames", type=int, default=40)
     ap.add_argument("--points", type=int, default=2500)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--cameras", type=int, default=0, help="also write rgb_i / sem_i camera images (train_seg.py's data)")
     a = ap.parse_args()
-    make_dataset(a.data_dir, a.routes, a.frames, a.seed, a.points)
+    make_dataset(a.data_dir, a.routes, a.frames, a.seed, a.points, a.cameras)
     print(f"wrote {a.routes} route(s) of {a.frames} frames under {a.data_dir}")

@@ -3,7 +3,9 @@
 3x1 / 1x3 (dilated) pairs, the 3x3/s2 and 2x2/s2 transposed convolutions - is one lav_conv2d launch with its
 bias, BatchNorm affine, residual add and ReLU fused into the epilogue (the reference issues ~6 kernels per
 non_bottleneck_1d convolution pair; MIOpen falls back to naive kernels for the dilated asymmetric shapes).
-The torch forward below is kept for training mode.
+The torch forward below is kept for training mode, where every non_bottleneck_1d on the GPU goes through
+lav_amd.train.hipnn.nb1d_train (its pairs on lav_pair_train_*, its BatchNorms on lav_bn_train_*; the downsamplers, upsamplers
+and the output transposed convolution stay torch ops).
 """
 from __future__ import annotations
 
@@ -79,6 +81,12 @@ class non_bottleneck_1d(nn.Module):  # name kept: it is part of pickled/traced c
         self.dropout = nn.Dropout2d(dropprob)
 
     def forward(self, x):
+        if self.training and x.is_cuda:    # train mode on the GPU: the pairs / BatchNorms on the training kernels where they apply
+            from .train.hipnn import nb1d_train
+            return nb1d_train(self, x)
+        return self.forward_torch(x)
+
+    def forward_torch(self, x):
         y = F.relu(self.bn1(self.conv1x3_1(F.relu(self.conv3x1_1(x)))))
         y = self.bn2(self.conv1x3_2(F.relu(self.conv3x1_2(y))))
         if self.dropout.p != 0:

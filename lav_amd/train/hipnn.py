@@ -194,7 +194,9 @@ def train_precision() -> int:
                        the batch-32 layers are matrix / power bound like the frame's head convolution -, packed weights re-gathered AND
                        re-scaled on the device per step (lav_conv_repack_scratch), every activation and gradient tensor measured once
                        per step (lav_absmax_parts) for the kernels that read it: train_full 132 -> 118 ms per step
-      bf16x6 (round 5) three bf16 pieces, six products."""
+      bf16x6 (round 5) three bf16 pieces, six products.
+    Not consulted by the segmenter's training kernels (nb1d_train, seg_cross_entropy): those compute in fp32 FMA and are selected by
+    LAV_TRAIN_CONV=hip alone."""
     name = os.environ.get("LAV_TRAIN_PRECISION") or (_train_precision_stack[-1] if _train_precision_stack else "bf16x6")
     return {"f16x3": _lib.CONV_F16X3, "bf16x6": _lib.CONV_BF16X6}.get(name, 0)
 
@@ -386,3 +388,149 @@ def conv_module(conv: torch.nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
             or not isinstance(conv.padding, tuple)):
         return conv(x)
     return conv2d(x, conv.weight, conv.stride[0], conv.padding, conv.dilation)
+
+
+# ------------------------------------------------------------------------------------------------------------------ ERFNet blocks
+# The segmenter's training step (LAV.train_seg): each non_bottleneck_1d's two factorised pairs on lav_pair_train_forward /
+# _backward (csrc/conv_pair_train.hip, one forward launch per pair, PyTorch weight layout, fixed-order weight gradients), bn1 on
+# lav_bn_train_* (bn_act), bn2 -> Dropout2d -> (+ x) -> ReLU on lav_bn_train_*_mask (Dropout2d's mask drawn by torch), the loss on
+# lav_seg_xent_forward.  These kernels compute in plain fp32 FMA whatever train_precision() says.
+# OPT-IN (LAV_TRAIN_CONV=hip): measured SLOWER than torch / MIOpen on the same step (profiles/train_seg_probe.json), so
+# with the variable unset - or any other value - the segmenter trains on torch.
+def _seg_kernels_on() -> bool:
+    return os.environ.get("LAV_TRAIN_CONV") == "hip"
+
+
+def _pair_train_ok(block, x) -> bool:
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and torch.is_grad_enabled() and block.training and _seg_kernels_on()
+            and bool(_lib.load().lav_pair_train_supported(int(x.shape[1]), int(x.shape[3]))))
+
+
+class _PairTrain(torch.autograd.Function):
+    """z = conv1x3_d(relu(conv3x1_d(x) + ba)) + bb."""
+    @staticmethod
+    def forward(ctx, x, wa, ba, wb, bb, d):
+        x = x.contiguous()
+        B, C, H, W = x.shape
+        wa, ba, wb, bb = (p.detach().contiguous() for p in (wa, ba, wb, bb))
+        t = torch.empty_like(x)
+        z = torch.empty_like(x)
+        check(_lib.load().lav_pair_train_forward(_ptr(x), _ptr(wa), _ptr(ba), _ptr(wb), _ptr(bb), B, C, H, W, int(d), _ptr(t), _ptr(z),
+                                                 _stream()), "lav_pair_train_forward")
+        ctx.save_for_backward(x, t, wa, wb)
+        ctx.d = int(d)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, t, wa, wb = ctx.saved_tensors
+        dz = dz.contiguous()
+        B, C, H, W = x.shape
+        lib = _lib.load()
+        dt, dx = torch.empty_like(x), torch.empty_like(x)
+        dwa, dwb = torch.empty_like(wa), torch.empty_like(wb)
+        dba = torch.empty(C, dtype=torch.float32, device=x.device)
+        dbb = torch.empty_like(dba)
+        ws = ops_mod._workspace("pair_train", lib.lav_pair_train_workspace_bytes(B, C, H), x.device)
+        check(lib.lav_pair_train_backward(_ptr(x), _ptr(t), _ptr(dz), _ptr(wa), _ptr(wb), B, C, H, W, ctx.d, _ptr(dt), _ptr(dx), _ptr(dwa),
+                                          _ptr(dba), _ptr(dwb), _ptr(dbb), _ptr(ws), ws.numel(), _stream()), "lav_pair_train_backward")
+        return dx, dwa, dba, dwb, dbb, None
+
+
+def pair_train(x, conv3x1, conv1x3):
+    """conv1x3(relu(conv3x1(x))) of one non_bottleneck_1d pair in train mode on lav_pair_train_* (shapes lav_pair_train_supported)."""
+    return _PairTrain.apply(x, conv3x1.weight, conv3x1.bias, conv1x3.weight, conv1x3.bias, int(conv3x1.dilation[0]))
+
+
+class _BnMask(torch.autograd.Function):
+    """relu(m * BN(z) + residual) with m [B, C] Dropout2d's multiplier: lav_bn_train_forward_mask / _backward_mask."""
+    @staticmethod
+    def forward(ctx, z, gamma, beta, residual, m, eps):
+        z, residual, m = z.contiguous(), residual.contiguous(), m.contiguous()
+        B, C, H, W = z.shape
+        y = torch.empty_like(z)
+        save = torch.empty((3, C), dtype=torch.float32, device=z.device)
+        ws = _workspace(C, z.device)
+        check(_lib.load().lav_bn_train_forward_mask(_ptr(z), _ptr(residual), _ptr(m), _ptr(y), B, C, H * W, _ptr(gamma.contiguous()),
+                                                    _ptr(beta.contiguous()), float(eps), 1, _ptr(save[0]), _ptr(save[1]), _ptr(save[2]), None,
+                                                    _ptr(ws), ws.numel(), _stream()), "lav_bn_train_forward_mask")
+        ctx.save_for_backward(z, y, gamma, m, save)
+        mean, var = save[0], save[1]
+        ctx.mark_non_differentiable(mean, var)
+        return y, mean, var
+
+    @staticmethod
+    def backward(ctx, dy, _dmean, _dvar):
+        z, y, gamma, m, save = ctx.saved_tensors
+        dy = dy.contiguous()
+        B, C, H, W = z.shape
+        dz, dres = torch.empty_like(z), torch.empty_like(z)
+        dgb = torch.empty((2, C), dtype=torch.float32, device=z.device)
+        ws = _workspace(C, z.device)
+        check(_lib.load().lav_bn_train_backward_mask(_ptr(z), _ptr(y), _ptr(dy), _ptr(m), B, C, H * W, _ptr(gamma.contiguous()), _ptr(save[0]),
+                                                     _ptr(save[2]), 1, _ptr(dz), _ptr(dres), _ptr(dgb[0]), _ptr(dgb[1]), None, _ptr(ws), ws.numel(),
+                                                     _stream()), "lav_bn_train_backward_mask")
+        return dz, dgb[0], dgb[1], dres, None, None
+
+
+def dropout2d_mask(p: float, B: int, C: int, device) -> torch.Tensor:
+    """[B, C] of {0, 1 / (1 - p)}: the multiplier nn.Dropout2d draws for a (B, C, H, W) input in train mode."""
+    if p >= 1:
+        return torch.zeros((B, C), dtype=torch.float32, device=device)
+    return torch.empty((B, C), dtype=torch.float32, device=device).bernoulli_(1 - p).div_(1 - p)
+
+
+def bn_mask_act(bn, z, residual, m):
+    """relu(m[:, :, None, None] * bn(z) + residual) with `bn` in train mode (running statistics updated like nn.BatchNorm2d)."""
+    y, mean, var = _BnMask.apply(z, bn.weight, bn.bias, residual, m, bn.eps)
+    _update_running(bn, mean, var, z.shape[0] * z.shape[2] * z.shape[3])
+    return y
+
+
+def nb1d_train(block, x, mask=None):
+    """non_bottleneck_1d.forward in train mode: relu(dropout(bn2(pair2(relu(bn1(pair1(x)))))) + x).  On the training kernels when
+    _pair_train_ok (the GPU, float32, grad enabled, LAV_TRAIN_CONV=hip, a supported shape), else the module's own torch forward.
+    mask: Dropout2d's [B, C] multiplier to use instead of a fresh draw (tests)."""
+    if not _pair_train_ok(block, x):
+        return block.forward_torch(x)
+    y = bn_act(block.bn1, pair_train(x, block.conv3x1_1, block.conv1x3_1), relu_post=True)
+    z = pair_train(y, block.conv3x1_2, block.conv1x3_2)
+    if block.dropout.p == 0 and mask is None:
+        return bn_act(block.bn2, z, relu_post=True, residual=x)
+    if mask is None:
+        mask = dropout2d_mask(block.dropout.p, x.shape[0], x.shape[1], x.device)
+    return bn_mask_act(block.bn2, z, x, mask)
+
+
+class _SegXent(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels):
+        logits = logits.contiguous()
+        labels = labels.contiguous()
+        B, Cn = logits.shape[:2]
+        plane = logits[0, 0].numel()
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        dlogits = torch.empty_like(logits)
+        lib = _lib.load()
+        ws = ops_mod._workspace("seg_xent", lib.lav_seg_xent_workspace_bytes(), logits.device)
+        check(lib.lav_seg_xent_forward(_ptr(logits), _ptr(labels), B, Cn, plane, _ptr(loss), _ptr(dlogits), _ptr(ws), ws.numel(), _stream()),
+              "lav_seg_xent_forward")
+        ctx.save_for_backward(dlogits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * g, None
+
+
+def seg_cross_entropy(logits, labels):
+    """F.cross_entropy(logits [B, C, H, W], labels [B, H, W]) (mean reduction): lav_seg_xent_forward with LAV_TRAIN_CONV=hip on the
+    GPU (loss and dlogits in one pass; the backward scales dlogits by the incoming gradient), torch otherwise."""
+    if (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() >= 2 and 1 <= logits.shape[1] <= 8 and torch.is_grad_enabled()
+            and labels.dtype == torch.int64 and _seg_kernels_on()):
+        lo, hi = torch.aminmax(labels)
+        if int(lo) < 0 or int(hi) >= logits.shape[1]:       # (as F.cross_entropy: the kernel does not check the range itself)
+            raise ValueError(f"seg_cross_entropy: labels span [{int(lo)}, {int(hi)}], classes 0..{logits.shape[1] - 1}")
+        return _SegXent.apply(logits, labels)
+    return F.cross_entropy(logits, labels)

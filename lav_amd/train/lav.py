@@ -1,4 +1,4 @@
-"""The LAV trainer (lav/lav_final_v2.py:19-270 `train_lidar`, lav/lav_privileged_v2.py:16-160 `train_bev`) with one
+"""The LAV trainer (lav/lav_final_v2.py:19-270 `train_lidar`, lav/lav_privileged_v2.py:16-160 `train_bev`, :162-184 `train_seg`) with one
 process per GPU: when torch.distributed is initialised the trainable modules are wrapped in DistributedDataParallel
 (bucketed gradient all-reduce over RCCL/xGMI overlapped with backward; BatchNorm statistics stay per rank and buffers
 are broadcast from rank 0, which is what the reference's nn.DataParallel replicas amount to)."""
@@ -91,11 +91,22 @@ def _ddp(module, device, find_unused=False):
 
 class LAV:
     def __init__(self, cfg: TrainConfig, device, what: str = "lidar", checkpoints=None):
-        """what: "bev" (train_bev_v2.py) or "lidar" (train_full_v2.py).  checkpoints: optional dict name -> state_dict
-        ('bev', 'lidar', 'uniplanner'); missing ones are seeded random weights (the released files are LFS objects)."""
+        """what: "bev" (train_bev_v2.py), "lidar" (train_full_v2.py) or "seg" (train_seg.py).  checkpoints: optional dict name ->
+        state_dict ('bev', 'lidar', 'uniplanner', 'seg'); missing ones are seeded random weights (the released files are LFS objects)."""
+        if what not in ("bev", "lidar", "seg"):
+            raise ValueError(f"LAV: unknown stage {what!r} (bev, lidar or seg)")
         self.cfg, self.device, self.what = cfg, torch.device(device), what
         self.steps = 0
         ck = checkpoints or {}
+        if what == "seg":
+            # the camera segmenter alone: ERFNet over 1 + len(seg_channels) classes, Adam(lr) over all of it (lav_privileged_v2.py:29, 45)
+            from ..rgb import RGBSegmentationModel
+            self.seg_model = RGBSegmentationModel(cfg.seg_channels)
+            self.seg_model.load_state_dict(ck.get("seg") or synth.seeded_state_dict(self.seg_model, prefix="seg."))
+            self.seg_model.to(self.device).train()
+            self.seg_optim = optim.Adam(self.seg_model.parameters(), lr=cfg.lr)
+            self.seg_ddp = _ddp(self.seg_model, self.device)
+            return
         y_off = 1 + cfg.min_x / ((cfg.max_x - cfg.min_x) / 2)
         common = dict(pixels_per_meter=cfg.pixels_per_meter, crop_size=cfg.crop_size, feature_x_jitter=cfg.feature_x_jitter,
                       feature_angle_jitter=cfg.feature_angle_jitter, x_offset=0, y_offset=y_off, num_cmds=cfg.num_cmds,
@@ -156,6 +167,8 @@ class LAV:
         self.student_ddp = _ddp(self.student, self.device, find_unused=True)
 
     def state_dict(self, model_name):
+        if model_name == "seg":
+            return self.seg_model.state_dict()
         return {"bev": self.bev_planner, "lidar": getattr(self, "lidar_model", None),
                 "uniplanner": getattr(self, "uniplanner", None)}[model_name].state_dict()
 
@@ -176,6 +189,25 @@ class LAV:
             loss.backward()
         self.bev_optim.step()
         return _scalars(loss, terms)
+
+    def train_seg(self, rgb, sem):
+        """One Adam step of the camera segmenter on (B, H, W, 3) uint8 RGB images and (B, H, W) integer labels: pixel-wise
+        softmax cross-entropy, mean over B * H * W.  Returns the reference's opt_info: loss, rgb / sem / argmax prediction of
+        sample 0 (lav_privileged_v2.py:162-184)."""
+        from .hipnn import seg_cross_entropy
+        d = self.device
+        rgb = rgb.float().permute(0, 3, 1, 2).to(d)
+        sem = sem.long().to(d)
+        # LAV_TRAIN_CONV=hip: the ERFNet blocks and the loss on the training kernels (hipnn.nb1d_train, seg_cross_entropy); by default
+        # torch, which measured faster on this step (DESIGN 4.7d)
+        pred_sem = self.seg_ddp(rgb)
+        loss = seg_cross_entropy(pred_sem, sem)
+        self.seg_optim.zero_grad()
+        loss.backward()
+        self.seg_optim.step()
+        self.steps += 1
+        return dict(loss=float(loss.detach()), rgb=rgb[0].permute(1, 2, 0).byte().cpu().numpy(), sem=sem[0].cpu().numpy(),
+                    pred_sem=pred_sem[0].detach().cpu().numpy().argmax(0))
 
     def train_lidar(self, lidars, num_points, heatmaps, sizemaps, orimaps, bev, ego_locs, cmds, nxps, bras, locs, oris, typs,
                     num_objs):

@@ -1,4 +1,4 @@
-"""Command-line driver shared by train_bev_v2.py / train_full_v2.py and bench.py's training modes."""
+"""Command-line driver shared by train_bev_v2.py / train_full_v2.py / train_seg.py and bench.py's training modes."""
 from __future__ import annotations
 
 import argparse
@@ -10,7 +10,7 @@ import torch
 import torch.distributed as dist
 
 from .lav import LAV, TrainConfig
-from .synthetic import synthetic_bev_batch, synthetic_lidar_batch
+from .synthetic import synthetic_bev_batch, synthetic_lidar_batch, synthetic_seg_batch
 
 
 def setup_distributed():
@@ -188,6 +188,8 @@ def main(what):
     under the config's `data_dir` are read by lav_amd.data ('temporal_lidar_painted' / 'temporal_bev' loaders, every rank its
     own shard of each epoch).  What this build adds: --synthetic / --steps-per-epoch (seeded synthetic batches instead of a
     data set), --save-dir, --lidar / --bev / --uniplanner (checkpoints to start from), --max-points, --log-every."""
+    if what == "seg":
+        return main_seg()
     ap = argparse.ArgumentParser()
     ap.add_argument("--config-path", default=None, help="the reference's config_v2.yaml (training keys are read from it)")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
@@ -283,6 +285,81 @@ def main(what):
                               data="synthetic batches" if loader is None else f"{len(loader.dataset)} recorded frames",
                               lr=(lav.bev_optim if what == "bev" else lav.lidar_optim).param_groups[0]["lr"],
                               scheduler_epochs=(lav.bev_scheduler if what == "bev" else lav.lidar_scheduler).last_epoch)))
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def main_seg():
+    """Command line of lav/train_seg.py (same flags and defaults; --config-path defaults to the v2 agent's config, the consumer
+    of the segmenter): the camera images of the config's data_dir through the 'seg' loader, one Adam step per batch,
+    seg_{epoch}.th saved every --num-per-save epochs with RGBSegmentationModel's keys (the agent's `seg_model_dir`).  What this
+    build adds: --synthetic / --steps-per-epoch (seeded synthetic 288 x 256 images), --save-dir, --seg (a checkpoint to start from)."""
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config-path", default="config_v2.yaml", help="the reference's config_v2.yaml (seg_channels, data_dir)")
+    ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
+    ap.add_argument("--num-epoch", type=int, default=1)
+    ap.add_argument("--num-per-log", type=int, default=100, help="log per iter")
+    ap.add_argument("--num-per-save", type=int, default=1, help="save per epoch")
+    ap.add_argument("--batch-size", type=int, default=256, help="GLOBAL batch, split over the ranks")
+    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--num-workers", type=int, default=16, help="DataLoader workers (recorded routes only)")
+    ap.add_argument("--seed", type=int, default=2021)
+    ap.add_argument("--synthetic", action="store_true", help="seeded synthetic batches instead of the config's data_dir")
+    ap.add_argument("--steps-per-epoch", type=int, default=20, help="iterations that make one epoch of synthetic data")
+    ap.add_argument("--save-dir", default="checkpoints")
+    ap.add_argument("--seg", default=None, help="seg_*.th to start from")
+    args = ap.parse_args()
+    have_cfg = bool(args.config_path) and os.path.isfile(args.config_path)
+    if not args.synthetic and not have_cfg:
+        raise SystemExit(f"recorded routes are read from the data_dir of --config-path ({args.config_path} not found; or pass --synthetic)")
+    rank, world, device = setup_distributed()
+    if args.device == "cpu":
+        device = torch.device("cpu")
+    cfg = load_config(args.config_path if have_cfg else None, lr=args.lr, seed=args.seed)
+    if args.batch_size % world:
+        raise SystemExit(f"global batch {args.batch_size} is not divisible by {world} ranks")
+    per_rank = args.batch_size // world
+    ck = {"seg": torch.load(args.seg, map_location="cpu")} if args.seg else {}
+    lav = LAV(cfg, device, what="seg", checkpoints=ck)
+    loader = None
+    if not args.synthetic:
+        from ..data import get_data_loader
+        loader = get_data_loader("seg", args, rank=rank, world=world)
+        if len(loader) == 0:
+            raise SystemExit(f"{args.config_path}: data_dir holds fewer camera images than one batch of {args.batch_size}")
+    torch.manual_seed(args.seed)
+
+    def batches(epoch):
+        if loader is not None:
+            if world > 1:
+                loader.sampler.set_epoch(epoch)
+            yield from loader
+            return
+        for it in range(args.steps_per_epoch):
+            yield synthetic_seg_batch(per_rank, seed=cfg.seed + 1000003 * epoch + 1009 * it + 100 * rank,
+                                      num_classes=len(cfg.seg_channels) + 1, device=device)
+
+    global_it, t0 = 0, time.perf_counter()
+    for epoch in range(args.num_epoch):
+        for rgb, sem in batches(epoch):
+            info = lav.train_seg(rgb, sem)
+            if global_it % args.num_per_log == 0 and rank == 0:
+                print(global_it, dict(loss=round(info["loss"], 4)), flush=True)
+            global_it += 1
+        if (epoch + 1) % args.num_per_save == 0 and rank == 0:
+            os.makedirs(args.save_dir, exist_ok=True)
+            path = os.path.join(args.save_dir, f"seg_{epoch + 1}.th")
+            torch.save(lav.state_dict("seg"), path)
+            print(f"saved to {path}", flush=True)
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if rank == 0:
+        print(json.dumps(dict(what="seg", samples_per_s=round(args.batch_size * global_it / max(dt, 1e-9), 2), n_gpus=world,
+                              global_batch=args.batch_size, steps=global_it, epochs=args.num_epoch,
+                              data="synthetic batches" if loader is None else f"{len(loader.dataset)} recorded camera images",
+                              lr=lav.seg_optim.param_groups[0]["lr"])))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -1,7 +1,7 @@
 """Synthetic training batches with the tensor contracts of the reference's data loaders: seeded, no
 dataset on disk.  Shapes: lidar (B, Nmax, 11) + num_points (B,), heat (B,2,H,W), size / ori (B,2,H,W), bev
 (B,9,H,W), ego_locs (B,T+1,2), cmds (B,), nxps (B,2), bras (B,), locs (B,N+1,T+1,2), oris (B,N+1), typs (B,N+1),
-num_objs (B,)."""
+num_objs (B,); camera segmentation: rgb (B,H,W,3) uint8, sem (B,H,W) int64."""
 from __future__ import annotations
 
 import numpy as np
@@ -66,3 +66,15 @@ def synthetic_lidar_batch(B, seed=2021, max_points=120000, num_plan=20, num_objs
     bev_args = synthetic_bev_batch(B, seed=seed + 7, num_plan=num_plan, num_objs=num_objs, hw=hw, device=device)
     t = lambda a: torch.from_numpy(a).to(device)
     return (t(lidars), t(num_points), t(heat), t(size), t(ori)) + bev_args
+
+
+def synthetic_seg_batch(B, seed=2021, hw=(288, 256), num_classes=5, device="cpu"):
+    """train_seg's arguments: (rgb (B, H, W, 3) uint8, sem (B, H, W) int64 labels in [0, num_classes)).  8 x 8 blocks of one
+    class each; a block's colour is its class's colour plus noise, so the labels can be learnt from the image."""
+    rng = np.random.default_rng(seed)
+    H, W = hw
+    palette = rng.integers(0, 256, (num_classes, 3))
+    cells = rng.integers(0, num_classes, (B, H // 8 + 1, W // 8 + 1))
+    sem = np.kron(cells, np.ones((1, 8, 8), np.int64))[:, :H, :W]
+    rgb = np.clip(palette[sem] + rng.normal(0, 16, (B, H, W, 3)), 0, 255).astype(np.uint8)
+    return torch.from_numpy(rgb).to(device), torch.from_numpy(np.ascontiguousarray(sem)).to(device)
