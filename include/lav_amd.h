@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 29
+#define LAV_ABI_VERSION 30
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -401,6 +401,21 @@ int lav_extract_peaks(const float *heat, int ncls, int h, int w, int ks, int max
 int lav_attn_pool(const float *x, int batch, int C, int N, int heads, const float *u, const float *dots_bias,
                   const float *w_v, const float *b_v, float *out, void *stream);
 
+/* Train mode of the same pooling (ABI 30; the brake-net trainer, lav_amd.train.hipnn.attn_pool_train).  q [heads][dh] (dh = C / heads,
+ * even), w_kv [2C][C] and b_kv [2C] = linear_kv (keys first), pe [N][dh] the positional encoding, scale = dh^-1/2: the LIVE
+ * parameters, folded on the device (no host preparation).  C <= 1024 (any multiple of the heads), N <= 4096.  fp32 arithmetic, every
+ * sum in an order fixed by the shape, no atomics: bit-reproducible.
+ *   forward:  u [heads][C], dots_bias [heads][N] (the folding, kept for the backward), out [batch][C], and the saved
+ *             p [batch][heads][N] (soft-max over the tokens) and xbar [batch][heads][C] (= sum_n p x_n).  Two launches.
+ *   backward: from dout [batch][C]: dx [batch][C][N], dq [heads * dh], dw_kv [2C][C], db_kv [2C] (the parameter gradients summed
+ *             over the batch, images in order).  Four launches; workspace lav_attn_train_workspace_bytes. */
+size_t lav_attn_train_workspace_bytes(int batch, int C, int N, int heads);
+int lav_attn_train_forward(const float *x, int batch, int C, int N, int heads, const float *q, const float *w_kv, const float *b_kv,
+                           const float *pe, float scale, float *u, float *dots_bias, float *out, float *p, float *xbar, void *stream);
+int lav_attn_train_backward(const float *x, int batch, int C, int N, int heads, const float *q, const float *w_kv, const float *b_kv,
+                            const float *pe, float scale, const float *u, const float *p, const float *xbar, const float *dout, float *dx,
+                            float *dq, float *dw_kv, float *db_kv, void *workspace, size_t workspace_bytes, void *stream);
+
 /*
  * Health counter of a frame: counter2[0] += how many of the n (<= 8) float tensors hold a NaN or an Inf, counter2[1] += 1.
  * Sticky and device resident: enqueued behind a frame's last kernels (it is part of the HIP graphs), read by the host when it
@@ -668,6 +683,14 @@ int lav_pair_train_backward(const float *x, const float *t, const float *dz, con
 size_t lav_seg_xent_workspace_bytes(void);
 int lav_seg_xent_forward(const float *logits, const long long *labels, int batch, int classes, long plane, float *loss, float *dlogits,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* The same loss on nearest-upsampled logits (ABI 30): F.cross_entropy(F.interpolate(logits, scale_factor=scale), labels) for
+ * logits [batch][classes][h][w] (classes <= 8) and labels [batch][scale*h][scale*w] of label_bytes 1 (uint8) or 8 (int64), without
+ * the upsampled map: per low-resolution cell, from the label histogram cnt of its scale x scale block, loss += s^2 lse - sum_k cnt_k
+ * logit_k and dlogits = (s^2 softmax - cnt) / (batch s^2 h w).  Same partials, workspace and label contract as lav_seg_xent_forward
+ * (lav_amd.train.hipnn.seg_cross_entropy_up checks labels and shapes before the launch). */
+int lav_seg_xent_up_forward(const float *logits, const void *labels, int label_bytes, int batch, int classes, int h, int w, int scale,
+                            float *loss, float *dlogits, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LAV_AMD_LIB") or os.path.join(HERE, "liblav_amd.so")   # LAV_AMD_LIB: A/B a second build
 
-ABI_VERSION = 29
+ABI_VERSION = 30
 MAX_CAM = 4
 
 
@@ -115,6 +115,10 @@ SIGNATURES = {
     "lav_pair_train_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "lav_seg_xent_workspace_bytes": (_Z, []),
     "lav_seg_xent_forward": (_I, [_P, _P, _I, _I, C.c_long, _P, _P, _P, _Z, _P]),
+    "lav_seg_xent_up_forward": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "lav_attn_train_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "lav_attn_train_forward": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P, _P]),
+    "lav_attn_train_backward": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "lav_bn_train_forward": (_I, [_P, _P, _P, _I, _I, C.c_long, _P, _P, C.c_double, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "lav_bn_train_backward": (_I, [_P, _P, _P, _I, _I, C.c_long, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "lav_bn_train_amax_count": (_I, [_I, _I, C.c_long]),

@@ -15,6 +15,8 @@
 //   lav_seg_xent_forward     k_xent          per pixel softmax cross-entropy (classes <= 8, labels in [0, classes)), dlogits = (softmax - onehot) / N,
 //                                            per-workgroup float64 partial sums of the loss
 //                            k_xent_final    partials summed in order by one workgroup
+//   lav_seg_xent_up_forward  k_xent_up       the same loss on the nearest s x-upsampled logits (the brake net's seg head), one thread per
+//                                            low-resolution cell from the label histogram of its s x s block; k_xent_final as above
 //
 // No float atomics anywhere: every sum is taken in an order fixed by the shape, so the results are bit-reproducible.
 // Shapes: (channels, width) in {(16, 128), (64, 64), (128, 32)} (ERFNet's stages on 256-pixel-wide images), any batch and
@@ -273,6 +275,56 @@ __global__ __launch_bounds__(PT_THREADS) void k_xent_final(const double *__restr
     if (threadIdx.x == 0) loss[0] = (float)(tot * inv_n);
 }
 
+// F.cross_entropy(F.interpolate(logits, scale_factor=s), labels) without the upsampled map: inside one s x s block the logits are
+// constant, so one thread per low-resolution cell takes the block's label histogram cnt and adds s^2 lse - sum_k cnt_k logit_k to
+// the loss; dlogits = (s^2 softmax - cnt) / N (N = batch * s^2 * plane)
+template <typename L>
+__global__ __launch_bounds__(PT_THREADS) void k_xent_up(const float *__restrict__ logits, const L *__restrict__ labels, int B, int NC, int h,
+                                                        int w, int s, float inv_n, float *__restrict__ dlogits, double *__restrict__ partial) {
+    __shared__ double lds[PT_THREADS];
+    const long plane = (long)h * w, n = (long)B * plane, Wf = (long)w * s, Pf = plane * s * s;
+    const float s2 = (float)(s * s);
+    double sum = 0.0;
+    for (long p = (long)blockIdx.x * PT_THREADS + threadIdx.x; p < n; p += (long)gridDim.x * PT_THREADS) {
+        const long b = p / plane, cell = p - b * plane, i = cell / w, j = cell - i * w;
+        const float *lg = logits + b * NC * plane + cell;
+        float v[XENT_MAX_C], e[XENT_MAX_C], cnt[XENT_MAX_C];
+        float m = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < XENT_MAX_C; ++c) {
+            v[c] = c < NC ? lg[c * plane] : -INFINITY;
+            m = fmaxf(m, v[c]);
+            cnt[c] = 0.f;
+        }
+        float se = 0.f;
+#pragma unroll
+        for (int c = 0; c < XENT_MAX_C; ++c) {
+            e[c] = c < NC ? expf(v[c] - m) : 0.f;
+            se += e[c];
+        }
+        const L *lb = labels + b * Pf + i * s * Wf + j * s;
+        for (int di = 0; di < s; ++di)
+            for (int dj = 0; dj < s; ++dj) {
+                const long long lab = (long long)lb[di * Wf + dj];      // (a label outside [0, classes) counts nowhere: memory safety only)
+#pragma unroll
+                for (int c = 0; c < XENT_MAX_C; ++c) cnt[c] += lab == c ? 1.f : 0.f;
+            }
+        const float lse = m + logf(se), rse = 1.f / se;
+        double cl = (double)s2 * (double)lse;
+        float *dl = dlogits + b * NC * plane + cell;
+#pragma unroll
+        for (int c = 0; c < XENT_MAX_C; ++c) {
+            if (c < NC) {
+                cl -= (double)cnt[c] * (double)v[c];
+                dl[c * plane] = (s2 * (e[c] * rse) - cnt[c]) * inv_n;
+            }
+        }
+        sum += cl;
+    }
+    const double tot = block_sum(sum, lds);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
 int wgrad_groups(int rows) { return std::max(1, std::min(rows, WG_MAX_GROUPS)); }
 
 template <int C, int W>
@@ -365,6 +417,32 @@ extern "C" int lav_seg_xent_forward(const float *logits, const long long *labels
     hipLaunchKernelGGL(k_xent, dim3((unsigned)groups), dim3(PT_THREADS), 0, st, logits, labels, batch, classes, plane, (float)(1.0 / (double)n),
                        dlogits, partial);
     hipLaunchKernelGGL(k_xent_final, dim3(1), dim3(PT_THREADS), 0, st, partial, groups, 1.0 / (double)n, loss);
+    timer_end(tok, st);
+    LAV_LAUNCH_CHECK();
+    return LAV_OK;
+}
+
+extern "C" int lav_seg_xent_up_forward(const float *logits, const void *labels, int label_bytes, int batch, int classes, int h, int w, int scale,
+                                       float *loss, float *dlogits, void *workspace, size_t workspace_bytes, void *stream) {
+    LAV_REQUIRE(logits && labels && loss && dlogits && workspace, "lav_seg_xent_up_forward: null pointer");
+    LAV_REQUIRE(label_bytes == 1 || label_bytes == 8, "lav_seg_xent_up_forward: labels of %d bytes (1: uint8, 8: int64)", label_bytes);
+    LAV_REQUIRE(classes >= 1 && classes <= XENT_MAX_C, "lav_seg_xent_up_forward: %d classes (1..%d)", classes, XENT_MAX_C);
+    LAV_REQUIRE(batch >= 1 && h >= 1 && w >= 1 && scale >= 1 && scale <= 64, "lav_seg_xent_up_forward: batch %d, %d x %d, scale %d", batch, h, w, scale);
+    LAV_REQUIRE((long)batch * h * w * scale * scale * std::max(classes, 8) < (1L << 40), "lav_seg_xent_up_forward: too large");
+    LAV_REQUIRE(workspace_bytes >= lav_seg_xent_workspace_bytes(), "lav_seg_xent_up_forward: workspace smaller than lav_seg_xent_workspace_bytes");
+    const long n = (long)batch * h * w;
+    const double inv_n = 1.0 / ((double)n * scale * scale);
+    const int groups = (int)std::min<long>((n + PT_THREADS - 1) / PT_THREADS, XENT_GROUPS);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double *partial = static_cast<double *>(workspace);
+    const int tok = timer_begin("seg_xent_up", st);
+    if (label_bytes == 1)
+        hipLaunchKernelGGL(k_xent_up<unsigned char>, dim3((unsigned)groups), dim3(PT_THREADS), 0, st, logits,
+                           static_cast<const unsigned char *>(labels), batch, classes, h, w, scale, (float)inv_n, dlogits, partial);
+    else
+        hipLaunchKernelGGL(k_xent_up<long long>, dim3((unsigned)groups), dim3(PT_THREADS), 0, st, logits,
+                           static_cast<const long long *>(labels), batch, classes, h, w, scale, (float)inv_n, dlogits, partial);
+    hipLaunchKernelGGL(k_xent_final, dim3(1), dim3(PT_THREADS), 0, st, partial, groups, inv_n, loss);
     timer_end(tok, st);
     LAV_LAUNCH_CHECK();
     return LAV_OK;

@@ -1,7 +1,8 @@
 """Recorded routes -> training batches: the loaders behind `train_bev_v2.py` ('temporal_bev'), `train_full_v2.py`
-('temporal_lidar_painted') and `train_seg.py` ('seg'), and the single-frame variants ('bev', 'lidar', 'lidar_painted').
+('temporal_lidar_painted'), `train_seg.py` ('seg') and `train_bra_v2.py` ('bra'), and the single-frame variants ('bev', 'lidar',
+'lidar_painted').
 
-Follows lav/utils/datasets/{basic,bev,temporal_bev,lidar,lidar_painted,temporal_lidar_painted,seg}_dataset.py and
+Follows lav/utils/datasets/{basic,bev,temporal_bev,lidar,lidar_painted,temporal_lidar_painted,seg,bra}_dataset.py and
 lav/utils/point_painting.py: same LMDB keys, same arithmetic (float32 reads, float64 geometry), same tuple layout, and the
 same ORDER of random draws (torch.rand for the crop jitter / rotation, np.random for the stacked sweeps' pose jitter and
 the point shuffle), so that a seeded reference loader and a seeded loader of this module return the same sample
@@ -9,10 +10,10 @@ the point shuffle), so that a seeded reference loader and a seeded loader of thi
 Routes are read with lav_amd.data.lmdb_ro (no liblmdb here), images with lav_amd.data.image (no OpenCV here).
 
 Differences from the reference, all deliberate: route directories are visited in sorted order (the reference takes
-`glob` order, which is file-system dependent); the 'seg' loader applies no image augmentation (the reference's
+`glob` order, which is file-system dependent); the 'seg' and 'bra' loaders apply no image augmentation (the reference's
 `augment(0.5)` - blur, noise, pixel dropout, colour, contrast, grayscale and elastic warps - is built on imgaug, which this
-build does not have: its samples are the reference's with the augmenter as the identity); the 'rgb' and 'bra' loaders (the
-brake net's trainer is outside this repository's scope) are not provided.
+build does not have: their samples are the reference's with the augmenter as the identity); the 'rgb' loader (the v1 brake
+trainer's, lav/train_bra.py) is not provided.
 """
 from __future__ import annotations
 
@@ -431,8 +432,34 @@ class SegmentationDataset(RouteFrames):
         return np.ascontiguousarray(rgb[..., ::-1]), filter_sem(sem, self.seg_channels)
 
 
+BRA_LABELS = (4, 10, 18)          # bra_dataset.py:34-35 hard-codes them (not the config's seg_channels)
+
+
+class BrakePredictionDataset(RouteFrames):
+    """'bra' (bra_dataset.py): one sample per frame.  rgb: the middle three of camera_yaws' images (rgb_{n//2-1}, rgb_{n//2},
+    rgb_{n//2+1}) side by side, BGR -> RGB, (H, 3W, 3) uint8; tel_rgb: the telephoto image without its bottom crop_tel_bottom
+    rows, RGB uint8; sem / tel_sem: their labels filter_sem(., [4, 10, 18]) (uint8, the same crop for tel_sem); bra: the frame's
+    brake flag (int).  Returned as (rgb, tel_rgb, sem, tel_sem, bra)."""
+
+    def _img(self, txn, tag, index):
+        mode = image.IMREAD_COLOR if "rgb" in tag else image.IMREAD_GRAYSCALE
+        return image.imdecode(np.frombuffer(txn.get(f"{tag}_{index:05d}".encode()), np.uint8), mode)
+
+    def __getitem__(self, idx):
+        txn, index = self.txn_map[idx], self.idx_map[idx]
+        mid = len(self.camera_yaws) // 2
+        cams = (mid - 1, mid, mid + 1)
+        rgb = np.concatenate([self._img(txn, f"rgb_{c}", index) for c in cams], axis=1)[..., ::-1]
+        sem = filter_sem(np.concatenate([self._img(txn, f"sem_{c}", index) for c in cams], axis=1), BRA_LABELS)
+        crop = self.crop_tel_bottom
+        tel_rgb = self._img(txn, "tel_rgb", index)[:-crop][..., ::-1]
+        tel_sem = filter_sem(self._img(txn, "tel_sem", index), BRA_LABELS)[:-crop]
+        bra = int(read_array(txn, "bra", index, np.uint8)[0, 0])
+        return np.ascontiguousarray(rgb), np.ascontiguousarray(tel_rgb), sem, np.ascontiguousarray(tel_sem), bra
+
+
 LOADERS = {"bev": BEVDataset, "temporal_bev": TemporalBEVDataset, "lidar": LiDARDataset, "lidar_painted": LiDARPaintedDataset,
-           "temporal_lidar_painted": TemporalLiDARPaintedDataset, "seg": SegmentationDataset}
+           "temporal_lidar_painted": TemporalLiDARPaintedDataset, "seg": SegmentationDataset, "bra": BrakePredictionDataset}
 
 
 def get_data_loader(data_type, args, rank: int = 0, world: int = 1):
@@ -441,8 +468,8 @@ def get_data_loader(data_type, args, rank: int = 0, world: int = 1):
     draws its own disjoint shard of each epoch (DistributedSampler; call loader.sampler.set_epoch(epoch)) in batches of
     batch_size / world."""
     if data_type not in LOADERS:
-        raise NotImplementedError(f"data loader {data_type!r}: this build provides {sorted(LOADERS)} (the camera-model loaders "
-                                  "'rgb' and 'bra' belong to the brake net's trainer, outside its scope)")
+        raise NotImplementedError(f"data loader {data_type!r}: this build provides {sorted(LOADERS)} (the reference's 'rgb' loader "
+                                  "feeds the v1 trainer train_bra.py, which is not part of it)")
     dataset = LOADERS[data_type](args.config_path, seed=args.seed)
     common = dict(num_workers=args.num_workers, drop_last=True, pin_memory=torch.cuda.is_available())
     if world > 1:

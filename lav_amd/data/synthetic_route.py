@@ -1,6 +1,7 @@
 """Writes a small synthetic route in the data collector's LMDB layout (the keys lav/utils/datasets reads: `len`, `town`,
 and per frame t `id_`, `loc_`, `ori_`, `bbox_`, `type_`, `nxp_`, `cmd_`, `bra_`, `lidar_`, `lidar_sem_`, `map_{0..11}_`; with
-cameras=N also `rgb_{0..N-1}_` (colour PNG) and `sem_{0..N-1}_` (grayscale PNG of CARLA class ids), what the 'seg' loader reads).
+cameras=N also `rgb_{0..N-1}_` (colour PNG) and `sem_{0..N-1}_` (grayscale PNG of CARLA class ids), what the 'seg' loader reads;
+with tel also `tel_rgb_` / `tel_sem_`, which the 'bra' loader reads besides the three middle cameras).
 No recorded data ships with the reference (Git-LFS pointers), so this is what the loader tests and a no-download smoke
 run of the trainers read:
 
@@ -34,11 +35,25 @@ def camera_images(r, cameras: int, hw=(72, 64)):
     return out
 
 
+def tel_images(r, hw=(72, 64)):
+    """{key stem: PNG bytes} of one frame's telephoto camera: `tel_rgb` and `tel_sem`, drawn like camera_images' views."""
+    H, W = hw
+    classes = np.array([0, 1, 4, 6, 7, 8, 10, 12, 18], np.uint8)
+    palette = r.integers(0, 256, (len(classes), 3))
+    cells = r.integers(0, len(classes), (H // 8 + 1, W // 8 + 1))
+    k = np.kron(cells, np.ones((8, 8), np.int64))[:H, :W]
+    rgb = np.clip(palette[k] + r.normal(0, 12, (H, W, 3)), 0, 255).astype(np.uint8)
+    return {"tel_rgb": image.imencode_png(rgb), "tel_sem": image.imencode_png(classes[k])}
+
+
 def make_route(path: str, seed: int = 0, frames: int = 40, points: int = 2500, town: str = "Town01", sem_channels: int = 4,
-               cameras: int = 0) -> None:
-    """cameras > 0: also per-frame camera images (own random stream: the other records are the same as without them)."""
+               cameras: int = 0, camera_hw=(72, 64), tel: bool = False, tel_hw=(72, 64)) -> None:
+    """cameras > 0: also per-frame camera images of camera_hw (H, W) pixels; tel: also the telephoto camera's `tel_rgb_` /
+    `tel_sem_` of tel_hw (what the 'bra' loader reads).  Each has its own random stream: the other records are the same as
+    without them, and the camera images the same with or without tel."""
     r = np.random.default_rng(seed)
     rc = np.random.default_rng([seed, 7919])
+    rt = np.random.default_rng([seed, 7927])
     items = {b"len": str(frames).encode(), b"town": town.encode()}
     f32 = lambda a: np.asarray(a, np.float32).tobytes()
     # actors: ego (id 100, vehicle) drives a gentle arc; vehicles / pedestrians around it, some leave early
@@ -88,18 +103,22 @@ def make_route(path: str, seed: int = 0, frames: int = 40, points: int = 2500, t
             maps[1 if typ[k] == 1 else 2][m] = 255
         for ch in range(12):
             items[f"map_{ch}_{t:05d}".encode()] = image.imencode_png(maps[ch])
-        for stem, png in camera_images(rc, cameras).items():
+        for stem, png in camera_images(rc, cameras, camera_hw).items():
             items[f"{stem}_{t:05d}".encode()] = png
+        if tel:
+            for stem, png in tel_images(rt, tel_hw).items():
+                items[f"{stem}_{t:05d}".encode()] = png
         pos = pos + speed[:, None] * np.stack([np.cos(np.deg2rad(ang)), np.sin(np.deg2rad(ang))], 1)
     lmdb_ro.write(path, items.items())
 
 
-def make_dataset(data_dir: str, routes: int = 2, frames: int = 40, seed: int = 0, points: int = 2500, cameras: int = 0) -> None:
+def make_dataset(data_dir: str, routes: int = 2, frames: int = 40, seed: int = 0, points: int = 2500, cameras: int = 0,
+                 camera_hw=(72, 64), tel: bool = False, tel_hw=(72, 64)) -> None:
     os.makedirs(data_dir, exist_ok=True)
     towns = ["Town01", "Town03", "Town02", "Town06"]
     for i in range(routes):
         make_route(os.path.join(data_dir, f"route_{i:03d}"), seed=seed + i, frames=frames, points=points, town=towns[i % len(towns)],
-                   cameras=cameras)
+                   cameras=cameras, camera_hw=camera_hw, tel=tel, tel_hw=tel_hw)
 
 
 if __name__ == "__main__":
@@ -110,6 +129,9 @@ if __name__ == "__main__":
     ap.add_argument("--points", type=int, default=2500)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--cameras", type=int, default=0, help="also write rgb_i / sem_i camera images (train_seg.py's data)")
+    ap.add_argument("--camera-hw", type=int, nargs=2, default=(72, 64), metavar=("H", "W"), help="camera image size")
+    ap.add_argument("--tel", action="store_true", help="also write the telephoto camera's tel_rgb / tel_sem (train_bra_v2.py's data)")
+    ap.add_argument("--tel-hw", type=int, nargs=2, default=(72, 64), metavar=("H", "W"), help="telephoto image size (before crop_tel_bottom)")
     a = ap.parse_args()
-    make_dataset(a.data_dir, a.routes, a.frames, a.seed, a.points, a.cameras)
+    make_dataset(a.data_dir, a.routes, a.frames, a.seed, a.points, a.cameras, tuple(a.camera_hw), a.tel, tuple(a.tel_hw))
     print(f"wrote {a.routes} route(s) of {a.frames} frames under {a.data_dir}")

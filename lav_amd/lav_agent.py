@@ -45,6 +45,18 @@ def get_entry_point():
     return "LAVAgent"
 
 
+def fit_bra_seg_head(bra_model, state_dict):
+    """Rebuild bra_model.seg_head at the class count of a brake checkpoint's seg head when it differs from the module's: the
+    reference trains RGBBrakePredictionModel([4, 10, 18]) (lav_privileged_v2.py:30, 4 classes) while the agent builds it from
+    seg_channels (5 classes).  Inference never runs the seg head; every other key and shape still has to match the strict load."""
+    from .rgb import SegmentationHead
+    w = state_dict.get("seg_head.upconv.9.weight")
+    mine = bra_model.seg_head.upconv[9].weight
+    if w is not None and w.dim() == mine.dim() and w.shape[0] != mine.shape[0] and tuple(w.shape[1:]) == tuple(mine.shape[1:]):
+        bra_model.seg_head = SegmentationHead(bra_model.seg_head.upconv[0].in_channels, int(w.shape[0]))
+    return bra_model
+
+
 def _rotate(x, y, theta):
     c, s = np.cos(theta), np.sin(theta)
     return np.array([[c, -s], [s, c]]) @ [x, y]
@@ -94,7 +106,10 @@ class LAVAgent(AutonomousAgent):
                                      (self.uniplanner, self.uniplanner_dir, "uni."),
                                      (self.seg_model, self.seg_model_dir, "seg."),
                                      (self.bra_model, self.bra_model_dir, "bra.")):
-            module.load_state_dict(self._checkpoint(module, path, prefix))
+            sd = self._checkpoint(module, path, prefix)
+            if module is self.bra_model:
+                fit_bra_seg_head(module, sd)
+            module.load_state_dict(sd)
             module.eval().to(self.device)
 
         extra = dict(points_per_tick=self.points_per_tick) if self.hip_graphs else {}

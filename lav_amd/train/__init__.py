@@ -8,4 +8,5 @@ backward, the GRU recurrences (forward + backward), BatchNorm on batch statistic
 the frozen teacher's inference kernels and the device-side re-packing behind the per-step log inference."""
 from .losses import DetLoss, build_seg_mask, bev_losses, lidar_losses  # noqa: F401
 from .lav import LAV, TrainConfig  # noqa: F401
-from .synthetic import synthetic_bev_batch, synthetic_lidar_batch  # noqa: F401
+from .synthetic import synthetic_bev_batch, synthetic_bra_batch, synthetic_lidar_batch  # noqa: F401
+from .brake import BrakeTrainer  # noqa: F401

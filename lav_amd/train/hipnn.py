@@ -534,3 +534,122 @@ def seg_cross_entropy(logits, labels):
             raise ValueError(f"seg_cross_entropy: labels span [{int(lo)}, {int(hi)}], classes 0..{logits.shape[1] - 1}")
         return _SegXent.apply(logits, labels)
     return F.cross_entropy(logits, labels)
+
+
+# ------------------------------------------------------------------------------------------------------------------ brake net
+# The brake net's training step (lav_amd.train.brake.BrakeTrainer): the two attention poolings on lav_attn_train_forward / _backward
+# (csrc/attn.hip: the projections folded around the single query on the device, fixed-order parameter gradients) and the seg head's
+# loss on lav_seg_xent_up_forward (the x4 nearest upsampling folded into the loss).  Both compute in fp32.  Which pieces of the step
+# run on liblav_amd by default is brake_piece_on's table, set from profiles/train_bra_probe.json: at the reference's
+# batch 52 every piece measured faster than the torch ops it replaces (forward + backward: attention 0.42 / 0.30 ms vs 0.67 / 0.48,
+# loss 0.12 / 0.11 vs 1.17 / 0.51; step 48.9 ms vs 57.2 all-torch), so all are on.
+BRAKE_PIECES = ("trunk", "attn", "xent")
+_BRAKE_DEFAULT = dict(trunk=True, attn=True, xent=True)
+
+
+def brake_piece_on(piece: str) -> bool:
+    """Whether `piece` of the brake-net step ("trunk": ResNet-18 on hipnn.conv_module + bn_act and the seg head's BatchNorm on bn_act;
+    "attn": attn_pool_train; "xent": seg_cross_entropy_up) runs on liblav_amd.  LAV_TRAIN_CONV=torch: none (the all-torch step);
+    LAV_TRAIN_CONV=hip: all; else LAV_TRAIN_BRA (a comma list of pieces, "" for none) if set; else the measured default."""
+    if piece not in BRAKE_PIECES:
+        raise ValueError(f"brake_piece_on: unknown piece {piece!r} ({', '.join(BRAKE_PIECES)})")
+    mode = os.environ.get("LAV_TRAIN_CONV")
+    if mode == "torch":
+        return False
+    if mode == "hip":
+        return True
+    sel = os.environ.get("LAV_TRAIN_BRA")
+    if sel is not None:
+        return piece in [s.strip() for s in sel.split(",")]
+    return _BRAKE_DEFAULT[piece]
+
+
+class _AttnTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, q, w_kv, b_kv, heads, pe):
+        x = x.contiguous()
+        B, C, H, W = x.shape
+        N = H * W
+        q, w_kv, b_kv = (t.detach().contiguous() for t in (q, w_kv, b_kv))
+        scale = float((C // heads) ** -0.5)
+        u = torch.empty((heads, C), dtype=torch.float32, device=x.device)
+        bias = torch.empty((heads, N), dtype=torch.float32, device=x.device)
+        out = torch.empty((B, C), dtype=torch.float32, device=x.device)
+        p = torch.empty((B, heads, N), dtype=torch.float32, device=x.device)
+        xbar = torch.empty((B, heads, C), dtype=torch.float32, device=x.device)
+        check(_lib.load().lav_attn_train_forward(_ptr(x), B, C, N, int(heads), _ptr(q), _ptr(w_kv), _ptr(b_kv), _ptr(pe), scale, _ptr(u),
+                                                 _ptr(bias), _ptr(out), _ptr(p), _ptr(xbar), _stream()), "lav_attn_train_forward")
+        ctx.save_for_backward(x, q, w_kv, b_kv, pe, u, p, xbar)
+        ctx.cfg = (int(heads), scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, q, w_kv, b_kv, pe, u, p, xbar = ctx.saved_tensors
+        heads, scale = ctx.cfg
+        dout = dout.contiguous()
+        B, C, H, W = x.shape
+        N = H * W
+        lib = _lib.load()
+        dx = torch.empty_like(x)
+        dq = torch.empty_like(q)
+        dw, db = torch.empty_like(w_kv), torch.empty_like(b_kv)
+        ws = ops_mod._workspace("attn_train", lib.lav_attn_train_workspace_bytes(B, C, N, heads), x.device)
+        check(lib.lav_attn_train_backward(_ptr(x), B, C, N, heads, _ptr(q), _ptr(w_kv), _ptr(b_kv), _ptr(pe), scale, _ptr(u), _ptr(p), _ptr(xbar),
+                                          _ptr(dout), _ptr(dx), _ptr(dq), _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), _stream()),
+              "lav_attn_train_backward")
+        return dx, dq, dw, db, None, None
+
+
+def attn_pool_train(attn, x: torch.Tensor) -> torch.Tensor:
+    """lav_amd.rgb.Attention's train-mode forward, attn(x) for x [B, C, h, w] -> [B, C], with forward and backward on
+    lav_attn_train_* (gradients for x, attn.q and attn.linear_kv).  On a CPU tensor, outside autograd, or with LAV_TRAIN_CONV=torch:
+    the module's own torch ops."""
+    if (not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or not torch.is_grad_enabled() or not attn.training
+            or os.environ.get("LAV_TRAIN_CONV") == "torch"):
+        return attn(x)
+    from ..rgb import _pe_on
+    C, N = x.shape[1], x.shape[2] * x.shape[3]
+    if C % attn.num_heads or (C // attn.num_heads) % 2 or C > 1024 or N > 4096:
+        raise ValueError(f"attn_pool_train: {C} channels / {attn.num_heads} heads, {N} tokens unsupported (C <= 1024, even head width, N <= 4096)")
+    ops_mod.train_work["attn_train_calls"] = ops_mod.train_work.get("attn_train_calls", 0) + 1
+    return _AttnTrain.apply(x, attn.q, attn.linear_kv.weight, attn.linear_kv.bias, attn.num_heads, _pe_on(x.device, C // attn.num_heads, N))
+
+
+class _SegXentUp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, scale):
+        logits = logits.contiguous()
+        labels = labels.contiguous()
+        B, K, h, w = logits.shape
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        dlogits = torch.empty_like(logits)
+        lib = _lib.load()
+        ws = ops_mod._workspace("seg_xent", lib.lav_seg_xent_workspace_bytes(), logits.device)
+        check(lib.lav_seg_xent_up_forward(_ptr(logits), _ptr(labels), labels.element_size(), B, K, h, w, int(scale), _ptr(loss), _ptr(dlogits),
+                                          _ptr(ws), ws.numel(), _stream()), "lav_seg_xent_up_forward")
+        ctx.save_for_backward(dlogits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogits,) = ctx.saved_tensors
+        return dlogits * g, None, None
+
+
+def seg_cross_entropy_up(logits: torch.Tensor, labels: torch.Tensor, scale: int) -> torch.Tensor:
+    """F.cross_entropy(F.interpolate(logits, scale_factor=scale), labels) (mean reduction) for logits [B, K, h, w] (K <= 8) and labels
+    [B, scale h, scale w] (uint8 or int64): lav_seg_xent_up_forward on the GPU, without the upsampled map or its gradient.  Labels
+    outside [0, K) and labels that are not exactly scale x the logits raise ValueError before the launch.  On a CPU tensor, outside
+    autograd, or with LAV_TRAIN_CONV=torch: the torch ops themselves."""
+    scale = int(scale)
+    if logits.dim() != 4 or labels.dim() != 3 or scale < 1 or tuple(labels.shape) != (logits.shape[0], scale * logits.shape[2], scale * logits.shape[3]):
+        raise ValueError(f"seg_cross_entropy_up: labels {tuple(labels.shape)} are not {scale} x the logits {tuple(logits.shape)}")
+    if (not logits.is_cuda or logits.dtype != torch.float32 or not 1 <= logits.shape[1] <= 8 or labels.dtype not in (torch.uint8, torch.int64)
+            or not torch.is_grad_enabled() or os.environ.get("LAV_TRAIN_CONV") == "torch" or scale > 64):
+        return F.cross_entropy(F.interpolate(logits, scale_factor=scale), labels.long())
+    lo, hi = torch.aminmax(labels)
+    if int(lo) < 0 or int(hi) >= logits.shape[1]:       # (as F.cross_entropy: the kernel does not check the range itself)
+        raise ValueError(f"seg_cross_entropy_up: labels span [{int(lo)}, {int(hi)}], classes 0..{logits.shape[1] - 1}")
+    ops_mod.train_work["seg_xent_up_calls"] = ops_mod.train_work.get("seg_xent_up_calls", 0) + 1
+    return _SegXentUp.apply(logits, labels, scale)

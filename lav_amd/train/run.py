@@ -1,4 +1,4 @@
-"""Command-line driver shared by train_bev_v2.py / train_full_v2.py / train_seg.py and bench.py's training modes."""
+"""Command-line driver shared by train_bev_v2.py / train_full_v2.py / train_seg.py / train_bra_v2.py and bench.py's training modes."""
 from __future__ import annotations
 
 import argparse
@@ -190,6 +190,8 @@ def main(what):
     data set), --save-dir, --lidar / --bev / --uniplanner (checkpoints to start from), --max-points, --log-every."""
     if what == "seg":
         return main_seg()
+    if what == "bra":
+        return main_bra()
     ap = argparse.ArgumentParser()
     ap.add_argument("--config-path", default=None, help="the reference's config_v2.yaml (training keys are read from it)")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
@@ -360,6 +362,89 @@ def main_seg():
                               global_batch=args.batch_size, steps=global_it, epochs=args.num_epoch,
                               data="synthetic batches" if loader is None else f"{len(loader.dataset)} recorded camera images",
                               lr=lav.seg_optim.param_groups[0]["lr"])))
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def main_bra():
+    """Command line of lav/train_bra_v2.py (same flags and defaults): the 'bra' loader over the config's data_dir (the three front
+    cameras side by side, the telephoto camera, their labels, the brake flag), one Adam step per batch, bra_{epoch}.th saved every
+    --num-per-save epochs with RGBBrakePredictionModel([4, 10, 18])'s keys (the agent's `bra_model_dir`).  What this build adds:
+    --synthetic / --steps-per-epoch (seeded synthetic 288 x 768 + 192 x 480 images), --save-dir, --bra (a checkpoint to start from)."""
+    from .brake import BRA_LABELS, BrakeTrainer
+    from .synthetic import synthetic_bra_batch
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config-path", default="config_v2.yaml", help="the reference's config_v2.yaml (data_dir, camera_yaws, crop_tel_bottom)")
+    ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
+    ap.add_argument("--num-epoch", type=int, default=10)
+    ap.add_argument("--num-per-log", type=int, default=100, help="log per iter")
+    ap.add_argument("--num-per-save", type=int, default=1, help="save per epoch")
+    ap.add_argument("--batch-size", type=int, default=52, help="GLOBAL batch, split over the ranks")
+    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--num-workers", type=int, default=16, help="DataLoader workers (recorded routes only)")
+    ap.add_argument("--seed", type=int, default=2021)
+    ap.add_argument("--synthetic", action="store_true", help="seeded synthetic batches instead of the config's data_dir")
+    ap.add_argument("--steps-per-epoch", type=int, default=20, help="iterations that make one epoch of synthetic data")
+    ap.add_argument("--save-dir", default="checkpoints")
+    ap.add_argument("--bra", default=None, help="bra_*.th to start from")
+    args = ap.parse_args()
+    have_cfg = bool(args.config_path) and os.path.isfile(args.config_path)
+    if not args.synthetic and not have_cfg:
+        raise SystemExit(f"recorded routes are read from the data_dir of --config-path ({args.config_path} not found; or pass --synthetic)")
+    rank, world, device = setup_distributed()
+    if args.device == "cpu":
+        device = torch.device("cpu")
+    cfg = load_config(args.config_path if have_cfg else None, lr=args.lr, seed=args.seed)
+    if args.batch_size % world:
+        raise SystemExit(f"global batch {args.batch_size} is not divisible by {world} ranks")
+    per_rank = args.batch_size // world
+    ck = {"bra": torch.load(args.bra, map_location="cpu")} if args.bra else {}
+    trainer = BrakeTrainer(cfg, device, checkpoints=ck)
+    loader = None
+    if not args.synthetic:
+        from ..data import get_data_loader
+        loader = get_data_loader("bra", args, rank=rank, world=world)
+        if len(loader) == 0:
+            raise SystemExit(f"{args.config_path}: data_dir holds fewer frames than one batch of {args.batch_size}")
+    torch.manual_seed(args.seed)
+
+    def batches(epoch):
+        if loader is not None:
+            if world > 1:
+                loader.sampler.set_epoch(epoch)
+            yield from loader
+            return
+        for it in range(args.steps_per_epoch):
+            yield synthetic_bra_batch(per_rank, seed=cfg.seed + 1000003 * epoch + 1009 * it + 100 * rank, num_classes=len(BRA_LABELS) + 1,
+                                      device=device)
+
+    global_it, t0 = 0, time.perf_counter()
+    for epoch in range(args.num_epoch):
+        for rgb1, rgb2, sem1, sem2, bra in batches(epoch):
+            info = trainer.train_bra(rgb1, rgb2, sem1, sem2, bra)
+            if global_it % args.num_per_log == 0 and rank == 0:
+                print(global_it, dict(loss=round(info["loss"], 4), bra=info["bra"], pred_bra=round(info["pred_bra"], 4)), flush=True)
+            global_it += 1
+        if (epoch + 1) % args.num_per_save == 0 and rank == 0:
+            os.makedirs(args.save_dir, exist_ok=True)
+            path = os.path.join(args.save_dir, f"bra_{epoch + 1}.th")
+            torch.save(trainer.state_dict("bra"), path)
+            print(f"saved to {path}", flush=True)
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    in_sync = None
+    if world > 1:   # as main(): a checksum of every trained parameter, compared across the ranks
+        mine = torch.stack([p_.detach().double().sum() for p_ in trainer.bra_model.parameters() if p_.requires_grad]).to(device)
+        every = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(every, mine)
+        in_sync = all(torch.equal(every[0], e) for e in every[1:])
+    if rank == 0:
+        print(json.dumps(dict(what="bra", samples_per_s=round(args.batch_size * global_it / max(dt, 1e-9), 2), n_gpus=world,
+                              replicas_in_sync=in_sync, global_batch=args.batch_size, steps=global_it, epochs=args.num_epoch,
+                              data="synthetic batches" if loader is None else f"{len(loader.dataset)} recorded frames",
+                              lr=trainer.bra_optim.param_groups[0]["lr"])))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

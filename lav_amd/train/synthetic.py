@@ -1,7 +1,7 @@
 """Synthetic training batches with the tensor contracts of the reference's data loaders: seeded, no
 dataset on disk.  Shapes: lidar (B, Nmax, 11) + num_points (B,), heat (B,2,H,W), size / ori (B,2,H,W), bev
 (B,9,H,W), ego_locs (B,T+1,2), cmds (B,), nxps (B,2), bras (B,), locs (B,N+1,T+1,2), oris (B,N+1), typs (B,N+1),
-num_objs (B,); camera segmentation: rgb (B,H,W,3) uint8, sem (B,H,W) int64."""
+num_objs (B,); camera segmentation: rgb (B,H,W,3) uint8, sem (B,H,W) int64; brake net: synthetic_bra_batch."""
 from __future__ import annotations
 
 import numpy as np
@@ -78,3 +78,22 @@ def synthetic_seg_batch(B, seed=2021, hw=(288, 256), num_classes=5, device="cpu"
     sem = np.kron(cells, np.ones((1, 8, 8), np.int64))[:, :H, :W]
     rgb = np.clip(palette[sem] + rng.normal(0, 16, (B, H, W, 3)), 0, 255).astype(np.uint8)
     return torch.from_numpy(rgb).to(device), torch.from_numpy(np.ascontiguousarray(sem)).to(device)
+
+
+def synthetic_bra_batch(B, seed=2021, hw=(288, 768), tel_hw=(192, 480), num_classes=4, device="cpu"):
+    """train_bra's arguments, what the 'bra' loader yields batched: (rgb (B, H, W, 3) uint8 - the three front cameras side by side -,
+    tel_rgb (B, Ht, Wt, 3) uint8, sem (B, H, W) uint8 and tel_sem (B, Ht, Wt) uint8 labels in [0, num_classes), bra (B,) int64 0/1).
+    Images as in synthetic_seg_batch (8 x 8 blocks of one class, colour = the class's plus noise); about one frame in five brakes."""
+    rng = np.random.default_rng(seed)
+    palette = rng.integers(0, 256, (num_classes, 3))
+
+    def view(H, W):
+        cells = rng.integers(0, num_classes, (B, H // 8 + 1, W // 8 + 1))
+        sem = np.kron(cells, np.ones((1, 8, 8), np.int64))[:, :H, :W]
+        rgb = np.clip(palette[sem] + rng.normal(0, 16, (B, H, W, 3)), 0, 255).astype(np.uint8)
+        return torch.from_numpy(rgb).to(device), torch.from_numpy(np.ascontiguousarray(sem.astype(np.uint8))).to(device)
+
+    rgb, sem = view(*hw)
+    tel_rgb, tel_sem = view(*tel_hw)
+    bra = torch.from_numpy((rng.random(B) < 0.2).astype(np.int64)).to(device)
+    return rgb, tel_rgb, sem, tel_sem, bra
