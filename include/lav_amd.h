@@ -269,8 +269,18 @@ typedef struct lav_conv {
 #define LAV_CONV_F16X3 3   /* as BF16X6, and wherever the plan is the split kernel (round 5: the head convolution's plan only; round 6:
                               every split plan - any stride, tile, split-K, tap pairs, the classes of a transposed convolution) each
                               operand is TWO fp16 pieces scaled by a power of two taken from the tensor's largest finite magnitude,
-                              three products: half the matrix instructions at 22 bits per operand - the error of the dot product
-                              stays at the level of its fp32 accumulation.  The activations' magnitude comes from the launches that
+                              three products: half the matrix instructions at 22 bits per operand.  Precision (tests/
+                              test_gpu_f16x3_contract.py): the scale s puts the tensor's largest magnitude into [2^14, 2^15) (exponent
+                              floored: s >= 2^-115), and an element keeps an ABSOLUTE error of up to 2^-25 s (fp16's subnormal
+                              quantum), i.e. 2^-40 .. 2^-39 of the tensor's maximum, so the bound is two-term:
+                                |y - y_exact| <= 2e-6 sum|w||x| + 2^-25 (s_x sum|w| + s_w sum|x|)   (sums over the receptive field)
+                              (measured: at most 0.21 of the second term where it dominates).  Outputs whose inputs and weights lie
+                              within 2^-20 of their tensors' maxima keep the 2e-6 of sum|w||x| bar of BF16X6 (measured <= 2.6e-7);
+                              at 2^-30 the error reached 2.8e-4 of sum|w||x|.  fp32 SUBNORMAL activations are not flushed (unlike
+                              BF16X6): they are scaled like any value and count when the scaled value is above 2^-25, i.e. when the
+                              tensor's maximum is small; Inf / NaN make the outputs they reach non-finite and change no other bit.
+                              Magnitudes up to FLT_MAX are exact as in BF16X6: the epilogue applies s_x s_w as two balanced powers
+                              of two, so neither it nor acc * s_x overflows where y does not.  The activations' magnitude comes from the launches that
                               wrote them (lav_conv2d_amax below) or, without that, from one measuring launch in front of the
                               convolution.  Re-packing on the device: lav_conv_repack_scratch (the weights' magnitude is measured first) */
 
@@ -317,7 +327,9 @@ int lav_conv2d(const lav_conv *c, const float *x, const float *w_packed, const f
  * (device, or NULL / 0): such maxima of the tensor(s) x was assembled from - any values whose maximum bounds max |x| (e.g. the
  * maxima of a tensor that x is a max-pooling, a crop or a bilinear resampling of); a LAV_CONV_F16X3 layer on the split kernel takes
  * its power-of-two scale from them instead of measuring x (other layers ignore them).  A bound that is too small would overflow
- * fp16 (Inf / NaN in y); one that is 2^k too large costs k of the 22 operand bits. */
+ * fp16 (a wrong, possibly finite y: the pieces saturate); one that is 2^k too large costs k of the 22 operand bits.  The library's
+ * Python engines keep a bound only while it holds: a tensor carries its producer's bound with the tensor's version and the buffer's
+ * generation (lav_amd/ops.py tag_amax / amax_of), and concurrent streams never share a buffer. */
 #define LAV_AMAX_PARTS 512   /* floats lav_absmax_parts writes */
 int lav_absmax_parts(const float *x, long n, float *parts, void *stream);   /* maxima of the finite |x[0 .. n)| in LAV_AMAX_PARTS parts: one launch */
 int lav_conv_amax_count(const lav_conv *c);

@@ -1164,8 +1164,8 @@ extern "C" int lav_conv_repack_scratch(const lav_conv *c, const float *d_weight,
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_conv_repack, dim3((unsigned)((nf + ntrip + 255) / 256)), dim3(256), 0, st, d_weight, d_map, nf, ntrip, d_packed);
     if (resolve_precision(*c) == LAV_CONV_F16X3 && f16x3_layer(*c, p)) {
-        // round 6: the fp16 section too - the weights' largest magnitude is measured on the device (512 parts, kept in the 2 KB behind
-        // the section's scale word: lav_conv_packed_weight_floats reserves them), then one gather launch splits w / s into pieces
+        // round 6: the fp16 section too - the weights' largest magnitude is measured on the device into the caller's scratch (d_parts,
+        // F16_PARTS floats), then one gather launch splits w / s into pieces
         LAV_REQUIRE(d_parts && parts_floats >= F16_PARTS, "lav_conv_repack: a LAV_CONV_F16X3 layer needs %d floats of scratch for the weights' maxima", F16_PARTS);
         const long npairs = (long)(split_weight_bytes_f16(p) / 4);
         const long nw = (long)c->cout * c->cin * c->kh * c->kw;

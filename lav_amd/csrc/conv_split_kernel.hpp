@@ -148,11 +148,19 @@ __device__ __forceinline__ void split_body(const SplitArgs &a, unsigned char *sm
         int e = 0;
         (void)frexpf(m, &e);                       // m = f 2^e, f in [0.5, 1): m / 2^(e - 15) in [16384, 32768)
         // (exponent floored at -100: a tensor whose largest value is below 2^-100 - or subnormal - would give a subnormal scale and an
-        //  infinite reciprocal; such values flush to zero in fp16 either way.  The two scales are applied one after the other in the
-        //  epilogue: their product alone can overflow for a huge activation maximum times a huge weight maximum.)
+        //  infinite reciprocal.  With the floor such a tensor is divided by 2^-115: its values, fp32 subnormals included, are kept
+        //  down to 2^-140.)
         const float sx = ldexpf(1.f, m > 0.f ? max(e, -100) - 15 : 0);
         inv_sx = 1.f / sx;                         // (a power of two: exact)
-        out_sx = sx; out_sw = *a.f16_wscale;
+        // The epilogue multiplies by two powers of two one after the other: sx * sw alone can overflow (2^113 * 2^113), and so can
+        // acc * sx when the weights are small (activations near FLT_MAX: acc ~ 2^32, sx = 2^113).  Both factors are therefore the
+        // halves of sx * sw's exponent: acc * out_sx lies between acc and y, so it over- or underflows only where y does, and y is
+        // rounded once, as with any other split of the exponent.
+        int ex = 0, ew = 0;
+        (void)frexpf(sx, &ex);
+        (void)frexpf(*a.f16_wscale, &ew);
+        const int et = ex + ew - 2;                // sx * sw = 2^et (both are powers of two in [2^-115, 2^113])
+        out_sx = ldexpf(1.f, et >> 1); out_sw = ldexpf(1.f, et - (et >> 1));
     }
     const int ntaps_real = a.cls_ntaps[cls];
     const int ntaps = TP ? (ntaps_real + 1) >> 1 : ntaps_real;   // steps per chunk (TP: tap pairs)

@@ -176,9 +176,10 @@ class ConvBackbone(_Engine):
         # LAV_CONV_F16X3: every layer leaves the maxima of what it writes for the layers that read it (lav_conv2d_amax) - none of
         # them measures its input; the three up-convolutions leave the feature map's for the heads and the crops' stems
         B = x.shape[0]
-        ams = e["amax"].get(tuple(x.shape))
+        key = ops.amax_key(x)
+        ams = e["amax"].get(key)
         if ams is None:
-            ams = e["amax"][tuple(x.shape)] = [Amax(x.device) for _ in range(len(e["s1"]) + len(e["s2"]) + len(e["s3"]) + 1)]
+            ams = e["amax"][key] = [Amax(x.device) for _ in range(len(e["s1"]) + len(e["s2"]) + len(e["s3"]) + 1)]
         stages = (e["s1"], e["s2"], e["s3"])
         feats, feat_am, am_prev, i = [], [], ops.amax_of(x), 0
         for si, st in enumerate(stages):
@@ -196,8 +197,7 @@ class ConvBackbone(_Engine):
         am_out = ams[-1].reset()
         for up, f, am in zip(e["ups"], feats, feat_am):
             up(f, out=out, amax_in=am, amax_out=am_out)
-        out._lav_amax = am_out
-        return out
+        return ops.tag_amax(out, am_out)
 
 
 class Head(_Engine):

@@ -100,7 +100,7 @@ def pillar_scatter(points: torch.Tensor, num_points: Sequence[int], grid: Grid, 
     rc = lib.lav_pillar_scatter_amax(_ptr(points) if nmax > 0 else None, h_num, B, nmax, D, C.byref(grid), C.byref(net),
                                      _ptr(canvas), _ptr(uc), _ptr(inv), _ptr(cnt), _ptr(parts), _ptr(ws), ws.numel(), _stream())
     if amax is not None:
-        canvas._lav_amax = amax
+        tag_amax(canvas, amax)
     if rc != 0:
         # the workspace's zero-at-rest state (arrival counters, epoch words) may be half-updated: never reuse it (lav_amd.h, workspace
         # contract) - the next call zero-fills a fresh one
@@ -390,16 +390,19 @@ def frame_precision() -> int:
 class Amax:
     """Maxima of the finite |values| of a tensor, in parts, as the launches that wrote it left them (lav_conv2d_amax): the next
     LAV_CONV_F16X3 layer takes its power-of-two activation scale from them instead of measuring its input.  One fixed buffer;
-    `take(n)` hands out the next n slots (the same addresses on every pass over the same layers: HIP graphs may hold them)."""
+    `take(n)` hands out the next n slots (the same addresses on every pass over the same layers: HIP graphs may hold them).
+    `generation` counts the resets: a bound handed on with a tensor (tag_amax) names the generation it was written in."""
     CAPACITY = 20480
 
     def __init__(self, device, capacity: Optional[int] = None, zeroed: bool = True):
         self.CAPACITY = int(capacity) if capacity else Amax.CAPACITY
         self.buf = (torch.zeros if zeroed else torch.empty)(self.CAPACITY, dtype=torch.float32, device=device)
         self.count = 0
+        self.generation = 0
 
     def reset(self):
         self.count = 0
+        self.generation += 1      # (the launches that follow rewrite the parts: every bound handed on before is void)
         return self
 
     def take(self, n: int) -> torch.Tensor:
@@ -410,11 +413,34 @@ class Amax:
         return v
 
 
+def tag_amax(t, am):
+    """Attach the Amax whose parts bound |t| to the tensor OBJECT t (the producer's side of amax_of), stamped with the tensor's
+    version and the Amax's generation: an in-place change of t, or a later call that resets the Amax (the same layers on another
+    input of the same shape), voids the bound."""
+    t._lav_amax = am
+    t._lav_amax_stamp = (id(am), t._version, am.generation)
+    return t
+
+
 def amax_of(t):
     """The Amax a producer attached to the tensor OBJECT it returned (engine-internal hand-off between modules: backbone -> heads /
-    crops); None for anything else.  A bound, not a measurement: valid for the tensor and for whatever is a max-pool, a crop or a
-    bilinear resampling of it."""
-    return getattr(t, "_lav_amax", None)
+    crops), while it still bounds the tensor; None for anything else - the consumer then measures its input (one launch more,
+    the same result).  A bound, not a measurement: valid for the tensor and for whatever is a max-pool, a crop or a bilinear
+    resampling of it.  Training-path tags (train.hipnn._tag) carry their version on the Amax."""
+    am = getattr(t, "_lav_amax", None)
+    if am is None:
+        return None
+    stamp = getattr(t, "_lav_amax_stamp", None)
+    if stamp is None:
+        return am if getattr(am, "version", None) == t._version else None
+    return am if stamp == (id(am), t._version, am.generation) else None
+
+
+def amax_key(x):
+    """Key of a module's Amax list for input x: its shape and the current stream.  Launches on different streams may run
+    concurrently (the frame's ego and others graphs: crop batches of one shape on s_ego and s_cap), so they never share the
+    buffers their layers leave maxima in - as the split-K workspaces (_workspace)."""
+    return tuple(x.shape), torch.cuda.current_stream(x.device).cuda_stream
 
 
 class ConvLayer:

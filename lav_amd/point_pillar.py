@@ -115,10 +115,10 @@ class PointPillarNet(nn.Module):
             raise RuntimeError(f"points have {pts.shape[2]} columns, PointNet expects {self.num_input - 5}")
         w1, b1, w2, b2 = self.point_net.folded(pts.device)
         # the canvas leaves with a bound of its values (one float per workgroup of the canvas kernel) for LAV_CONV_F16X3 readers; one
-        # fixed buffer per batch size and device: HIP graphs hold its address
+        # fixed buffer per batch size, device and stream (ops.amax_key): HIP graphs hold its address
         am = None
         if not return_indices and os.environ.get("LAV_PILLAR_AMAX", "1") != "0":
-            key = (int(pts.shape[0]), str(pts.device))
+            key = (int(pts.shape[0]), str(pts.device), torch.cuda.current_stream(pts.device).cuda_stream)
             am = self._amax.get(key)
             if am is None:
                 am = self._amax[key] = ops.Amax(pts.device, capacity=2048)

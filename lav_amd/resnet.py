@@ -93,9 +93,10 @@ class ResNet(_Engine):
         # LAV_CONV_F16X3: every convolution leaves the maxima of its output for the layers that read it (lav_conv2d_amax); the stem
         # takes those of its input from whoever made it (the crops carry the feature map's), the max-pool passes its input's on
         B = x.shape[0]
-        ams = e["amax"].get(tuple(x.shape))
+        key = ops.amax_key(x)
+        ams = e["amax"].get(key)
         if ams is None:
-            ams = e["amax"][tuple(x.shape)] = [Amax(x.device) for _ in range(1 + 2 * len(e["blocks"]))]
+            ams = e["amax"][key] = [Amax(x.device) for _ in range(1 + 2 * len(e["blocks"]))]
         blocks = e["blocks"]
         def want(readers, h, w):
             return any(r is not None and r.uses_amax(B, h, w) for r in readers)

@@ -188,8 +188,8 @@ _train_precision_stack = []
 
 def train_precision() -> int:
     """lav_conv.precision of the training graph's forward / data-gradient / weight-gradient convolutions: the environment's
-    LAV_TRAIN_PRECISION if set, else the innermost `use_precision(...)` (the trainers: LAV.train_lidar asks for f16x3, LAV.train_bev for
-    bf16x6), else bf16x6.
+    LAV_TRAIN_PRECISION if set, else the innermost `use_precision(...)` (the trainers: LAV.train_lidar and LAV.train_bev ask for
+    TrainConfig.conv_precision, default f16x3), else bf16x6.
       f16x3 (round 6)  every split-kernel layer and the weight-gradient kernels on two fp16 pieces per operand and three products -
                        the batch-32 layers are matrix / power bound like the frame's head convolution -, packed weights re-gathered AND
                        re-scaled on the device per step (lav_conv_repack_scratch), every activation and gradient tensor measured once

@@ -51,7 +51,7 @@ class TrainConfig:
     distill: bool = True
     lr: float = 3e-4
     perceive_only: bool = False
-    conv_precision: str = ""      # "" = the trainer's default (train_lidar: f16x3, train_bev: bf16x6); LAV_TRAIN_PRECISION overrides
+    conv_precision: str = ""      # "" = the trainers' default (train_lidar and train_bev: f16x3); LAV_TRAIN_PRECISION overrides
     motion_only: bool = False
     log_inference: bool = True     # the reference runs one eval-mode inference of sample 0 per step, for its logs only
     log_every: int = 100           # (lav_final_v2.py:228-236; logged every --num-per-log = 100 steps): here it runs on those steps

@@ -83,8 +83,7 @@ class UniPlanner(DecoderMixin, _Engine):
         if amax is not None and not self.training and map_index is None:
             ox, oy = self.offsets()
             crops = crop_feature(features, rel_locs, rel_oris, pixels_per_meter, crop_size, ox, oy)
-            crops._lav_amax = amax
-            return crops
+            return ops.tag_amax(crops, amax)
         ox, oy = self.offsets()
         if map_index is not None and features.is_cuda and (_hip_train("CROP") or not self.training):   # HIP forward + backward (autograd.Function)
             return ops.crop_rotate_indexed(features, map_index, rel_locs, rel_oris, pixels_per_meter, crop_size, ox, oy)
