@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 30
+#define LAV_ABI_VERSION 31
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -656,6 +656,31 @@ int lav_conv1d_pair_chain_f16(int batch, int channels, int h, int w, int npairs,
 int lav_conv1d_pair_chain_region(int row_offset, int clean_rows);
 int lav_conv1d_pair_chain_status(const void *workspace, int *h_timeouts_launches2, void *stream);
 size_t lav_conv1d_pair_lds_bytes(int channels, int w, int d_b);
+/*
+ * lav_conv3x3_run_f16 (ABI 31): a RUN of nlayers (<= 8) identical layers conv3x3(stride 1, pad 1, no bias) -> ReLU -> y * scale + shift at
+ * 64 or 128 channels over one [channels][h][w] map (batch 1) as ONE persistent launch - the stages of the BEV backbone behind their
+ * stride-2 layer (team_code_v2/models/lidar.py:57-108).  A workgroup owns one output row (and a slice of the output channels) for all
+ * layers; between two layers the rows travel through two ping-pong maps of the workspace (write-through stores) and one 64-bit word
+ * {layers done | largest finite |y| written} per workgroup and layer, the protocol of lav_conv1d_pair_chain_f16.  Arithmetic of
+ * LAV_CONV_F16X3: two fp16 pieces per operand, three products, fp32 accumulate.  w_f16[i]: the fp16 section of layer i's packed weights
+ * (lav_conv_pack_weights of a LAV_CONV_F16X3 layer, at lav_conv_f16_weights_offset floats).  The first layer's activation scale comes from
+ * amax_in (amax_in_count maxima that bound |x|: lav_absmax_parts, or a producer's lav_conv2d_amax); inside the run every workgroup takes
+ * it per layer from the words it waited for.  amax_out (optional): one float per workgroup (h * slices =
+ * lav_conv3x3_run_f16_amax_count) - the maxima of the result, as lav_conv2d_amax leaves them.  Only the last layer's map is an output.
+ * Waits are bounded (LAV_CHAIN_SPIN_LIMIT): a workgroup that gives up raises the launch's abort word (its peers stop waiting too), fills
+ * its part of `out` with NaN and raises a sticky counter; lav_conv3x3_run_f16_status copies {workgroups that gave up, launches} since the
+ * workspace was zero-filled (it SYNCHRONISES `stream`).  workspace: lav_conv3x3_run_f16_workspace_bytes (0: the geometry is not served -
+ * run the layers one launch each), ZERO before its first use, private to the stream.
+ */
+size_t lav_conv3x3_run_f16_workspace_bytes(int channels, int h, int w, int nlayers);
+size_t lav_conv3x3_run_f16_lds_bytes(int channels, int h, int w);
+size_t lav_conv3x3_run_f16_weight_bytes(int channels);
+int lav_conv3x3_run_f16_amax_count(int channels, int h, int w);
+long lav_conv_f16_weights_offset(const lav_conv *c);
+int lav_conv3x3_run_f16(int channels, int h, int w, int nlayers, const float *x, const void *const *w_f16, const float *const *scale,
+                        const float *const *shift, float *out, const float *amax_in, int amax_in_count, float *amax_out, void *workspace,
+                        size_t workspace_bytes, void *stream);
+int lav_conv3x3_run_f16_status(const void *workspace, int *h_timeouts_launches2, void *stream);
 int lav_conv1d_pair(int batch, int channels, int h, int w, int d_a, int d_b, const float *x, const float *wa_packed,
                     const float *bias_a, const float *wb_packed, const float *bias_b, const float *scale, const float *shift,
                     const float *residual, int relu_post, float *y, void *stream);

@@ -998,6 +998,16 @@ extern "C" size_t lav_conv_packed_weight_floats(const lav_conv *c) {
     return n;
 }
 
+// Where the LAV_CONV_F16X3 section ([cout block][tap][chunk][piece][lane] x 16 B, then the weights' scale) starts inside the packed
+// weights, in floats; -1: the layer has none.  lav_conv3x3_run_f16 reads the layers' own packing.
+extern "C" long lav_conv_f16_weights_offset(const lav_conv *c) {
+    if (!c) return -1;
+    Plan p;
+    if (build_plan(*c, p)) return -1;
+    if (resolve_precision(*c) != LAV_CONV_F16X3 || !f16x3_layer(*c, p)) return -1;
+    return (long)((p.wfloats + 3) / 4 * 4 + split_weight_bytes(p) / 4);
+}
+
 extern "C" int lav_conv_pack_weights(const lav_conv *c, const float *h_weight, float *h_packed) {
     LAV_REQUIRE(c && h_weight && h_packed, "lav_conv_pack_weights: null");
     Plan p;

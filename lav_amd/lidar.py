@@ -14,7 +14,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import ops
-from .ops import Amax, ConvLayer, GroupedDeconv, PointwiseUpconv
+from .ops import Amax, ConvLayer, ConvRun, GroupedDeconv, PointwiseUpconv
 from .point_pillar import PointPillarNet
 
 _NORM = dict(eps=1e-3, momentum=0.01)
@@ -143,6 +143,10 @@ class ConvBackbone(_Engine):
                                      out_c_total=self.out_channels, out_c_offset=off, precision=prec, device=device))
             off += ct.weight.shape[1]
         eng[key] = dict(s1=stage(self.conv1), s2=stage(self.conv2), s3=stage(self.conv3), ups=ups, amax={}, f16=prec == _lib.CONV_F16X3)
+        # layers 2..n of a stage share one geometry: one persistent launch each where LAV_BEV_RUN asks for it (ops.ConvRun; the choice
+        # sits here, so the eager and the graphed pipeline run the same kernels)
+        want = ops.bev_run_stages() if prec == _lib.CONV_F16X3 else ()
+        eng[key]["runs"] = [ConvRun(eng[key][s][1:]) if s in want and len(eng[key][s]) > 2 else None for s in ("s1", "s2", "s3")]
         eng["tensor_ids"] = self._tensor_ids()   # recorded where the engine is built, not at its first use
         object.__setattr__(self, "_eng", eng)
         return eng[key]
@@ -183,13 +187,18 @@ class ConvBackbone(_Engine):
         stages = (e["s1"], e["s2"], e["s3"])
         feats, feat_am, am_prev, i = [], [], ops.amax_of(x), 0
         for si, st in enumerate(stages):
-            for li, layer in enumerate(st):
+            run, li = e["runs"][si], 0
+            while li < len(st):
+                layer = st[li]
                 oh, ow = layer.out_hw(x.shape[2], x.shape[3])
-                readers = ([st[li + 1]] if li + 1 < len(st) else ([stages[si + 1][0]] if si + 1 < len(stages) else [])) + \
-                          ([e["ups"][si]] if li + 1 == len(st) else [])
-                am = ams[i].reset() if any(r.uses_amax(B, oh, ow) for r in readers) else None
-                x = layer(x, amax_in=am_prev, amax_out=am)
-                am_prev, i = am, i + 1
+                runs_next = run is not None and run.takes(B, oh, ow)       # layers 1 .. n-1 as one launch
+                n = len(st) - 1 if runs_next and li == 1 else 1
+                nxt = li + n
+                readers = ([run if runs_next and nxt == 1 else st[nxt]] if nxt < len(st) else ([stages[si + 1][0]] if si + 1 < len(stages) else [])) + \
+                          ([e["ups"][si]] if nxt == len(st) else [])
+                am = ams[i + n - 1].reset() if any(r.uses_amax(B, oh, ow) for r in readers) else None
+                x = (run if n > 1 else layer)(x, amax_in=am_prev, amax_out=am)
+                am_prev, i, li = am, i + n, nxt
             feats.append(x); feat_am.append(am_prev)
         oh, ow = e["ups"][0].out_hw(feats[0].shape[2], feats[0].shape[3])
         if out is None:

@@ -895,6 +895,93 @@ def pair_chain_status(device, stream=None):
     return (int(v[0]), int(v[1]))
 
 
+def bev_run_stages():
+    """The backbone stages (s1, s2, s3) whose same-shape 3x3 layers run as one persistent launch (ConvRun): LAV_BEV_RUN=0 none,
+    =1 all, =s1,s3 those; default: what the measurement kept (profiles/bev_run_ab.txt)."""
+    v = _os.environ.get("LAV_BEV_RUN", BEV_RUN_DEFAULT).strip().lower()
+    if v in ("0", "", "off", "none"):
+        return frozenset()
+    if v in ("1", "on", "all"):
+        return frozenset(("s1", "s2", "s3"))
+    return frozenset(s for s in v.split(",") if s in ("s1", "s2", "s3"))
+
+
+BEV_RUN_DEFAULT = "s2,s3"
+
+
+class ConvRun:
+    """A run of ConvLayers of one geometry - conv3x3(stride 1, pad 1, no bias) -> ReLU -> BatchNorm affine, C -> C channels, packed for
+    LAV_CONV_F16X3 - as ONE persistent launch (lav_conv3x3_run_f16).  Reads the layers' own packed weights and epilogue vectors (a
+    ConvLayer.refresh re-packs in place: nothing to refresh here).  `takes(B, h, w)`: whether the launch serves that input; else the
+    caller runs the layers one by one."""
+
+    def __init__(self, layers):
+        lib = _lib.load()
+        layers = list(layers)
+        l0 = layers[0]
+        for l in layers:
+            d = l.desc
+            if not (d.precision == _lib.CONV_F16X3 and (d.kh, d.kw, d.stride, d.pad_h, d.pad_w, d.dil_h, d.dil_w) == (3, 3, 1, 1, 1, 1, 1)
+                    and not d.transposed and l.cin == l.cout == l0.cin and l.in_c_total == l.cin and l.out_c_total == l.cout
+                    and l.bias is None and l.scale is not None and d.relu_pre and not d.relu_post and not d.sigmoid and d.pad_value == 0.0):
+                raise RuntimeError("ConvRun: layers must be identical conv3x3 / ReLU / BatchNorm layers packed for LAV_CONV_F16X3")
+        self.layers, self.ch = layers, l0.cin
+        probe = Conv.from_buffer_copy(l0.desc)
+        probe.h, probe.w = 64, 64
+        self._woff = int(lib.lav_conv_f16_weights_offset(C.byref(probe)))
+        if self._woff < 0 or len(layers) > 8:
+            raise RuntimeError("ConvRun: at most 8 layers with fp16 packed weights")
+        n = len(layers)
+        self._n = n
+
+    def takes(self, B: int, h: int, w: int) -> bool:
+        return B == 1 and _lib.load().lav_conv3x3_run_f16_workspace_bytes(self.ch, h, w, self._n) > 0
+
+    def uses_amax(self, B: int, h: int, w: int) -> bool:
+        return self.takes(B, h, w)
+
+    def __call__(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, amax_in: Optional["Amax"] = None,
+                 amax_out: Optional["Amax"] = None) -> torch.Tensor:
+        lib = _lib.load()
+        x = _f32c(x, "x")
+        B, ch, h, w = x.shape
+        if ch != self.ch or not self.takes(B, h, w):
+            raise RuntimeError(f"ConvRun: input {tuple(x.shape)} is not served (lav_conv3x3_run_f16_workspace_bytes)")
+        if out is None:
+            out = torch.empty_like(x)
+        n = self._n
+        # one workspace per run, shape AND stream (the maps and the hand-off words are private to the launches of one stream)
+        ws = _workspace(("conv_run", id(self), ch, h, w), lib.lav_conv3x3_run_f16_workspace_bytes(ch, h, w, n), x.device)
+        if amax_in is not None and amax_in.count > 0:
+            a_in, n_in = amax_in.buf, amax_in.count
+        else:   # nobody left the input's maxima: measure it (one launch more)
+            a_in = _workspace(("conv_run_amax", id(self)), 512 * 4, x.device).view(torch.float32)
+            n_in = 512
+            check(lib.lav_absmax_parts(_ptr(x), x.numel(), _ptr(a_in), _stream()), "lav_absmax_parts")
+        a_out = amax_out.take(lib.lav_conv3x3_run_f16_amax_count(ch, h, w)) if amax_out is not None else None
+        pa = lambda ts: (C.c_void_p * n)(*[t if isinstance(t, int) else t.data_ptr() for t in ts])
+        check(lib.lav_conv3x3_run_f16(ch, h, w, n, _ptr(x), pa([l.w.data_ptr() + 4 * self._woff for l in self.layers]),
+                                      pa([l.scale for l in self.layers]), pa([l.shift for l in self.layers]), _ptr(out), _ptr(a_in), n_in,
+                                      _ptr(a_out), _ptr(ws), ws.numel(), _stream()), "lav_conv3x3_run_f16")
+        return out
+
+
+def bev_run_status(device, stream=None):
+    """(workgroups that gave up, launches) of the lav_conv3x3_run_f16 launches on `stream` (default: the current one), summed over
+    the runs' workspaces.  Synchronises that stream."""
+    st = stream if stream is not None else torch.cuda.current_stream()
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    tot = [0, 0]
+    for (key, dev, s), ws in list(_workspaces.items()):
+        if isinstance(key, tuple) and key and key[0] == "conv_run" and dev == device and s == st.cuda_stream:
+            v = (C.c_int * 2)()
+            check(_lib.load().lav_conv3x3_run_f16_status(_ptr(ws), v, st.cuda_stream), "lav_conv3x3_run_f16_status")
+            tot[0] += int(v[0]); tot[1] += int(v[1])
+    return tuple(tot)
+
+
 _CU_COUNT = {}
 
 
