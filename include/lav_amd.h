@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 31
+#define LAV_ABI_VERSION 32
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -728,6 +728,39 @@ int lav_seg_xent_forward(const float *logits, const long long *labels, int batch
  * (lav_amd.train.hipnn.seg_cross_entropy_up checks labels and shapes before the launch). */
 int lav_seg_xent_up_forward(const float *logits, const void *labels, int label_bytes, int batch, int classes, int h, int w, int scale,
                             float *loss, float *dlogits, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Offline point painting (ABI 32): the data collector's painter, lav/data_paint.py + lav/utils/point_painting.py, for a batch
+ * of recorded frames in one launch.  Unlike lav_paint (the agent's painter: float32 projection, <= 4 cameras, fused rows) it
+ * projects in FLOAT64 like CoordConverter.lidar_to_cam and writes only the class scores.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct lav_camera_f64 {
+    double l2w[16]; /* row-major 4x4 lidar_to_world  (point_painting.py:14-16) */
+    double w2c[16]; /* row-major 4x4 world_to_cam    (:18-21) */
+    double K[9];    /* row-major 3x3 intrinsics      (:7-12) */
+} lav_camera_f64;
+
+/*
+ * lidar    [total][lidar_dim] float32: `frames` ragged clouds one after the other (xyz in columns 0..2; lidar_dim >= 3)
+ * offsets  DEVICE int32 [frames + 1]: frame f owns rows offsets[f] .. offsets[f+1]-1; offsets[0] = 0, offsets[frames] = total,
+ *          non-decreasing (1 <= frames <= 1024).  A row is painted from the last frame whose offset is <= its index, clamped to
+ *          [0, frames-1]: wrong offsets give wrong values, never an access outside sem.
+ * sem      [frames][ncam][sem_c+1][h][w] float32 class probabilities; channel 0 is the background.  1 <= ncam <= 8, sem_c == 4.
+ * h_cams   ncam HOST records, copied into the kernel arguments.
+ * painted  out [total][sem_c] (16-byte aligned).  xyz promoted to double; world = l2w.[x y z 1], cam = w2c.world,
+ *          (X,Y,Z) = (cam_y, -cam_z, cam_x), p = K.(X,Y,Z), every product and sum rounded separately in k order;
+ *          u = trunc(p0/(1e-5+p2)), v = trunc(p1/(1e-5+p2)), d = trunc(p2) as int64 (non-finite / out of range: invalid, numpy's
+ *          astype(int) gives INT64_MIN there).  Per camera in order (later cameras overwrite), for d>=0, 0<=u<w, 0<=v<h:
+ *          painted[c] = sem[1+c][v][u] * (1 - sem[0][v][u]) (float32 subtraction, float32 product); rows no camera sees are 0.
+ *          Every row is written exactly once.
+ * uvz      optional out [ncam][total][3] int32: (u, v, d) saturated to the int32 range, INT32_MIN where invalid; NULL to skip.
+ */
+int lav_paint_frames(const float *lidar, const int *offsets, int frames, int total, int lidar_dim, const float *sem, int ncam,
+                     int sem_c, int h, int w, const lav_camera_f64 *h_cams, float *painted, int *uvz, void *stream);
+
+/* img [n][h][w][c_src] uint8 (c_src 3 or 4) -> out [n][3][h][w] float32 of channels 0, 1, 2 (reverse != 0: 2, 1, 0 - BGR(A) ->
+ * RGB, point_paint_dataset.py:32).  Exact. */
+int lav_image_u8_to_f32(const unsigned char *img, int n, int h, int w, int c_src, int reverse, float *out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,8 +12,9 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LAV_AMD_LIB") or os.path.join(HERE, "liblav_amd.so")   # LAV_AMD_LIB: A/B a second build
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 MAX_CAM = 4
+MAX_CAM_F64 = 8
 
 
 class Grid(C.Structure):
@@ -28,6 +29,10 @@ class PointNet(C.Structure):
 
 class Camera(C.Structure):
     _fields_ = [("K", C.c_float * 9), ("l2w", C.c_float * 16), ("w2c", C.c_float * 16)]
+
+
+class CameraF64(C.Structure):
+    _fields_ = [("l2w", C.c_double * 16), ("w2c", C.c_double * 16), ("K", C.c_double * 9)]
 
 
 class Conv(C.Structure):
@@ -57,6 +62,8 @@ SIGNATURES = {
     "lav_pillar_scatter_amax": (_I, [_P, C.POINTER(_I), _I, _I, _I, C.POINTER(Grid), C.POINTER(PointNet), _P, _P, _P, _P, _P,
                                      _P, _Z, _P]),
     "lav_paint": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, C.POINTER(Camera), _P, _P, _P]),
+    "lav_paint_frames": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _I, _I, C.POINTER(CameraF64), _P, _P, _P]),
+    "lav_image_u8_to_f32": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "lav_gru_cast": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "lav_gru_cast_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "lav_embed_cast": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

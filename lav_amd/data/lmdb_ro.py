@@ -12,6 +12,11 @@ against files from this module's own writer only (tests/test_data_host.py: tree 
 found, absent keys rejected).  NO FILE WRITTEN BY liblmdb / py-lmdb HAS EVER BEEN READ BY THIS MODULE (a search of the image
 found no .mdb file and no lmdb or cv2 package to produce a fixture with): treat the recorded-route path of the trainers as
 experimental until one has.  The surface mirrors py-lmdb's: open(path, ...).begin(write=False).get(key).
+
+`update(path, items)` adds or replaces keys of an existing route (what the reference's `txn.put` does for the point painter,
+lav/utils/datasets/point_paint_dataset.py:34-46) by REWRITING the route in this module's own page layout - bulk-loaded, no
+free-page list, transaction id 1 - and putting the new file in data.mdb's place.  The same caveat holds: a route recorded by
+liblmdb comes out as a file of this writer, which no liblmdb has read here.
 """
 from __future__ import annotations
 
@@ -211,21 +216,16 @@ def open(path: str, **kwargs) -> Environment:   # noqa: A001  (py-lmdb's name)
 
 
 # ------------------------------------------------------------------------------------------------------------ writer
-def write(path: str, items: Iterable[Tuple[bytes, bytes]], psize: int = 4096) -> None:
-    """Write `items` as a fresh single-database LMDB environment (directory `path` with data.mdb), bulk-loaded: leaves filled
-    left to right in key order, branch levels built bottom-up.  For test routes and synthetic datasets."""
-    items = sorted((bytes(k), bytes(v)) for k, v in items)
-    for (a, _), (b, _) in zip(items, items[1:]):
-        if a == b:
-            raise Error(f"duplicate key {a!r}")
+def _bulk_load(f, items: Iterable[Tuple[bytes, bytes]], psize: int) -> None:
+    """Write the pairs of `items` - an iterator in strictly ascending key order - to the open binary file `f` as a single-database
+    environment.  Streams: overflow pages and leaves go to the file as they fill (pages 2 ...), the branch levels follow, the two
+    meta pages are written last; what stays in memory is the leaf being filled and one (first key, page number) per finished
+    page of the level being built."""
     nodemax = (((psize - PAGEHDR) // 2) & -2) - 2
     maxkey = 511
-    pages = [None, None]                     # pgno -> bytes; 0 and 1 are the meta pages
     counts = dict(branch=0, leaf=0, overflow=0)
-
-    def new_page(data: bytes) -> int:
-        pages.append(data)
-        return len(pages) - 1
+    state = dict(npages=2, entries=0)
+    f.seek(2 * psize)
 
     def build_page(flags: int, nodes) -> bytes:
         """nodes: list of raw node byte strings; laid out from the end of the page downwards, as liblmdb does."""
@@ -245,24 +245,30 @@ def write(path: str, items: Iterable[Tuple[bytes, bytes]], psize: int = 4096) ->
         return bytes(buf)
 
     def flush(flags, nodes, first_key, level):
-        pg = new_page(build_page(flags, nodes))
+        f.write(build_page(flags, nodes))
+        pg = state["npages"]
+        state["npages"] += 1
         counts["leaf" if flags & P_LEAF else "branch"] += 1
         level.append((first_key, pg))
 
     # leaves
     level = []
     nodes, used, first = [], PAGEHDR, None
+    last = None
     for k, v in items:
+        if last is not None and not last < k:
+            raise Error(f"keys out of order or duplicate: {last!r}, {k!r}")
+        last = k
+        state["entries"] += 1
         if not 0 < len(k) <= maxkey:
             raise Error(f"key of {len(k)} bytes (1..{maxkey} allowed)")
         if 8 + len(k) + len(v) > nodemax:                       # value goes to overflow pages
             npg = (PAGEHDR + len(v) + psize - 1) // psize
-            body = bytearray(npg * psize)
-            struct.pack_into("<QHHI", body, 0, 0, 0, P_OVERFLOW, npg)
-            body[PAGEHDR:PAGEHDR + len(v)] = v
-            first_pg = len(pages)
-            for i in range(npg):
-                pages.append(bytes(body[i * psize:(i + 1) * psize]))
+            first_pg = state["npages"]
+            f.write(struct.pack("<QHHI", 0, 0, P_OVERFLOW, npg))
+            f.write(v)
+            f.write(bytes(npg * psize - PAGEHDR - len(v)))
+            state["npages"] += npg
             counts["overflow"] += npg
             nd = _NODE.pack(len(v) & 0xFFFF, len(v) >> 16, F_BIGDATA, len(k)) + k + struct.pack("<Q", first_pg)
         else:
@@ -299,27 +305,88 @@ def write(path: str, items: Iterable[Tuple[bytes, bytes]], psize: int = 4096) ->
         level = upper_level
         depth += 1
     root = level[0][1] if level else P_INVALID
-    last_pg = len(pages) - 1
+    npages = state["npages"]
+    last_pg = npages - 1
 
     def meta(pgno: int, txnid: int, live: bool) -> bytes:
         buf = bytearray(psize)
         struct.pack_into("<QHHHH", buf, 0, pgno, 0, P_META, 0, 0)
         o = PAGEHDR
-        _META.pack_into(buf, o, MAGIC, VERSION, 0, max(len(pages) * psize, 1 << 20))
+        _META.pack_into(buf, o, MAGIC, VERSION, 0, max(npages * psize, 1 << 20))
         o += _META.size
         _DB.pack_into(buf, o, psize, 0x08, 0, 0, 0, 0, 0, P_INVALID)                        # free-page database: empty, integer keys
         o += _DB.size
         if live:
-            _DB.pack_into(buf, o, 0, 0, depth, counts["branch"], counts["leaf"], counts["overflow"], len(items), root)
+            _DB.pack_into(buf, o, 0, 0, depth, counts["branch"], counts["leaf"], counts["overflow"], state["entries"], root)
         else:
             _DB.pack_into(buf, o, 0, 0, 0, 0, 0, 0, 0, P_INVALID)
         o += _DB.size
         struct.pack_into("<QQ", buf, o, last_pg if live else 1, txnid)
         return bytes(buf)
 
-    pages[0] = meta(0, 0, False)
-    pages[1] = meta(1, 1, True)
+    f.seek(0)
+    f.write(meta(0, 0, False))
+    f.write(meta(1, 1, True))
+
+
+def write(path: str, items: Iterable[Tuple[bytes, bytes]], psize: int = 4096) -> None:
+    """Write `items` as a fresh single-database LMDB environment (directory `path` with data.mdb), bulk-loaded: leaves filled
+    left to right in key order, branch levels built bottom-up.  For test routes and synthetic datasets."""
+    items = sorted((bytes(k), bytes(v)) for k, v in items)
+    for (a, _), (b, _) in zip(items, items[1:]):
+        if a == b:
+            raise Error(f"duplicate key {a!r}")
     os.makedirs(path, exist_ok=True)
     with builtins.open(os.path.join(path, "data.mdb"), "wb") as f:
-        for p_ in pages:
-            f.write(p_)
+        _bulk_load(f, iter(items), psize)
+
+
+def _merged(old: Iterator[Tuple[bytes, bytes]], new) -> Iterator[Tuple[bytes, bytes]]:
+    """Two key-ordered streams as one; a key of `new` (a sorted list) replaces the same key of `old`."""
+    j = 0
+    for k, v in old:
+        while j < len(new) and new[j][0] < k:
+            yield new[j]
+            j += 1
+        if j < len(new) and new[j][0] == k:
+            yield new[j]
+            j += 1
+        else:
+            yield k, v
+    yield from new[j:]
+
+
+def update(path: str, items: Iterable[Tuple[bytes, bytes]]) -> None:
+    """Add `items` to the existing environment `path`: a key that exists is replaced, as `txn.put` does.  The route is REWRITTEN
+    in this module's own page layout (see the module docstring): every existing pair is streamed, merged with `items` in key
+    order, into a new file beside data.mdb, which takes data.mdb's place (os.replace) once it is complete and synced - a run
+    killed at any point leaves the old route or the new one, never a torn file, and no temporary file survives success.  Host
+    memory holds `items` and one pair of the old route at a time, not the route.  An environment of this module that already
+    has the route open keeps reading the old file until it is reopened."""
+    new = {}
+    for k, v in items:
+        new[bytes(k)] = bytes(v)                     # (a repeated key: the last one wins, as consecutive puts)
+    new = sorted(new.items())
+    fname = os.path.join(path, "data.mdb") if os.path.isdir(path) else path
+    tmp = f"{fname}.update-{os.getpid()}"
+    env = Environment(path)
+    try:
+        with builtins.open(tmp, "wb") as f:
+            _bulk_load(f, _merged(env.begin().items(), new), env.psize)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, fname)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        raise
+    finally:
+        env.close()
+    try:                                             # make the rename itself durable where the platform allows it
+        d = os.open(os.path.dirname(os.path.abspath(fname)), os.O_RDONLY)
+        try:
+            os.fsync(d)
+        finally:
+            os.close(d)
+    except OSError:
+        pass

@@ -197,6 +197,58 @@ def paint(lidar: torch.Tensor, sem: torch.Tensor, cams, want_uvz: bool = False):
     return (fused, uvz) if want_uvz else fused
 
 
+def make_cameras_f64(mats) -> C.Array:
+    """mats: sequence of (K 3x3, lidar_to_world 4x4, world_to_cam 4x4) float64 arrays, or of objects with those three as
+    attributes K, lidar_to_world, world_to_cam (lav_amd.data.datasets.CameraProjection) -> lav_camera_f64 records."""
+    arr = (_lib.CameraF64 * len(mats))()
+    for cam, m in zip(arr, mats):
+        K, l2w, w2c = (m.K, m.lidar_to_world, m.world_to_cam) if hasattr(m, "world_to_cam") else m
+        cam.K[:] = [float(v) for v in np.asarray(K, np.float64).reshape(9)]
+        cam.l2w[:] = [float(v) for v in np.asarray(l2w, np.float64).reshape(16)]
+        cam.w2c[:] = [float(v) for v in np.asarray(w2c, np.float64).reshape(16)]
+    return arr
+
+
+def paint_frames(lidar: torch.Tensor, offsets: torch.Tensor, sem: torch.Tensor, cams, want_uvz: bool = False):
+    """The offline painter for a batch of frames in one launch (lav_paint_frames).  lidar (total, Dl) f32: the frames' clouds one
+    after the other; offsets (frames + 1,) int32 in HBM, offsets[0] = 0, offsets[-1] = total; sem (frames, ncam, 1+Cs, H, W) class
+    probabilities; cams: make_cameras_f64(...) of ncam cameras -> painted (total, Cs) [+ uvz (ncam, total, 3) int32]."""
+    lib = _lib.load()
+    lidar = _f32c(lidar, "lidar")
+    sem = _f32c(sem, "sem")
+    if not (offsets.is_cuda and offsets.dtype == torch.int32 and offsets.dim() == 1):
+        raise RuntimeError(f"offsets: expected a 1-d int32 tensor in HBM, got {offsets.dtype} {tuple(offsets.shape)} on {offsets.device}")
+    offsets = offsets.contiguous()
+    total, dl = lidar.shape
+    frames, ncam, cs1, h, w = sem.shape
+    if offsets.numel() != frames + 1:
+        raise RuntimeError(f"offsets: {offsets.numel()} entries for {frames} frames (frames + 1 expected)")
+    if not 1 <= ncam <= _lib.MAX_CAM_F64:
+        raise RuntimeError(f"paint_frames: ncam {ncam} outside [1,{_lib.MAX_CAM_F64}]")
+    if len(cams) != ncam:
+        raise RuntimeError(f"{len(cams)} camera records for {ncam} cameras' maps")
+    painted = torch.empty((total, cs1 - 1), dtype=torch.float32, device=lidar.device)
+    uvz = torch.empty((ncam, total, 3), dtype=torch.int32, device=lidar.device) if want_uvz else None
+    check(lib.lav_paint_frames(_ptr(lidar), _ptr(offsets), frames, total, dl, _ptr(sem), ncam, cs1 - 1, h, w, cams, _ptr(painted),
+                               _ptr(uvz), _stream()), "lav_paint_frames")
+    return (painted, uvz) if want_uvz else painted
+
+
+def image_u8_to_f32(img: torch.Tensor, reverse: bool = False) -> torch.Tensor:
+    """img (n, H, W, 3 or 4) uint8 in HBM -> (n, 3, H, W) float32 of its first three channels, reversed with `reverse`
+    (BGR / BGRA -> RGB).  Exact."""
+    lib = _lib.load()
+    if not img.is_cuda:
+        raise RuntimeError(f"img: expected a tensor in HBM (cuda/hip device), got {img.device}; lav_amd has no CPU path")
+    if img.dtype != torch.uint8 or img.dim() != 4:
+        raise RuntimeError(f"img: expected (n, H, W, C) uint8, got {img.dtype} {tuple(img.shape)}")
+    img = img.contiguous()
+    n, h, w, c = img.shape
+    out = torch.empty((n, 3, h, w), dtype=torch.float32, device=img.device)
+    check(lib.lav_image_u8_to_f32(_ptr(img), n, h, w, c, int(bool(reverse)), _ptr(out), _stream()), "lav_image_u8_to_f32")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ GRU decoders
 def gru_cast(embd, w_ih, w_hh, b_ih, b_hh, mlp_w, mlp_b, T: int):
     """embd (B, E); stacked per-command GRU/MLP weights -> (B, num_cmds, T, 2)."""
