@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 32
+#define LAV_ABI_VERSION 33
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -761,6 +761,54 @@ int lav_paint_frames(const float *lidar, const int *offsets, int frames, int tot
 /* img [n][h][w][c_src] uint8 (c_src 3 or 4) -> out [n][3][h][w] float32 of channels 0, 1, 2 (reverse != 0: 2, 1, 0 - BGR(A) ->
  * RGB, point_paint_dataset.py:32).  Exact. */
 int lav_image_u8_to_f32(const unsigned char *img, int n, int h, int w, int c_src, int reverse, float *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Image augmentation for the camera trainers (ABI 33): the reference's augment(0.5) (lav/utils/augmenter.py: seven imgaug
+ * operations in random order, each with probability 0.5) restated as this library's own specification - parity with imgaug is
+ * UNPINNED (no imgaug, no recorded outputs); what is pinned is this kernel against lav_amd.data.augment.augment_numpy.
+ * One record per image, drawn on the host (lav_amd.data.augment.Augmenter.draw).  32 four-byte words.
+ * ------------------------------------------------------------------------------------------ */
+enum { LAV_AUG_BLUR = 0, LAV_AUG_NOISE = 1, LAV_AUG_DROPOUT = 2, LAV_AUG_MULTIPLY = 3, LAV_AUG_CONTRAST = 4, LAV_AUG_GRAYSCALE = 5,
+       LAV_AUG_ELASTIC = 6, LAV_AUG_OPS = 7 };
+
+typedef struct lav_augment_params {
+    int order[7];          /* the ops in execution order; a permutation of 0..6 (a repeated neighbourhood op or another id is skipped) */
+    int active;            /* bit op: that op runs */
+    int per_channel;       /* bit LAV_AUG_NOISE / LAV_AUG_DROPOUT: one random draw per pixel-channel instead of per pixel */
+    unsigned sample;       /* Philox counter word 2: the sample id */
+    unsigned tag;          /* Philox counter word 3 is tag | op << 8 | draw index; the stream tag sits in bits 16..31 */
+    float blur_sigma;      /* informational (the kernel reads blur_w) */
+    float blur_w[5];       /* normalised 5-tap Gaussian, computed in float64 on the host */
+    float noise_scale;
+    float dropout_p;
+    float multiply[3];     /* per channel (three equal values when not per_channel) */
+    float contrast[3];
+    float gray_alpha;
+    float elastic_alpha;
+    float field_w[5];      /* the 5-tap Gaussian at sigma = 0.25 that smooths the displacement field */
+} lav_augment_params;
+
+/*
+ * in, out  [n][h][w][3] uint8 (HWC, RGB), in != out and not overlapping (halos are read from `in`); h, w >= 1.
+ * params   DEVICE array of n records.  seed: the Philox4x32-10 key (low word, high word); the counter of a pixel's random words is
+ *          (x, y, params.sample, params.tag | op << 8 | draw), so they depend on the global pixel only, never on tile or launch shape;
+ *          uniforms are (word >> 8) * 2^-24.
+ * Every op maps uint8 to uint8: float32 arithmetic, every product and sum rounded separately in a fixed order, round-half-to-even
+ * and clip to [0, 255] after the op.
+ *   blur       separable 5-tap (horizontal, then vertical; float32 in between), border reflect-101
+ *   noise      v + scale z,  z = sqrtf(-2 logf(u1)) cosf(2 pi u2), u1 = ((word >> 8) + 1) 2^-24; draw 0 words 0,1 (all channels, or
+ *              channel 0) and 2,3 (channel 1), draw 1 words 0,1 (channel 2)
+ *   dropout    0 where u < p (draw 0 word c of channel c; word 0 for all when not per_channel)
+ *   multiply   v m[c]                contrast   128 + a[c] (v - 128)      (these two in float64, where they are exact)
+ *   grayscale  g = (4899 R + 9617 G + 1868 B + 8192) >> 14;  v + alpha (g - v)
+ *   elastic    raw field (dx, dy) = 2u - 1 from draw 0 words 0, 1 of every pixel; smoothed by field_w like blur (reflect-101), times
+ *              alpha; out(x, y) = Keys bicubic (a = -0.75) of the image at (x - dx, y - dy), rows then columns, taps outside the image 0
+ * The whole chain of an image runs in ONE launch: a workgroup owns a 64 x 32 output tile, loads it with a halo of 8 into LDS and
+ * runs the active ops between two LDS buffers (blur consumes 2 of the halo, elastic 6: |displacement| <= 3.5 plus the cubic
+ * footprint); pointwise ops are recomputed in the halo.  Wrong records give wrong pixels, never an access outside in / out / LDS.
+ */
+int lav_augment_u8(const unsigned char *in, unsigned char *out, int n, int h, int w, const lav_augment_params *params,
+                   unsigned long long seed, void *stream);
 
 #ifdef __cplusplus
 }

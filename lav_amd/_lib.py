@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LAV_AMD_LIB") or os.path.join(HERE, "liblav_amd.so")   # LAV_AMD_LIB: A/B a second build
 
-ABI_VERSION = 32
+ABI_VERSION = 33
 MAX_CAM = 4
 MAX_CAM_F64 = 8
 
@@ -154,6 +154,7 @@ SIGNATURES = {
     "lav_stack_sweeps": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "lav_extract_peaks_workspace_bytes": (_Z, [_I, _I, _I]),
     "lav_extract_peaks": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _Z, _P]),
+    "lav_augment_u8": (_I, [_P, _P, _I, _I, _I, _P, C.c_ulonglong, _P]),
 }
 
 _lib = None

@@ -10,9 +10,10 @@ the point shuffle), so that a seeded reference loader and a seeded loader of thi
 Routes are read with lav_amd.data.lmdb_ro (no liblmdb here), images with lav_amd.data.image (no OpenCV here).
 
 Differences from the reference, all deliberate: route directories are visited in sorted order (the reference takes
-`glob` order, which is file-system dependent); the 'seg' and 'bra' loaders apply no image augmentation (the reference's
-`augment(0.5)` - blur, noise, pixel dropout, colour, contrast, grayscale and elastic warps - is built on imgaug, which this
-build does not have: their samples are the reference's with the augmenter as the identity); the 'rgb' loader (the v1 brake
+`glob` order, which is file-system dependent); the 'seg' and 'bra' loaders apply no image augmentation themselves (the
+reference's `augment(0.5)` - blur, noise, pixel dropout, colour, contrast, grayscale and elastic warps - is built on imgaug,
+which this build does not have: their samples are the reference's with the augmenter as the identity, and the trainers augment
+the uploaded uint8 batch on the device instead - lav_amd.data.augment, `--augment`); the 'rgb' loader (the v1 brake
 trainer's, lav/train_bra.py) is not provided.
 """
 from __future__ import annotations

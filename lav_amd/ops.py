@@ -249,6 +249,28 @@ def image_u8_to_f32(img: torch.Tensor, reverse: bool = False) -> torch.Tensor:
     return out
 
 
+def augment_u8(images: torch.Tensor, params: np.ndarray, seed: int) -> torch.Tensor:
+    """The camera trainers' image augmentation in one launch (lav_augment_u8): images (n, H, W, 3) uint8 in HBM, params n records
+    of lav_amd.data.augment.PARAMS_DTYPE (host; uploaded here, 128 bytes per image), seed the 64-bit Philox key -> the augmented
+    (n, H, W, 3) uint8 images in a new tensor.  Bit-identical to lav_amd.data.augment.augment_numpy except for noise's rounding ties."""
+    from .data.augment import check_params
+    lib = _lib.load()
+    if not images.is_cuda:
+        raise RuntimeError(f"images: expected a tensor in HBM (cuda/hip device), got {images.device}; lav_amd.ops has no CPU path "
+                           "(lav_amd.data.augment.Augmenter runs augment_numpy on CPU tensors)")
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise RuntimeError(f"images: expected (n, H, W, 3) uint8, got {images.dtype} {tuple(images.shape)}")
+    images = images.contiguous()
+    n, h, w, _ = images.shape
+    params = check_params(params, n)
+    out = torch.empty_like(images)
+    if n == 0 or h == 0 or w == 0:
+        return out
+    table = torch.from_numpy(params.view(np.uint8).reshape(n, -1)).to(images.device)
+    check(lib.lav_augment_u8(_ptr(images), _ptr(out), n, h, w, _ptr(table), int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()), "lav_augment_u8")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ GRU decoders
 def gru_cast(embd, w_ih, w_hh, b_ih, b_hh, mlp_w, mlp_b, T: int):
     """embd (B, E); stacked per-command GRU/MLP weights -> (B, num_cmds, T, 2)."""

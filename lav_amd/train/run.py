@@ -292,11 +292,28 @@ def main(what):
         dist.destroy_process_group()
 
 
+def _augmenters(args, rank, world, streams):
+    """--augment PROB > 0: one lav_amd.data.augment.Augmenter per image stream (stream tags 0, 1, ...), every rank with its own sample
+    ids; None for 0 (nothing changes: no uint8 upload, no launch)."""
+    if not 0.0 <= args.augment <= 1.0:
+        raise SystemExit(f"--augment {args.augment}: a probability")
+    if args.augment == 0.0:
+        return None
+    from ..data.augment import Augmenter
+    return [Augmenter(args.augment, seed=args.seed, rank=rank, world=world, stream_tag=t) for t in range(streams)]
+
+
+def _as_u8_hwc(rgb):
+    """(B, H, W, 3) uint8 of a batch of images, whatever dtype they arrive in (the loaders and the synthetic batches yield uint8)."""
+    return rgb if rgb.dtype == torch.uint8 else rgb.round().clamp(0, 255).to(torch.uint8)
+
+
 def main_seg():
     """Command line of lav/train_seg.py (same flags and defaults; --config-path defaults to the v2 agent's config, the consumer
     of the segmenter): the camera images of the config's data_dir through the 'seg' loader, one Adam step per batch,
     seg_{epoch}.th saved every --num-per-save epochs with RGBSegmentationModel's keys (the agent's `seg_model_dir`).  What this
-    build adds: --synthetic / --steps-per-epoch (seeded synthetic 288 x 256 images), --save-dir, --seg (a checkpoint to start from)."""
+    build adds: --synthetic / --steps-per-epoch (seeded synthetic 288 x 256 images), --save-dir, --seg (a checkpoint to start from),
+    --augment PROB (the reference's augment(0.5) of every camera image, here on the device: lav_amd.data.augment)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--config-path", default="config_v2.yaml", help="the reference's config_v2.yaml (seg_channels, data_dir)")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
@@ -311,6 +328,9 @@ def main_seg():
     ap.add_argument("--steps-per-epoch", type=int, default=20, help="iterations that make one epoch of synthetic data")
     ap.add_argument("--save-dir", default="checkpoints")
     ap.add_argument("--seg", default=None, help="seg_*.th to start from")
+    ap.add_argument("--augment", type=float, default=0.0, metavar="PROB",
+                    help="image augmentation (lav_amd.data.augment): each of the seven ops with this probability, on the device, after a "
+                         "uint8 upload; the reference trains with 0.5 (augment(0.5)).  Default 0: no augmentation")
     args = ap.parse_args()
     have_cfg = bool(args.config_path) and os.path.isfile(args.config_path)
     if not args.synthetic and not have_cfg:
@@ -331,6 +351,8 @@ def main_seg():
         if len(loader) == 0:
             raise SystemExit(f"{args.config_path}: data_dir holds fewer camera images than one batch of {args.batch_size}")
     torch.manual_seed(args.seed)
+    aug = _augmenters(args, rank, world, 1)
+    aug = aug[0] if aug else None
 
     def batches(epoch):
         if loader is not None:
@@ -345,6 +367,8 @@ def main_seg():
     global_it, t0 = 0, time.perf_counter()
     for epoch in range(args.num_epoch):
         for rgb, sem in batches(epoch):
+            if aug is not None:
+                rgb = aug(_as_u8_hwc(rgb).to(device))      # uploaded as uint8 and augmented there; train_seg converts it as ever
             info = lav.train_seg(rgb, sem)
             if global_it % args.num_per_log == 0 and rank == 0:
                 print(global_it, dict(loss=round(info["loss"], 4)), flush=True)
@@ -371,7 +395,8 @@ def main_bra():
     """Command line of lav/train_bra_v2.py (same flags and defaults): the 'bra' loader over the config's data_dir (the three front
     cameras side by side, the telephoto camera, their labels, the brake flag), one Adam step per batch, bra_{epoch}.th saved every
     --num-per-save epochs with RGBBrakePredictionModel([4, 10, 18])'s keys (the agent's `bra_model_dir`).  What this build adds:
-    --synthetic / --steps-per-epoch (seeded synthetic 288 x 768 + 192 x 480 images), --save-dir, --bra (a checkpoint to start from)."""
+    --synthetic / --steps-per-epoch (seeded synthetic 288 x 768 + 192 x 480 images), --save-dir, --bra (a checkpoint to start from),
+    --augment PROB (the reference's augment(0.5) of the wide and the telephoto image, here on the device: lav_amd.data.augment)."""
     from .brake import BRA_LABELS, BrakeTrainer
     from .synthetic import synthetic_bra_batch
     ap = argparse.ArgumentParser()
@@ -388,6 +413,9 @@ def main_bra():
     ap.add_argument("--steps-per-epoch", type=int, default=20, help="iterations that make one epoch of synthetic data")
     ap.add_argument("--save-dir", default="checkpoints")
     ap.add_argument("--bra", default=None, help="bra_*.th to start from")
+    ap.add_argument("--augment", type=float, default=0.0, metavar="PROB",
+                    help="image augmentation (lav_amd.data.augment): each of the seven ops with this probability, on the device, after a "
+                         "uint8 upload; the reference trains with 0.5 (augment(0.5)).  Default 0: no augmentation")
     args = ap.parse_args()
     have_cfg = bool(args.config_path) and os.path.isfile(args.config_path)
     if not args.synthetic and not have_cfg:
@@ -408,6 +436,7 @@ def main_bra():
         if len(loader) == 0:
             raise SystemExit(f"{args.config_path}: data_dir holds fewer frames than one batch of {args.batch_size}")
     torch.manual_seed(args.seed)
+    aug = _augmenters(args, rank, world, 2)      # wide, tele: separate stream tags
 
     def batches(epoch):
         if loader is not None:
@@ -422,6 +451,8 @@ def main_bra():
     global_it, t0 = 0, time.perf_counter()
     for epoch in range(args.num_epoch):
         for rgb1, rgb2, sem1, sem2, bra in batches(epoch):
+            if aug is not None:
+                rgb1, rgb2 = aug[0](_as_u8_hwc(rgb1).to(device)), aug[1](_as_u8_hwc(rgb2).to(device))
             info = trainer.train_bra(rgb1, rgb2, sem1, sem2, bra)
             if global_it % args.num_per_log == 0 and rank == 0:
                 print(global_it, dict(loss=round(info["loss"], 4), bra=info["bra"], pred_bra=round(info["pred_bra"], 4)), flush=True)
