@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 33
+#define LAV_ABI_VERSION 34
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -809,6 +809,33 @@ typedef struct lav_augment_params {
  */
 int lav_augment_u8(const unsigned char *in, unsigned char *out, int n, int h, int w, const lav_augment_params *params,
                    unsigned long long seed, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The data loaders' BEV map stacks behind the upload (ABI 34; train_bev_v2 / train_full_v2 --bev-on-device).  Every BEV plane of
+ * every loader (lav/utils/datasets/{bev,temporal_bev,lidar,lidar_painted,temporal_lidar_painted}_dataset.py) is
+ *     out = ( W2( crop( W1(src) ) ) > 0 )
+ * W1, W2: cv2.warpAffine(INTER_LINEAR, constant border 0) on 8-bit images as lav_amd/data/image.py:warp_inverse_linear restates its
+ * fixed-point path; crop(I)[r][c] = I[r + shift[0]][c + shift[1]], zero where that leaves the image.  Parity with OpenCV itself is
+ * UNPINNED (as for the restatement); pinned, bit for bit, is this kernel against lav_amd.data.bev_stack.bev_stack_numpy.
+ *
+ * planes  [n][h][w] uint8, the decoded source planes; out [n][h][w] uint8, not overlapping planes; h, w >= 1 (any size).
+ * coef    DEVICE [n][12] float64: the inverse map i00, i01, i10, i11, b1, b2 of W1, then of W2 - output pixel (x, y) samples
+ *         (i00 x + i01 y + b1, i10 x + i11 y + b2).  Computed on the host (lav_amd.data.image.inverse_map): the device evaluates no
+ *         trigonometric function and no division.  Finite, and no map may reach beyond +-2^30 pixels.
+ * shift   DEVICE [n][2] int32: rows, columns.
+ * threshold != 0: out = value > 0 (0 / 1); 0: the interpolated value.
+ * Per warp, in float64 with every product and sum rounded on its own: X = rint((i00 x) 1024) + rint((i01 y + b1) 1024) + 16 (Y alike
+ * from i10, i11, b2) as 64-bit integers; sx = clamp(X >> 10, -32768, 32767), fx = (X >> 5) & 31; the four taps (sy, sx) .. (sy + 1,
+ * sx + 1), zero outside the image, with weights (32 - fy)(32 - fx) 32, (32 - fy) fx 32, fy (32 - fx) 32, fy fx 32; (sum + 2^14) >> 15.
+ * One launch for all n planes; a workgroup owns a 64 x 32 tile and keeps the tile's footprint of W1(src) in LDS (it never reaches HBM);
+ * a tile whose footprints exceed the LDS budget (8 KiB of W1(src), 16 KiB of src: no rotation does, a map that shrinks the image can)
+ * interpolates every pixel from global memory instead.  Wrong records give wrong pixels, never an access outside planes / out / LDS.
+ */
+int lav_bev_stack_u8(const unsigned char *planes, const double *coef, const int *shift, unsigned char *out, int n, int h, int w,
+                     int threshold, void *stream);
+/* The launcher's rule, on the host: how many of one plane's tiles are zero without reading anything (counts[0]), staged in LDS
+ * (counts[1]) and interpolated from global memory (counts[2]).  coef [12] and shift [2] are HOST pointers here.  No device needed. */
+int lav_bev_stack_tile_paths(const double *coef, const int *shift, int h, int w, int *counts);
 
 #ifdef __cplusplus
 }

@@ -27,7 +27,7 @@ import torch
 import yaml
 from torch.utils.data import DataLoader, Dataset
 
-from . import image, lmdb_ro
+from . import bev_stack, image, lmdb_ro
 
 TRAIN_TOWNS = ("Town01", "Town03", "Town04", "Town06")
 BEV_CENTER = (160, 280)          # ego pixel of the recorded 320x320 BEV maps: the centre of every rotation augment
@@ -157,6 +157,8 @@ class RouteFrames(Dataset):
     """Every frame of every recorded route under `data_dir` that has num_plan future frames (basic_dataset.py:12-77).
     The YAML's keys become attributes, as in the reference."""
 
+    bev_on_device = False     # True: samples carry a bev_stack.BevRecord where the tuple holds `bev` (rendered behind the upload)
+
     def __init__(self, config_path, close_txn=False, seed=2021):
         super().__init__()
         with open(config_path, "r") as f:
@@ -200,24 +202,50 @@ class RouteFrames(Dataset):
     def _bev_stack(self, txn, index, angle, y_offset=0):
         """(3 + 2 (num_frame_stack + 1), 320, 320): road / lane channels of the current frame, then (vehicles, pedestrians) of
         the current and the stacked past frames moved into the current ego frame (temporal_bev_dataset.py:34-66)."""
+        deferred = self.bev_on_device
         bev = np.zeros((3 + 2 * (self.num_frame_stack + 1), 320, 320), np.uint8)
-        bev[:3] = self._bev_channels(txn, index, [0, 9, 10], angle_offset=angle, y_offset=y_offset)
+        parts = [self._bev_channels(txn, index, [0, 9, 10], angle_offset=angle, y_offset=y_offset)]
+        if not deferred:
+            bev[:3] = parts[0]
         for k, i in enumerate(reversed(range(index - self.num_frame_stack, index + 1))):
             if i < 0:
+                parts.append(bev_stack.zero_record(2, 320, 320))
                 continue
             _, locs_i, oris_i, *_ = self._tracks(txn, i)
             if i == index:
                 loc0, ori0 = locs_i[0], oris_i[0]
             dloc = (locs_i[0] - loc0) @ [[np.cos(ori0), -np.sin(ori0)], [np.sin(ori0), np.cos(ori0)]] * self.pixels_per_meter
-            bev[3 + 2 * k:5 + 2 * k] = self._bev_channels(txn, i, [1, 2], angle=oris_i[0] - ori0, angle_offset=angle, y_offset=y_offset, loc=dloc)
-        return bev
+            parts.append(self._bev_channels(txn, i, [1, 2], angle=oris_i[0] - ori0, angle_offset=angle, y_offset=y_offset, loc=dloc))
+            if not deferred:
+                bev[3 + 2 * k:5 + 2 * k] = parts[-1]
+        return bev_stack.concat_records(parts) if deferred else bev
 
     def _bev_channels(self, txn, t, channels, angle=0, angle_offset=0, y_offset=0, loc=(0, 0)):
         dx, dy = map(int, loc)
+        if self.bev_on_device:
+            return self._bev_record(txn, t, channels, -angle * 180 / math.pi, (dx, dy + y_offset), angle_offset)
         bev = rotate_image(read_bev(txn, t, channels), -angle * 180 / math.pi)
         bev = np.pad(bev, [[MARGIN, MARGIN], [MARGIN, MARGIN], [0, 0]])
         bev = bev[dx + MARGIN:dx + MARGIN + 320, dy + MARGIN + y_offset:dy + MARGIN + y_offset + 320, :]
         return (rotate_image(bev, angle_offset) > 0).astype(np.uint8).transpose(2, 0, 1)
+
+    def _bev_frame(self, txn, index, angle, offset=0):
+        """(5, 320, 320): the single-frame loaders' map, rotated by the jitter angle and moved `offset` columns
+        (bev_dataset.py:47-51, lidar_dataset.py:47)."""
+        if self.bev_on_device:
+            return self._bev_record(txn, index, [0, 1, 2, 9, 10], angle, (0, offset), None)
+        bev = (rotate_image(read_bev(txn, index, [0, 1, 2, 9, 10]), angle) > 0).astype(np.uint8).transpose(2, 0, 1)
+        if offset:
+            bev = np.pad(bev, [[0, 0], [MARGIN, MARGIN], [MARGIN, MARGIN]])[:, MARGIN:MARGIN + 320, MARGIN + offset:MARGIN + offset + 320]
+        return bev
+
+    def _bev_record(self, txn, t, channels, angle1_deg, shift, angle2_deg):
+        """The deferred form of a frame's map channels: out = (W2(crop(W1(src))) > 0) as a bev_stack.BevRecord - the planes as
+        decoded, the rotations about BEV_CENTER as inverse-map coefficients (angle2_deg None: W2 is the identity).  Every BEV plane of
+        every loader comes through here when bev_on_device is set."""
+        planes = read_bev(txn, t, channels).transpose(2, 0, 1)
+        w2 = None if angle2_deg is None else image.rotation_matrix_2d(BEV_CENTER, angle2_deg, 1.0)
+        return bev_stack.plane_record(planes, image.rotation_matrix_2d(BEV_CENTER, angle1_deg, 1.0), shift, w2, limit=MARGIN, frame=t)
 
     def _commands(self, txn, index):
         return (int(read_array(txn, "cmd", index, np.uint8).reshape(-1)[0]), int(read_array(txn, "bra", index, np.uint8).reshape(-1)[0]),
@@ -243,8 +271,7 @@ class BEVDataset(RouteFrames):
         if self.temporal:
             bev = self._bev_stack(txn, index, angle, y_offset=offset)
         else:
-            bev = (rotate_image(read_bev(txn, index, [0, 1, 2, 9, 10]), angle) > 0).astype(np.uint8).transpose(2, 0, 1)
-            bev = np.pad(bev, [[0, 0], [MARGIN, MARGIN], [MARGIN, MARGIN]])[:, MARGIN:MARGIN + 320, MARGIN + offset:MARGIN + offset + 320]
+            bev = self._bev_frame(txn, index, angle, int(offset))
         shift = [offset / self.pixels_per_meter, 0]
         cmd, bra, nxp = self._commands(txn, index)
         if self.temporal:     # the two loaders rotate in a different order; the pivot is the (already moved) ego position
@@ -326,7 +353,7 @@ class LiDARDataset(RouteFrames):
         ego_locs, locs, oris, bbox, typs = to_ego_frame(ego_locs, locs, oris, bbox, typs, ego_oris[0], self.num_plan + 1)
         angle = float(torch.rand(1) * 2 - 1) * self.angle_jitter
         cmd, bra, nxp = self._commands(txn, index)
-        bev = (rotate_image(read_bev(txn, index, [0, 1, 2, 9, 10]), angle) > 0).astype(np.uint8).transpose(2, 0, 1)
+        bev = self._bev_frame(txn, index, angle)
         if not self.painted:
             xyzr = self.drop_ego_points(xyzr)
         xyzr = rotate_lidar(xyzr[:, :4], -angle)
@@ -463,15 +490,20 @@ LOADERS = {"bev": BEVDataset, "temporal_bev": TemporalBEVDataset, "lidar": LiDAR
            "temporal_lidar_painted": TemporalLiDARPaintedDataset, "seg": SegmentationDataset, "bra": BrakePredictionDataset}
 
 
-def get_data_loader(data_type, args, rank: int = 0, world: int = 1):
+def get_data_loader(data_type, args, rank: int = 0, world: int = 1, bev_on_device: bool = False):
     """lav/utils/datasets/__init__.py:12-40: shuffled, drop_last batches of `args.batch_size` from `args.config_path`'s data_dir.
     The reference feeds one loader of the global batch to nn.DataParallel; with one process per GPU (world > 1) every rank
     draws its own disjoint shard of each epoch (DistributedSampler; call loader.sampler.set_epoch(epoch)) in batches of
-    batch_size / world."""
+    batch_size / world.  bev_on_device (the five loaders with a BEV map): the batches carry a bev_stack.BevRecord - planes (B, P, 320, 320)
+    uint8, coef (B, P, 12) float64, shift (B, P, 2) int32 - where they carry `bev`, for lav_amd.data.bev_stack.BevStacker."""
     if data_type not in LOADERS:
         raise NotImplementedError(f"data loader {data_type!r}: this build provides {sorted(LOADERS)} (the reference's 'rgb' loader "
                                   "feeds the v1 trainer train_bra.py, which is not part of it)")
     dataset = LOADERS[data_type](args.config_path, seed=args.seed)
+    if bev_on_device:
+        if data_type in ("seg", "bra"):
+            raise ValueError(f"data loader {data_type!r} has no BEV map to defer")
+        dataset.bev_on_device = True
     common = dict(num_workers=args.num_workers, drop_last=True, pin_memory=torch.cuda.is_available())
     if world > 1:
         from torch.utils.data.distributed import DistributedSampler

@@ -45,12 +45,12 @@ def rotation_matrix_2d(center, angle_deg: float, scale: float = 1.0) -> np.ndarr
     return np.array([[alpha, beta, (1 - alpha) * cx - beta * cy], [-beta, alpha, beta * cx + (1 - alpha) * cy]], np.float64)
 
 
-def warp_affine_linear(image: np.ndarray, M: np.ndarray) -> np.ndarray:
-    """cv2.warpAffine(image, M, (W, H), flags=INTER_LINEAR) for uint8 images of shape (H, W) or (H, W, C); constant border 0."""
-    if image.dtype != np.uint8:
-        raise TypeError("warp_affine_linear restates the 8-bit fixed-point path only")
-    src = image if image.ndim == 3 else image[..., None]
-    H, W, _ = src.shape
+IDENTITY_INVERSE_MAP = (1.0, 0.0, 0.0, 1.0, 0.0, 0.0)
+
+
+def inverse_map(M) -> np.ndarray:
+    """The six float64 coefficients (i00, i01, i10, i11, b1, b2) warpAffine derives from the forward matrix M: output pixel (x, y)
+    samples the source at (i00 x + i01 y + b1, i10 x + i11 y + b2)."""
     m = np.array(M, np.float64).reshape(2, 3)
     # forward map -> inverse map, exactly as warpAffine does it
     D = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
@@ -59,6 +59,24 @@ def warp_affine_linear(image: np.ndarray, M: np.ndarray) -> np.ndarray:
     i00, i01, i10, i11 = a11, m[0, 1] * -D, m[1, 0] * -D, a22
     b1 = -i00 * m[0, 2] - i01 * m[1, 2]
     b2 = -i10 * m[0, 2] - i11 * m[1, 2]
+    return np.array([i00, i01, i10, i11, b1, b2], np.float64)
+
+
+def warp_affine_linear(image: np.ndarray, M: np.ndarray) -> np.ndarray:
+    """cv2.warpAffine(image, M, (W, H), flags=INTER_LINEAR) for uint8 images of shape (H, W) or (H, W, C); constant border 0."""
+    if image.dtype != np.uint8:
+        raise TypeError("warp_affine_linear restates the 8-bit fixed-point path only")
+    return warp_inverse_linear(image, inverse_map(M))
+
+
+def warp_inverse_linear(image: np.ndarray, coef) -> np.ndarray:
+    """warp_affine_linear from the inverse map's coefficients (inverse_map's six): the fixed-point remap itself.  This is the
+    arithmetic lav_bev_stack_u8 (csrc/bev_stack.hip) reproduces bit for bit."""
+    if image.dtype != np.uint8:
+        raise TypeError("warp_inverse_linear restates the 8-bit fixed-point path only")
+    src = image if image.ndim == 3 else image[..., None]
+    H, W, _ = src.shape
+    i00, i01, i10, i11, b1, b2 = (np.float64(c) for c in coef)
     AB_SCALE, ROUND = 1024, 16
     xs = np.arange(W, dtype=np.float64)
     ys = np.arange(H, dtype=np.float64)

@@ -271,6 +271,41 @@ def augment_u8(images: torch.Tensor, params: np.ndarray, seed: int) -> torch.Ten
     return out
 
 
+def bev_stack_u8(planes: torch.Tensor, coef, shift, threshold: bool = True) -> torch.Tensor:
+    """The loaders' BEV stacks in one launch (lav_bev_stack_u8): planes (..., P, H, W) uint8 in HBM, coef (..., P, 12) float64 and shift
+    (..., P, 2) int32 (arrays or tensors, host or device; uploaded here) -> W2(crop(W1(planes))) > 0 per plane, or the interpolated
+    values with threshold=False, in a new uint8 tensor.  Bit-identical to lav_amd.data.bev_stack.bev_stack_numpy."""
+    from .data.bev_stack import check_record
+    lib = _lib.load()
+    if not planes.is_cuda:
+        raise RuntimeError(f"planes: expected a tensor in HBM (cuda/hip device), got {planes.device}; lav_amd.ops has no CPU path "
+                           "(lav_amd.data.bev_stack.BevStacker runs bev_stack_numpy on CPU tensors)")
+    if planes.dtype != torch.uint8 or planes.dim() < 3:
+        raise RuntimeError(f"planes: expected (..., P, H, W) uint8, got {planes.dtype} {tuple(planes.shape)}")
+    planes = planes.contiguous()
+    coef, shift = check_record(planes.shape, coef, shift)
+    out = torch.empty_like(planes)
+    h, w = planes.shape[-2:]
+    n = len(coef)
+    if n == 0 or h == 0 or w == 0:
+        return out
+    coef_d, shift_d = torch.from_numpy(coef).to(planes.device), torch.from_numpy(shift).to(planes.device)
+    check(lib.lav_bev_stack_u8(_ptr(planes), _ptr(coef_d), _ptr(shift_d), _ptr(out), n, h, w, int(bool(threshold)), _stream()), "lav_bev_stack_u8")
+    return out
+
+
+def bev_stack_tile_paths(coef, shift, h: int, w: int):
+    """(zero, staged, direct): how many of a plane's 64 x 32 tiles lav_bev_stack_u8 leaves zero, renders from LDS and renders from
+    global memory - the kernel's own rule, evaluated on the host (lav_bev_stack_tile_paths).  coef (12,), shift (2,)."""
+    import ctypes
+    coef = np.ascontiguousarray(np.asarray(coef, np.float64).reshape(12))
+    shift = np.ascontiguousarray(np.asarray(shift, np.int32).reshape(2))
+    counts = (ctypes.c_int * 3)()
+    check(_lib.load().lav_bev_stack_tile_paths(coef.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), shift.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                               int(h), int(w), counts), "lav_bev_stack_tile_paths")
+    return tuple(counts)
+
+
 # ------------------------------------------------------------------------------------------ GRU decoders
 def gru_cast(embd, w_ih, w_hh, b_ih, b_hh, mlp_w, mlp_b, T: int):
     """embd (B, E); stacked per-command GRU/MLP weights -> (B, num_cmds, T, 2)."""

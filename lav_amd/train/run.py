@@ -187,7 +187,8 @@ def main(what):
     """Command line of lav/train_full_v2.py:48-70 / lav/train_bev_v2.py:42-63 (same flags and defaults): the recorded routes
     under the config's `data_dir` are read by lav_amd.data ('temporal_lidar_painted' / 'temporal_bev' loaders, every rank its
     own shard of each epoch).  What this build adds: --synthetic / --steps-per-epoch (seeded synthetic batches instead of a
-    data set), --save-dir, --lidar / --bev / --uniplanner (checkpoints to start from), --max-points, --log-every."""
+    data set), --save-dir, --lidar / --bev / --uniplanner (checkpoints to start from), --max-points, --log-every, --bev-on-device
+    (the loaders hand over the decoded map planes and their warps, lav_bev_stack_u8 renders the batch's BEV stacks behind the upload)."""
     if what == "seg":
         return main_seg()
     if what == "bra":
@@ -215,6 +216,10 @@ def main(what):
     ap.add_argument("--log-every", type=int, default=None, help="steps between the eval-mode log inference (default: --num-per-log)")
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible steps: deterministic torch / MIOpen algorithms "
                     "(liblav_amd's own kernels always are); slower convolution gradients")
+    ap.add_argument("--bev-on-device", action="store_true",
+                    help="recorded routes only: the loaders return the decoded map planes with their warp coefficients "
+                         "(lav_amd.data.bev_stack) and the batch's BEV stacks are rendered after the uint8 upload, bit-identical to the "
+                         "loaders' own; no effect with --synthetic")
     args = ap.parse_args()
     if args.deterministic:
         set_deterministic(True)
@@ -236,15 +241,25 @@ def main(what):
     loader = None
     if not args.synthetic:
         from ..data import get_data_loader
-        loader = get_data_loader("temporal_bev" if what == "bev" else "temporal_lidar_painted", args, rank=rank, world=world)
+        loader = get_data_loader("temporal_bev" if what == "bev" else "temporal_lidar_painted", args, rank=rank, world=world,
+                                 bev_on_device=args.bev_on_device)
         if len(loader) == 0:
             raise SystemExit(f"{args.config_path}: data_dir holds fewer frames than one batch of {args.batch_size}")
+
+    stacker, bev_at = None, 0 if what == "bev" else 5      # where the sample tuples hold `bev`
+    if loader is not None and args.bev_on_device:
+        from ..data.bev_stack import BevStacker
+        stacker = BevStacker()
 
     def batches(epoch):
         if loader is not None:
             if world > 1:
                 loader.sampler.set_epoch(epoch)
-            yield from loader
+            for batch in loader:
+                if stacker is not None:      # the planes go up as uint8 (the bytes `bev` itself would take) and are rendered there
+                    batch = list(batch)
+                    batch[bev_at] = stacker(batch[bev_at], device=device)
+                yield batch
             return
         for it in range(args.steps_per_epoch):
             seed = cfg.seed + 1000003 * epoch + 1009 * it + 100 * rank
