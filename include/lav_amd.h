@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 34
+#define LAV_ABI_VERSION 35
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -836,6 +836,35 @@ int lav_bev_stack_u8(const unsigned char *planes, const double *coef, const int 
 /* The launcher's rule, on the host: how many of one plane's tiles are zero without reading anything (counts[0]), staged in LDS
  * (counts[1]) and interpolated from global memory (counts[2]).  coef [12] and shift [2] are HOST pointers here.  No device needed. */
 int lav_bev_stack_tile_paths(const double *coef, const int *shift, int h, int w, int *counts);
+
+/* ------------------------------------------------------------------------------------------
+ * The agent's per-tick debug frame (ABI 35; team_code_v2/lav_agent_fast.py:459-518, 567-581), rendered on the device: the cameras and
+ * the telephoto image resized to the LiDAR panel's height, the LiDAR bird's-eye histogram (lidar_to_bev) with the drawing records on
+ * it, the predicted BEV - side by side as a canvas of x_bins rows and w_rgb + w_tel + y_bins + bev_w columns that exists only tile by
+ * tile in LDS - resized to half its size, with four lines of text.  Specification: lav_amd.agent.debug_view.compose_numpy, bit for
+ * bit.  Parity with OpenCV's rasterisers, its resize and its font is UNPINNED (see there).
+ *
+ * rgb [rgb_h][rgb_w][3], tel [tel_h][tel_w][3] uint8 RGB; cloud [npts][stride] float32, x and y first (rows with a non-finite x or y
+ * and rows outside the grid count nowhere); bev [3][x_bins][bev_w] float32, already sigmoided.
+ * prims   DEVICE [nprims] records of 8 int32: kind (0 dot, 1 segment), x0, y0, x1, y1, radius, colour (r | g << 8 | b << 16), unused;
+ *         LiDAR-panel pixel coordinates within +-2^20, in drawing order - a pixel takes the last record that covers it.  A dot
+ *         covers dx^2 + dy^2 <= radius^2, a segment the pixels whose centre lies within distance 1 of it (and within radius of its
+ *         bounding box).
+ * text    DEVICE [4][text_len] uint8, 7-bit characters; font DEVICE [128][7] uint8, 5 x 7 glyphs, bit 4 the leftmost pixel; line l
+ *         has its baseline-left at (4, 10 + 10 l), glyphs 6 pixels apart, white.
+ * lut     DEVICE [11] uint8: grey of a cell holding 0 .. 10 (or more) points.
+ * tables  DEVICE, 16-byte aligned, rows (i0, i1, w0, w1) int32 of lav_amd.data.image.resize_linear_table for, in this order: the
+ *         camera panel's w_rgb columns, the telephoto panel's w_tel columns, the x_bins rows of each, the frame's columns and rows.
+ *         Indices are clamped on the device: a wrong table gives wrong pixels, never an access outside the images or LDS.
+ * The histogram's edges are np.linspace(start, stop, bins + 1) per axis, binned in float64 by np.histogramdd's rule.
+ * counts  DEVICE workspace [x_bins][y_bins] uint32, zeroed here.  out [x_bins / 2][(canvas columns) / 2][3] uint8.
+ * Up to three operations on `stream`: the zeroing, one launch over the cloud, one over the frame's 32 x 16 tiles.
+ */
+int lav_debug_view(const unsigned char *rgb, int rgb_h, int rgb_w, const unsigned char *tel, int tel_h, int tel_w, const float *cloud,
+                   int npts, int stride, const float *bev, int bev_w, const void *prims, int nprims, const unsigned char *text,
+                   int text_len, const unsigned char *font, const unsigned char *lut, const int *tables, double x_start, double x_stop,
+                   int x_bins, double y_start, double y_stop, int y_bins, int w_rgb, int w_tel, unsigned *counts, unsigned char *out,
+                   void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,9 @@ remapBilinear): the inverse map is evaluated in 1/1024 pixel integers with a rou
 cut to 1/32 pixel, the four weights are (32 - a)(32 - b) * 32 / 32768 exactly, the sum is rounded with +2^14 >> 15, and
 pixels outside the source read the constant border 0.  PARITY UNPINNED against OpenCV itself (none here to compare with);
 the loaders only use the result through `> 0`, so only pixels whose interpolated value rounds to zero could differ.
+
+resize_linear_u8 restates a fourth call, `cv2.resize` on 8-bit images (the agent's debug view, team_code_v2/lav_agent_fast.py:
+497-503), in the same way and with the same caveat: parity with OpenCV itself is UNPINNED.
 """
 from __future__ import annotations
 
@@ -43,6 +46,46 @@ def rotation_matrix_2d(center, angle_deg: float, scale: float = 1.0) -> np.ndarr
     a = angle_deg * np.pi / 180.0
     alpha, beta = np.cos(a) * scale, np.sin(a) * scale
     return np.array([[alpha, beta, (1 - alpha) * cx - beta * cy], [-beta, alpha, beta * cx + (1 - alpha) * cy]], np.float64)
+
+
+def resize_linear_table(src: int, dst: int) -> np.ndarray:
+    """One axis of resize_linear_u8 as (dst, 4) int32 rows (i0, i1, w0, w1): output index d reads source indices i0 and i1 with
+    the 11-bit weights w0 and w1.  The source coordinate is float32((d + 0.5) * scale - 0.5) with scale = src / dst in float64;
+    its floor is the index and the rest the fraction; an index left of the image or on / right of its last pixel is clamped to
+    the edge with the fraction zeroed; the weights are rint(2048 * (1 - fraction)) and rint(2048 * fraction) in float32."""
+    if src < 1 or dst < 1:
+        raise ValueError(f"resize_linear_table: sizes {src} -> {dst}")
+    scale = np.float64(src) / np.float64(dst)
+    f = ((np.arange(dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    i0 = np.floor(f).astype(np.int64)
+    f = f - i0.astype(np.float32)
+    left, right = i0 < 0, i0 >= src - 1
+    f[left | right] = 0
+    i0[left] = 0
+    i0[right] = src - 1
+    w0 = np.rint((np.float32(1) - f) * np.float32(2048)).astype(np.int32)
+    w1 = np.rint(f * np.float32(2048)).astype(np.int32)
+    return np.stack([i0.astype(np.int32), np.minimum(i0 + 1, src - 1).astype(np.int32), w0, w1], axis=1)
+
+
+def resize_linear_u8(image: np.ndarray, dsize) -> np.ndarray:
+    """cv2.resize(image, dsize) (dsize = (width, height), INTER_LINEAR) for uint8 images of shape (H, W) or (H, W, C), restating
+    OpenCV 4's fixed-point path for 8-bit bilinear resizing (imgproc/src/resize.cpp: HResizeLinear / VResizeLinear): the
+    horizontal pass is S[i0] * w0 + S[i1] * w1 unshifted (resize_linear_table holds the indices and the 11-bit weights), the
+    vertical pass (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.  Written from the memory of that source: this
+    function is the specification of the debug view (lav_amd/agent/debug_view.py, csrc/debug_view.hip reproduces it bit for
+    bit); PARITY UNPINNED against OpenCV itself, as for warp_affine_linear."""
+    if image.dtype != np.uint8:
+        raise TypeError("resize_linear_u8 restates the 8-bit fixed-point path only")
+    src = image if image.ndim == 3 else image[..., None]
+    dw, dh = int(dsize[0]), int(dsize[1])
+    tx, ty = resize_linear_table(src.shape[1], dw), resize_linear_table(src.shape[0], dh)
+    s = src.astype(np.int64)
+    rows = s[:, tx[:, 0]] * tx[:, 2].astype(np.int64)[None, :, None] + s[:, tx[:, 1]] * tx[:, 3].astype(np.int64)[None, :, None]
+    b0, b1 = ty[:, 2].astype(np.int64)[:, None, None], ty[:, 3].astype(np.int64)[:, None, None]
+    out = (((b0 * (rows[ty[:, 0]] >> 4)) >> 16) + ((b1 * (rows[ty[:, 1]] >> 4)) >> 16) + 2) >> 2
+    out = np.minimum(out, 255).astype(np.uint8)          # (saturate_cast: a weight pair may sum to 2049)
+    return out if image.ndim == 3 else out[..., 0]
 
 
 IDENTITY_INVERSE_MAP = (1.0, 0.0, 0.0, 1.0, 0.0, 0.0)

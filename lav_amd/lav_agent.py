@@ -5,8 +5,11 @@ setup(path_to_conf_file), run_step(input_data, timestamp) -> VehicleControl, des
 on the GPU in run_step (:233-323) is one call of lav_amd.frame.GraphedFramePipeline.step; the host side (EKF pose,
 route/command tracking, PID, the brake / collision / creep overrides) is restated in lav_amd/agent/.
 
-Differences, all deliberate: no wandb / OpenCV video logging (flush_data and visualize are no-ops); the two camera
-networks are loaded from state_dicts (`seg_model_dir`, `bra_model_dir`) instead of TorchScript traces, because the HIP
+The debug view of the reference (visualize, :459-518) is rendered on the device and recorded when `debug_view: true`
+(lav_amd/agent/debug_view.py, csrc/debug_view.hip; off by default: nothing is launched, allocated or written then).
+
+Differences, all deliberate: no wandb logging and no mp4 encoding (flush_data writes the recorded frames as .npy files); the
+two camera networks are loaded from state_dicts (`seg_model_dir`, `bra_model_dir`) instead of TorchScript traces, because the HIP
 convolution engines are built from the modules' parameters; `synthetic_weights: true` in the config replaces missing
 checkpoint files by seeded random weights (tests, benchmarks - the released checkpoints are git-LFS objects).
 """
@@ -19,8 +22,9 @@ import numpy as np
 import torch
 import yaml
 
-from . import synth
+from . import ops, synth
 from .agent import EKF, AutonomousAgent, PIDController, RoutePlanner, Track, VehicleControl, Waypointer
+from .agent import debug_view as view
 from .bev_planner import BEVPlanner
 from .frame import GAP, FramePipeline, GraphedFramePipeline
 from .lidar import LiDARModel
@@ -38,7 +42,9 @@ DEFAULT_CONFIG = dict(
     speed_KD=1.0, speed_n=40, brake_speed=0.2, brake_ratio=1.1, clip_delta=0.25, max_throttle=0.8, max_speed=35,
     speed_ratio=[0.8, 0.8, 0.8, 0.6, 0.8, 0.8], lidar_model_dir="weights/lidar_v2_7.th",
     uniplanner_dir="weights/uniplanner_v2_7.th", bra_model_dir="weights/bra_v2_9.th", seg_model_dir="weights/seg_1.th",
-    synthetic_weights=False, hip_graphs=True, points_per_tick=32768, precapture=True, log_wandb=False)
+    synthetic_weights=False, hip_graphs=True, points_per_tick=32768, precapture=True, log_wandb=False,
+    # the debug view: render every debug_view_every-th tick, write debug_view_dir/view_{first frame}.npy every debug_view_flush frames
+    debug_view=False, debug_view_dir="debug_view", debug_view_every=1, debug_view_flush=600)
 
 
 def get_entry_point():
@@ -123,7 +129,8 @@ class LAVAgent(AutonomousAgent):
 
         self.ekf = EKF(1, 1.477531, 1.393600)      # cos0 = 1 rad (sic), lf, lr (lav_agent_fast.py:141)
         self.ekf_initialized = False
-        self.vizs = []
+        self.vizs = view.ViewRecorder(self.debug_view_dir, int(self.debug_view_flush) if self.debug_view else 0)
+        self._view_frame = None
         self.num_frames = 0
         self.num_frame_keep = (self.num_frame_stack + 1) * GAP
         self.turn_controller = PIDController(K_P=self.turn_KP, K_I=self.turn_KI, K_D=self.turn_KD, n=self.turn_n)
@@ -142,9 +149,13 @@ class LAVAgent(AutonomousAgent):
         raise FileNotFoundError(f"LAVAgent: checkpoint {path!r} not found (set synthetic_weights: true for seeded random weights)")
 
     def flush_data(self):
-        self.vizs.clear()
+        """Write the recorded frames (waits for the last frame's copy) and clear the ring; nothing to do with the view off."""
+        return self.vizs.flush()
 
     def destroy(self):
+        if len(getattr(self, "vizs", ())) > 0:
+            self.flush_data()
+        self._view_frame = None
         self.waypointer = self.planner = None
         self.turn_controller = self.speed_controller = None
         self.num_frames = 0
@@ -188,9 +199,11 @@ class LAVAgent(AutonomousAgent):
         # copy is the conversion (one kernel per tensor instead of .float() + a layout copy); the eager pipeline takes floats.
         as_input = (lambda t: t) if self.hip_graphs else (lambda t: t.float())
         all_rgbs = as_input(views.permute(0, 3, 1, 2))
-        rgbs = as_input(torch.cat(list(views), dim=1)[None].permute(0, 3, 1, 2))      # (1,3,288,768)
+        rgb_hwc = torch.cat(list(views), dim=1)                                       # (288,768,3) uint8: what the debug view shows
+        rgbs = as_input(rgb_hwc[None].permute(0, 3, 1, 2))                            # (1,3,288,768)
         tel = torch.from_numpy(np.ascontiguousarray(input_data.get("TEL_RGB")[1][..., :3])).to(self.device).flip(-1)
-        tel_rgbs = as_input(tel[:-self.crop_tel_bottom][None].permute(0, 3, 1, 2))    # (1,3,192,480)
+        tel_hwc = tel[:-self.crop_tel_bottom]
+        tel_rgbs = as_input(tel_hwc[None].permute(0, 3, 1, 2))                        # (1,3,192,480)
 
         # high-level command and next route point (:280-307)
         if self.waypointer is None:
@@ -246,6 +259,13 @@ class LAVAgent(AutonomousAgent):
         if self.force_move > 0:
             throt, brake = max(0.4, throt), 0
             self.force_move -= 1
+        if self.debug_view and self.num_frames % max(int(self.debug_view_every), 1) == 0:
+            # everything but the cloud, the BEV and the images is already on the host: no new read of a model output
+            self.vizs.append(self.visualize(rgb_hwc, tel_hwc, out["lidar_points"], pred_bra, torch.sigmoid(out["pred_bev"][0]), ego_plan_locs,
+                                            other_cast_locs, other_cast_cmds, out["det"], [-wx, -wy], cmd_value, spd, steer, throt, brake),
+                             self.num_frames)
+            if self.vizs.full():
+                self.flush_data()
         return VehicleControl(steer=steer, throttle=throt, brake=brake)
 
     # ---------------------------------------------------------------------------------------------- host-side rules
@@ -283,5 +303,15 @@ class LAVAgent(AutonomousAgent):
         from .frame import ego_box_mask
         return lidar_xyzr[~ego_box_mask(lidar_xyzr)]
 
-    def visualize(self, *a, **k):
-        return None
+    def visualize(self, rgb, tel_rgb, lidar, pred_bra, pred_bev, pred_loc, cast_locs, cast_cmds, det, tgt, cmd, spd, steer, throt, brake):
+        """The reference's debug frame (:459-518) as a device tensor (H / 2, W / 2, 3) uint8: the drawing records and the text are
+        built here from host values, lav_debug_view renders from the device tensors rgb / tel_rgb (uint8 HWC), lidar and pred_bev
+        (sigmoided) on the current stream.  No synchronisation: at the end of pipeline.step the current stream has waited for every
+        side stream, and the next tick's input copies are issued on this same stream - the render is ordered after its producers
+        and before the next tick overwrites the pipeline's static buffers.  The frame tensor is reused from tick to tick; its
+        copy into the recorder's ring is ordered behind the render the same way."""
+        grid = (self.min_x, self.max_x, self.min_y, self.max_y, self.pixels_per_meter)
+        prims = view.primitives(pred_loc, cast_locs, cast_cmds, det, tgt, ppm=self.pixels_per_meter, cmd_thresh=self.cmd_thresh)
+        text = view.text_rows(cmd, spd, steer, throt, brake, pred_bra)
+        self._view_frame = ops.debug_view(rgb, tel_rgb, lidar, pred_bev, prims, text, grid=grid, out=self._view_frame)
+        return self._view_frame

@@ -306,6 +306,56 @@ def bev_stack_tile_paths(coef, shift, h: int, w: int):
     return tuple(counts)
 
 
+_view_constants: dict = {}
+
+
+def debug_view(rgb: torch.Tensor, tel_rgb: torch.Tensor, lidar: torch.Tensor, pred_bev: torch.Tensor, prims, text, *, grid,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The agent's debug frame on the device (lav_debug_view; zeroing, histogram and compose launches on the current stream): rgb
+    (h, w, 3) and tel_rgb (h', w', 3) uint8 RGB, lidar (n, >= 2) float32, pred_bev (3, x bins, width) float32 already sigmoided, all
+    in HBM; prims the records of lav_amd.agent.debug_view.primitives and text those of text_rows (host arrays, uploaded here);
+    grid = (min_x, max_x, min_y, max_y, pixels_per_meter).  Returns the (H / 2, W / 2, 3) uint8 frame (`out` when given).
+    Bit-identical to lav_amd.agent.debug_view.compose_numpy.  Wrong shapes or dtypes raise ValueError before anything is launched."""
+    from .agent import debug_view as V
+    for name, t, dtype, dim in (("rgb", rgb, torch.uint8, 3), ("tel_rgb", tel_rgb, torch.uint8, 3), ("lidar", lidar, torch.float32, 2),
+                                ("pred_bev", pred_bev, torch.float32, 3)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"debug_view: {name} must be a tensor in HBM (cuda/hip device); lav_amd.ops has no CPU path "
+                             "(lav_amd.agent.debug_view.compose_numpy is the CPU specification)")
+        if t.dtype != dtype or t.dim() != dim:
+            raise ValueError(f"debug_view: {name} must be {dim}-d {dtype}, got {t.dtype} {tuple(t.shape)}")
+    if lidar.shape[1] < 2:
+        raise ValueError(f"debug_view: lidar {tuple(lidar.shape)} has no x and y columns")
+    lay = V.layout(rgb.shape, tel_rgb.shape, grid, pred_bev.shape)
+    (x0, x1, nxb), (y0, y1, nyb) = V.grid_bins(grid)
+    prims, text = V.check_primitives(prims), V.check_text(text)
+    shape = (lay["frame_h"], lay["frame_w"], 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=rgb.device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()):
+        raise ValueError(f"debug_view: out must be a contiguous uint8 tensor of shape {shape} in HBM")
+    lib = _lib.load()
+    dev = rgb.device
+    rgb, tel_rgb, lidar, pred_bev = rgb.contiguous(), tel_rgb.contiguous(), lidar.contiguous(), pred_bev.contiguous()
+    key = (dev, tuple(rgb.shape), tuple(tel_rgb.shape), tuple(grid), lay["w_bev"])
+    const = _view_constants.get(key)
+    if const is None:      # per geometry, once: font, grey table and the six resize tables
+        if len(_view_constants) > 16:
+            _view_constants.clear()
+        const = _view_constants[key] = (torch.from_numpy(V.FONT.copy()).to(dev), torch.from_numpy(V.HIST_LUT.copy()).to(dev),
+                                        torch.from_numpy(V.resize_tables(rgb.shape, tel_rgb.shape, lay)).to(dev))
+    font, lut, tables = const
+    # text and records in one upload: [4 x TEXT_LEN bytes][records]
+    host = np.concatenate([text.reshape(-1), prims.view(np.uint8).reshape(-1)])
+    up = torch.from_numpy(host).to(dev)
+    counts = _workspace(("debug_view", nxb, nyb), nxb * nyb * 4, dev)
+    check(lib.lav_debug_view(_ptr(rgb), rgb.shape[0], rgb.shape[1], _ptr(tel_rgb), tel_rgb.shape[0], tel_rgb.shape[1], _ptr(lidar),
+                             lidar.shape[0], lidar.shape[1], _ptr(pred_bev), lay["w_bev"], up.data_ptr() + text.size, len(prims), up.data_ptr(),
+                             text.shape[1], _ptr(font), _ptr(lut), _ptr(tables), x0, x1, nxb, y0, y1, nyb, lay["w_rgb"], lay["w_tel"],
+                             _ptr(counts), _ptr(out), _stream()), "lav_debug_view")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ GRU decoders
 def gru_cast(embd, w_ih, w_hh, b_ih, b_hh, mlp_w, mlp_b, T: int):
     """embd (B, E); stacked per-command GRU/MLP weights -> (B, num_cmds, T, 2)."""
