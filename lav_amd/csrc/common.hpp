@@ -111,13 +111,6 @@ __device__ __forceinline__ float parts_absmax(const float *__restrict__ parts, i
     for (int i = i0 + lane; i < n; i += 64) m = fmaxf(m, parts[i]);
     return wave_finite_absmax(m);
 }
-// the power of two that puts a tensor's largest finite magnitude m into [16384, 32768) - fp16 overflows at 65504; exponent floored at
-// -100 (a tensor whose largest value is below 2^-100 - or subnormal - would give a subnormal scale and an infinite reciprocal)
-__device__ __forceinline__ float f16_scale_of(float m) {
-    int e = 0;
-    (void)frexpf(m, &e);                           // m = f 2^e, f in [0.5, 1): m / 2^(e - 15) in [16384, 32768)
-    return ldexpf(1.f, m > 0.f ? max(e, -100) - 15 : 0);
-}
 
 #define LAV_HIP(expr)                                                                                      \
     do {                                                                                                   \

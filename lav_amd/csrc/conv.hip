@@ -26,10 +26,10 @@
 
 #include "common.hpp"
 #include "conv_f16.hpp"
+#include "split_arith.hpp"
 
 namespace {
 using namespace lav;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int MAX_TAPS = 64;
 constexpr int MAX_CLASSES = 16;
@@ -1132,9 +1132,7 @@ __global__ __launch_bounds__(256) void k_conv_repack_f16(const float *__restrict
     if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
     __syncthreads();
     m = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-    int e = 0;
-    (void)frexpf(m, &e);
-    const float sw = ldexpf(1.f, m > 0.f ? max(e, -100) - 15 : 0), inv = 1.f / sw;
+    const float sw = f16_scale_of(m), inv = 1.f / sw;
     const long j = (long)blockIdx.x * 256 + threadIdx.x;
     if (j < npairs) {
         const int src = map16[j];

@@ -2,7 +2,7 @@
 // translation unit of their own (36 + 2 instantiations of split_body<..., F16 = true>: compile time).
 //
 // x = s (h0 + h1) with two fp16 pieces carries 22 mantissa bits and a . b ~ a0 b0 + a0 b1 + a1 b0 is THREE
-// v_mfma_f32_32x32x16_f16 per 16 k-steps instead of six bf16 ones (conv_split_kernel.hpp).  The power-of-two scale s puts the
+// v_mfma_f32_32x32x16_f16 per 16 k-steps instead of six bf16 ones (split_arith.hpp).  The power-of-two scale s puts the
 // tensor's largest finite magnitude into [16384, 32768).  Round 5 measured it with a launch of its own (k_absmax_parts) in front
 // of the head convolution; round 6 lets every convolution leave the per-workgroup maxima of what it WRITES (amax_out), so the
 // layers of a chain hand the scale on with no extra launch and no extra pass over the activations.
@@ -12,10 +12,10 @@
 
 #include "common.hpp"
 #include "conv_f16.hpp"
+#include "split_arith.hpp"
 
 namespace {
 using namespace lav;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int MAX_TAPS = 64;
 constexpr int MAX_CLASSES = 16;
 #include "conv_split_kernel.hpp"

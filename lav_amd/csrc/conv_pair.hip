@@ -29,10 +29,10 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "split_arith.hpp"
 
 namespace {
 using namespace lav;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct PairArgs {
     const float *x, *wA, *bA, *wB, *bB, *scale, *shift, *res, *zero_page;
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair(PairArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ bf16x6 variant
-// The same pair on the bf16 matrix cores with every fp32 operand split exactly into three bf16 pieces (conv_split.hpp has
+// The same pair on the bf16 matrix cores with every fp32 operand split exactly into three bf16 pieces (split_arith.hpp has
 // the arithmetic and its error analysis): six v_mfma_f32_32x32x16_bf16 per 16 channels and tap instead of eight fp32 ones
 // of twice the length - the phases of a 128-channel pair are matrix bound INSIDE the workgroup (1536 fp32 MFMAs on one CU).
 //   input   all C channels of rows y-dA, y, y+dA travel HBM -> registers -> three bf16 pieces -> LDS as
@@ -236,31 +236,6 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair(PairArgs a) {
 //           straight from L2 into registers, a ring of chunks ahead
 //   mid     relu(acc + bA) is split in registers and written to LDS in the same entry layout (a lane holds channels
 //           4h..4h+3 of four 8-channel groups of its pixel: one 8-byte store per group and piece), zero halo of dB
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void pair_split3(float x, unsigned &p0, unsigned &p1, unsigned &p2) {   // = split3 of conv_split.hpp
-    const unsigned u = __float_as_uint(x), r = u + 0x8000u;
-    p0 = ((r & 0x7f800000u) == 0x7f800000u ? u : r) & 0xffff0000u;
-    const float r1 = x - __uint_as_float(p0);
-    p1 = (__float_as_uint(r1) + 0x8000u) & 0xffff0000u;
-    const float r2 = r1 - __uint_as_float(p1);
-    p2 = __float_as_uint(r2) + 0x8000u;
-}
-__device__ __forceinline__ unsigned pair_pack(unsigned even, unsigned odd) { return __builtin_amdgcn_perm(odd, even, 0x07060302u); }
-// two values at once on v_cvt_pk_bf16_f32 (= split3_pair of conv_split.hpp: 13 instructions per pair instead of ~25)
-typedef __bf16 pair_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float pair_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void pair_split3x2(float x0, float x1, unsigned &q0, unsigned &q1, unsigned &q2) {
-    constexpr float M = 3.3895313892515355e38f;   // the largest finite bf16
-    const float c0 = __builtin_amdgcn_fmed3f(x0, -M, M), c1 = __builtin_amdgcn_fmed3f(x1, -M, M);
-    q0 = __builtin_bit_cast(unsigned, __builtin_convertvector(pair_f32x2{c0, c1}, pair_bf16x2));
-    const float r0 = x0 - __uint_as_float(q0 << 16), r1 = x1 - __uint_as_float(q0 & 0xffff0000u);
-    q1 = __builtin_bit_cast(unsigned, __builtin_convertvector(pair_f32x2{r0, r1}, pair_bf16x2));
-    const float s0 = r0 - __uint_as_float(q1 << 16), s1 = r1 - __uint_as_float(q1 & 0xffff0000u);
-    q2 = __builtin_bit_cast(unsigned, __builtin_convertvector(pair_f32x2{s0, s1}, pair_bf16x2));
-}
 
 struct PairSplitArgs {
     const float *x, *bA, *bB, *scale, *shift, *res;
@@ -333,7 +308,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_split(PairSplitArgs a)
                     for (int e = 0; e < 4; ++e) {
                         const float x0 = ok[u] ? v[u][8 * h + 2 * e] : 0.f, x1 = ok[u] ? v[u][8 * h + 2 * e + 1] : 0.f;
                         unsigned p0, p1, p2;
-                        pair_split3x2(x0, x1, p0, p1, p2);
+                        split3_pair(x0, x1, p0, p1, p2);
                         q3[0][e] = p0; q3[1][e] = p1; q3[2][e] = p2;
                     }
                     const int entry = ((c * 2 + h) * 3 + t) * W + pxs;
@@ -360,11 +335,10 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_split(PairSplitArgs a)
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    auto mma6 = [&](const u32x4 (&w)[3], const u32x4 (&b)[3]) {
-        constexpr int PA[6] = {1, 2, 0, 1, 0, 0}, PB[6] = {1, 0, 2, 0, 1, 0};
+    auto mma6 = [&](const u32x4 (&w)[3], const u32x4 (&b)[3]) {   // smallest terms first (split_arith.hpp)
 #pragma unroll
         for (int k = 0; k < 6; ++k)
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w[PA[k]]), __builtin_bit_cast(bf16x8, b[PB[k]]), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w[BF16X6_A[k]]), __builtin_bit_cast(bf16x8, b[BF16X6_B[k]]), acc, 0, 0, 0);
     };
     if (co_ok) {
         for (int j0 = 0; j0 < nch; j0 += R) {
@@ -408,7 +382,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_split(PairSplitArgs a)
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const float v0 = acc[4 * g8 + 2 * e] + bAv[4 * g8 + 2 * e], v1 = acc[4 * g8 + 2 * e + 1] + bAv[4 * g8 + 2 * e + 1];
-                pair_split3x2(v0 > 0.f ? v0 : 0.f, v1 > 0.f ? v1 : 0.f, pk[0][e], pk[1][e], pk[2][e]);
+                split3_pair(v0 > 0.f ? v0 : 0.f, v1 > 0.f ? v1 : 0.f, pk[0][e], pk[1][e], pk[2][e]);
             }
             const int grp = cg * 4 + g8;   // 8-channel group = chunk * 2 + k half
             if (grp * 8 < C) {
@@ -587,7 +561,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_chain(PairChainArgs a)
                     for (int e = 0; e < 4; ++e) {
                         const float x0 = ok[u] ? v[u][8 * h + 2 * e] : 0.f, x1 = ok[u] ? v[u][8 * h + 2 * e + 1] : 0.f;
                         unsigned p0, p1, p2;
-                        pair_split3x2(x0, x1, p0, p1, p2);
+                        split3_pair(x0, x1, p0, p1, p2);
                         q3[0][e] = p0; q3[1][e] = p1; q3[2][e] = p2;
                     }
                     const int entry = ((c * 2 + h) * 3 + t) * W + pxs;
@@ -609,11 +583,10 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_chain(PairChainArgs a)
 #pragma unroll
     for (int r = 0; r < 16; ++r) blk_in[r] = a.x0[base + (long)min(cg * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, C - 1) * plane];
 
-    auto mma6 = [&](f32x16 &acc, const u32x4 (&w)[3], const u32x4 (&b)[3]) {
-        constexpr int PA[6] = {1, 2, 0, 1, 0, 0}, PB[6] = {1, 0, 2, 0, 1, 0};
+    auto mma6 = [&](f32x16 &acc, const u32x4 (&w)[3], const u32x4 (&b)[3]) {   // smallest terms first (split_arith.hpp)
 #pragma unroll
         for (int k = 0; k < 6; ++k)
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w[PA[k]]), __builtin_bit_cast(bf16x8, b[PB[k]]), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w[BF16X6_A[k]]), __builtin_bit_cast(bf16x8, b[BF16X6_B[k]]), acc, 0, 0, 0);
     };
 
     for (int p = 0; p < a.npairs; ++p) {
@@ -723,7 +696,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_chain(PairChainArgs a)
                 for (int e = 0; e < 2; ++e) {
                     const int cch = min(cg * 32 + 8 * g8 + 4 * half + 2 * e, C - 2);
                     const float v0 = acc[4 * g8 + 2 * e] + s_epi[0][cch], v1 = acc[4 * g8 + 2 * e + 1] + s_epi[0][cch + 1];
-                    pair_split3x2(v0 > 0.f ? v0 : 0.f, v1 > 0.f ? v1 : 0.f, pk[0][e], pk[1][e], pk[2][e]);
+                    split3_pair(v0 > 0.f ? v0 : 0.f, v1 > 0.f ? v1 : 0.f, pk[0][e], pk[1][e], pk[2][e]);
                 }
                 const int grp = cg * 4 + g8;
                 if (grp * 8 < C) {
@@ -798,7 +771,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_chain(PairChainArgs a)
                 for (int g8 = 0; g8 < 4; ++g8) {
                     unsigned pk[3][2];
 #pragma unroll
-                    for (int e = 0; e < 2; ++e) pair_split3x2(vout[4 * g8 + 2 * e], vout[4 * g8 + 2 * e + 1], pk[0][e], pk[1][e], pk[2][e]);
+                    for (int e = 0; e < 2; ++e) split3_pair(vout[4 * g8 + 2 * e], vout[4 * g8 + 2 * e + 1], pk[0][e], pk[1][e], pk[2][e]);
                     const int grp = cg * 4 + g8;
                     if (grp * 8 < C) {
                         const int entry = (grp * 3 + 1) * W + px;   // (chunk * 2 + k half) = grp, row slot t = 1
@@ -855,16 +828,6 @@ struct PairChainF16Args {
     int rm_stride;
     int dbmax;
 };
-typedef _Float16 pair_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 pair_f16x8 __attribute__((ext_vector_type(8)));
-// two values -> two fp16 pieces each (= split2h_pair of conv_split_kernel.hpp): u = h0 + h1 + O(2^-22 |u|), |u| <= 32768 by the caller's scale
-__device__ __forceinline__ void pair_split2h(float u0, float u1, unsigned &q0, unsigned &q1) {
-    const pair_f16x2 h0 = __builtin_convertvector(pair_f32x2{u0, u1}, pair_f16x2);
-    const pair_f32x2 f0 = __builtin_convertvector(h0, pair_f32x2);
-    const pair_f16x2 h1 = __builtin_convertvector(pair_f32x2{u0 - f0[0], u1 - f0[1]}, pair_f16x2);
-    q0 = __builtin_bit_cast(unsigned, h0);
-    q1 = __builtin_bit_cast(unsigned, h1);
-}
 
 // TRACE (LAV_PAIR_CHAIN_TRACE): as in the bf16 run - thread 0 of every workgroup accumulates the shader-clock cycles of each phase into a.trace[workgroup][8]:
 // 0 whole run, 1 hand-off waits, 2 neighbour rows + own row (loads, conversion, LDS), 3 barrier, 4 phase A, 5 combine + intermediate row, 6 phase B,
@@ -960,7 +923,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_chain_f16(PairChainF16
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         unsigned p0, p1;
-                        pair_split2h(v[u][8 * h + 2 * e] * inv, v[u][8 * h + 2 * e + 1] * inv, p0, p1);
+                        split2h_pair(v[u][8 * h + 2 * e] * inv, v[u][8 * h + 2 * e + 1] * inv, p0, p1);
                         q2[0][e] = p0; q2[1][e] = p1;
                     }
                     const int entry = ((c * 2 + h) * 3 + t) * W + pxs;
@@ -1001,11 +964,10 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_chain_f16(PairChainF16
         stage_store(std::true_type{}, 1.f / f16_scale_of(m3));
     }
 
-    auto mma3 = [&](f32x16 &acc, const u32x4 (&w)[2], const u32x4 (&b)[2]) {
-        constexpr int HA[3] = {1, 0, 0}, HB[3] = {0, 1, 0};   // smallest terms first: w1 b0, w0 b1, w0 b0
+    auto mma3 = [&](f32x16 &acc, const u32x4 (&w)[2], const u32x4 (&b)[2]) {   // smallest terms first: w1 b0, w0 b1, w0 b0 (split_arith.hpp)
 #pragma unroll
         for (int k = 0; k < 3; ++k)
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(pair_f16x8, w[HA[k]]), __builtin_bit_cast(pair_f16x8, b[HB[k]]), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, w[F16X3_A[k]]), __builtin_bit_cast(f16x8, b[F16X3_B[k]]), acc, 0, 0, 0);
     };
     float m_own = 0.f;   // (wave 0) largest finite magnitude of this row's last output
 
@@ -1077,7 +1039,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_chain_f16(PairChainF16
                 for (int g8 = 0; g8 < 4; ++g8) {
                     unsigned pk[2][2];
 #pragma unroll
-                    for (int e = 0; e < 2; ++e) pair_split2h(own[4 * g8 + 2 * e] * inv, own[4 * g8 + 2 * e + 1] * inv, pk[0][e], pk[1][e]);
+                    for (int e = 0; e < 2; ++e) split2h_pair(own[4 * g8 + 2 * e] * inv, own[4 * g8 + 2 * e + 1] * inv, pk[0][e], pk[1][e]);
                     const int grp = cg * 4 + g8;
                     if (grp * 8 < C) {
                         const int entry = (grp * 3 + 1) * W + px;   // (chunk * 2 + k half) = grp, row slot t = 1
@@ -1140,7 +1102,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_chain_f16(PairChainF16
                 for (int e = 0; e < 2; ++e) {
                     const int cch = min(cg * 32 + 8 * g8 + 4 * half + 2 * e, C - 2);
                     const float v0 = fmaf(acc[4 * g8 + 2 * e], fA, s_epi[0][cch]), v1 = fmaf(acc[4 * g8 + 2 * e + 1], fA, s_epi[0][cch + 1]);
-                    pair_split2h((v0 > 0.f ? v0 : 0.f) * inv_mid, (v1 > 0.f ? v1 : 0.f) * inv_mid, pk[0][e], pk[1][e]);
+                    split2h_pair((v0 > 0.f ? v0 : 0.f) * inv_mid, (v1 > 0.f ? v1 : 0.f) * inv_mid, pk[0][e], pk[1][e]);
                 }
                 const int grp = cg * 4 + g8;
                 if (grp * 8 < C) {
@@ -1284,16 +1246,6 @@ extern "C" int lav_conv1d_pair_pack_weights(int channels, const float *h_weight,
                     }
     // split packing: [tap][chunk][cout block][piece][lane = khalf*32 + cout%32][8 channels] bf16
     unsigned short *o = reinterpret_cast<unsigned short *>(h_packed + pair_f32_floats(C));
-    auto bf = [](float x, float &rest) {
-        unsigned u;
-        memcpy(&u, &x, 4);
-        const unsigned r = u + 0x8000u;
-        u = ((r & 0x7f800000u) == 0x7f800000u ? u : r) & 0xffff0000u;
-        float b;
-        memcpy(&b, &u, 4);
-        rest = x - b;
-        return (unsigned short)(u >> 16);
-    };
     for (int t = 0; t < 3; ++t)
         for (int ch = 0; ch < nchunk; ++ch)
             for (int blk = 0; blk < CP / 32; ++blk)
@@ -1302,7 +1254,7 @@ extern "C" int lav_conv1d_pair_pack_weights(int channels, const float *h_weight,
                         const int co = blk * 32 + (lane & 31), ci = ch * 16 + 8 * (lane >> 5) + e;
                         const float w = co < C ? h_weight[((size_t)co * C + ci) * 3 + t] : 0.f;
                         float r1, r2, r3;
-                        const unsigned short p0 = bf(w, r1), p1 = bf(r1, r2), p2 = bf(r2, r3);
+                        const unsigned short p0 = bf16_round(w, r1), p1 = bf16_round(r1, r2), p2 = bf16_round(r2, r3);
                         const size_t frag = ((((size_t)t * nchunk + ch) * (CP / 32) + blk) * 3) * 512;
                         o[frag + lane * 8 + e] = p0; o[frag + 512 + lane * 8 + e] = p1; o[frag + 1024 + lane * 8 + e] = p2;
                     }
@@ -1317,9 +1269,7 @@ extern "C" int lav_conv1d_pair_pack_weights(int channels, const float *h_weight,
             for (int k = 0; k < C * 3; ++k) { const float v = fabsf(h_weight[(size_t)co * C * 3 + k]); if (v <= 3.4028235e38f) acc += v; }
             l1 = std::max(l1, (float)(acc * (1.0 + 1e-6)));
         }
-        int ex = 0;
-        (void)frexpf(m, &ex);
-        const float sw = ldexpf(1.f, m > 0.f ? std::max(ex, -100) - 15 : 0), inv = 1.f / sw;
+        const float sw = f16_scale_of(m), inv = 1.f / sw;
         _Float16 *h = reinterpret_cast<_Float16 *>(h_packed + pair_f32_floats(C) + pair_split_bytes(C) / 4);
         for (int t = 0; t < 3; ++t)
             for (int ch = 0; ch < nchunk; ++ch)

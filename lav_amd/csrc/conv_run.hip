@@ -26,14 +26,10 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "split_arith.hpp"
 
 namespace {
 using namespace lav;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 run_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 run_f16x8 __attribute__((ext_vector_type(8)));
-typedef float run_f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int RUN_MAX = 8;            // layers per run
 constexpr int RUN_MAX_WG = 256;       // workgroups per run: all resident at once, one per CU
@@ -54,15 +50,6 @@ struct RunArgs {
     long long spin_limit;
     int amax_in_count, C, H, W, L, NS, data_bytes;
 };
-
-// two values -> two fp16 pieces each (= split2h_pair of conv_split_kernel.hpp)
-__device__ __forceinline__ void run_split2h(float u0, float u1, unsigned &q0, unsigned &q1) {
-    const run_f16x2 h0 = __builtin_convertvector(run_f32x2{u0, u1}, run_f16x2);
-    const run_f32x2 f0 = __builtin_convertvector(h0, run_f32x2);
-    const run_f16x2 h1 = __builtin_convertvector(run_f32x2{u0 - f0[0], u1 - f0[1]}, run_f16x2);
-    q0 = __builtin_bit_cast(unsigned, h0);
-    q1 = __builtin_bit_cast(unsigned, h1);
-}
 
 template <int NPB, int NCBW, int KS, int NTK>
 __global__ __launch_bounds__(512) void k_conv3x3_run_f16(RunArgs a) {
@@ -182,7 +169,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_run_f16(RunArgs a) {
                         for (int e = 0; e < 4; ++e) {
                             unsigned p0, p1;
                             const float x0 = okr[u] ? v[u][8 * h + 2 * e] : 0.f, x1 = okr[u] ? v[u][8 * h + 2 * e + 1] : 0.f;
-                            run_split2h(x0 * inv, x1 * inv, p0, p1);
+                            split2h_pair(x0 * inv, x1 * inv, p0, p1);
                             q2[0][e] = p0; q2[1][e] = p1;
                         }
                         const int entry = ((c * 2 + h) * 3 + t) * WP + px + 1;
@@ -193,15 +180,9 @@ __global__ __launch_bounds__(512) void k_conv3x3_run_f16(RunArgs a) {
             }
         }
         __syncthreads();
-        // the epilogue's two powers of two: the halves of sx * sw's exponent (as split_body: neither product over- or underflows before y does)
+        // the epilogue's two powers of two: the halves of sx * sw's exponent (neither product over- or underflows before y does)
         float out_sx, out_sw;
-        {
-            int ex = 0, ew = 0;
-            (void)frexpf(sx, &ex);
-            (void)frexpf(*a.wscale[l], &ew);
-            const int et = ex + ew - 2;
-            out_sx = ldexpf(1.f, et >> 1); out_sw = ldexpf(1.f, et - (et >> 1));
-        }
+        f16_out_scales(sx, *a.wscale[l], out_sx, out_sw);
 
         // ---- matrix phase
         f32x16 acc[NPB];
@@ -218,7 +199,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_run_f16(RunArgs a) {
             for (int t = 0; t < 9; ++t) {
                 const int toff = ((t / 3) * WP + (t % 3)) * 16;
                 // pixel blocks in groups of three: fragments of one group in registers at a time; within a group the three products go
-                // round the accumulators (smallest terms first: w1 b0, w0 b1, w0 b0)
+                // round the accumulators (split_arith.hpp's F16X3_A / _B order, smallest terms first: w1 b0, w0 b1, w0 b0)
 #pragma unroll
                 for (int g0 = 0; g0 < NPB; g0 += 3) {
                     constexpr int GMAX = 3;
@@ -232,15 +213,15 @@ __global__ __launch_bounds__(512) void k_conv3x3_run_f16(RunArgs a) {
 #pragma unroll
                     for (int j = 0; j < GMAX; ++j)
                         if (g0 + j < NPB)
-                            acc[g0 + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(run_f16x8, wr[t][1]), __builtin_bit_cast(run_f16x8, b[j][0]), acc[g0 + j], 0, 0, 0);
+                            acc[g0 + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wr[t][1]), __builtin_bit_cast(f16x8, b[j][0]), acc[g0 + j], 0, 0, 0);
 #pragma unroll
                     for (int j = 0; j < GMAX; ++j)
                         if (g0 + j < NPB)
-                            acc[g0 + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(run_f16x8, wr[t][0]), __builtin_bit_cast(run_f16x8, b[j][1]), acc[g0 + j], 0, 0, 0);
+                            acc[g0 + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wr[t][0]), __builtin_bit_cast(f16x8, b[j][1]), acc[g0 + j], 0, 0, 0);
 #pragma unroll
                     for (int j = 0; j < GMAX; ++j)
                         if (g0 + j < NPB)
-                            acc[g0 + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(run_f16x8, wr[t][0]), __builtin_bit_cast(run_f16x8, b[j][0]), acc[g0 + j], 0, 0, 0);
+                            acc[g0 + j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wr[t][0]), __builtin_bit_cast(f16x8, b[j][0]), acc[g0 + j], 0, 0, 0);
                 }
                 // the slot's next tenant: the next chunk's tap, or the next layer's first chunk (in flight across the hand-off)
                 load_w(w_refill, t, wr[t]);

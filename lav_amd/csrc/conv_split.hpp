@@ -1,12 +1,8 @@
 // fp32 convolution on the bf16 matrix cores by operand splitting - included by conv.hip (inside its namespace).
 //
-// v_mfma_f32_32x32x2_f32 runs at the fp32 VECTOR rate (157 TFLOP/s, 1/16 of the bf16 matrix rate).  Every fp32 value is
-// the exact sum of three bf16 pieces, x = x0 + x1 + x2 (8 + 8 + 8 significant bits; x1 = bf16(x - x0), ...), so
-//     a*b = a0b0 + (a0b1 + a1b0) + (a0b2 + a2b0 + a1b1) + O(2^-24 |ab|)
-// is six v_mfma_f32_32x32x16_bf16 (products exact, fp32 accumulate) per 16 k-steps instead of eight fp32 MFMAs of 64
-// cycles: 192 instead of 512 matrix-pipe cycles, with the error of an fp32 dot product (tools/probes/split_mfma_probe.hip
-// on MI355X, K = 1152, 2^12 dynamic range: max |err| / sum|ab| 3.1e-7 against 6.3e-7 for the fp32 MFMA chain).  fp32
-// range is kept (bf16 has the fp32 exponent); fp32 SUBNORMAL inputs are flushed by the bf16 matrix pipe.
+// Every fp32 operand is the exact sum of three bf16 pieces and the six leading partial products run on v_mfma_f32_32x32x16_bf16 with
+// fp32 accumulation: 192 instead of 512 matrix-pipe cycles per 16 k-steps, with the error of an fp32 dot product.  split_arith.hpp
+// has the arithmetic, its error analysis and what happens to non-finite and subnormal values.
 //
 // Kernel structure (one workgroup = 8 waves):
 //   waves 0-3  compute: MP x MC tiles of 32 pixels x 32 couts each (wave grid WPX x 4/WPX), operands from LDS with one
@@ -127,9 +123,7 @@ inline void split_pack_weights_f16(const lav_conv &c, const Plan &p, const float
     const size_t nw = (size_t)c.cout * c.cin * c.kh * c.kw;
     float m = 0.f;
     for (size_t i = 0; i < nw; ++i) { const float v = fabsf(h_weight[i]); if (v <= 3.4028235e38f && v > m) m = v; }
-    int e = 0;
-    (void)frexpf(m, &e);
-    const float sw = ldexpf(1.f, m > 0.f ? std::max(e, -100) - 15 : 0), inv = 1.f / sw;   // (floor: as the activations' scale in split_body)
+    const float sw = f16_scale_of(m), inv = 1.f / sw;   // (the activations' rule in split_body)
     _Float16 *o = reinterpret_cast<_Float16 *>(out);
     size_t cls_off = 0;   // in halves
     for (int cls = 0; cls < p.nclasses; ++cls) {
@@ -154,17 +148,6 @@ inline void split_pack_weights_f16(const lav_conv &c, const Plan &p, const float
     }
     const float tail[4] = {sw, 0.f, 0.f, 0.f};   // (the scale and its 12 bytes of padding: the whole buffer is defined - device re-packs compare equal)
     memcpy(out + split_weight_bytes_f16(p), tail, sizeof(tail));
-}
-
-inline unsigned short bf16_round(float x, float &rest) {
-    unsigned u;
-    memcpy(&u, &x, 4);
-    const unsigned r = u + 0x8000u;
-    u = ((r & 0x7f800000u) == 0x7f800000u ? u : r) & 0xffff0000u;   // as split3: no round-up into the Inf exponent
-    float b;
-    memcpy(&b, &u, 4);
-    rest = x - b;
-    return (unsigned short)(u >> 16);
 }
 
 // [class][cout block][tap][chunk][piece][lane = khalf*32 + cout%32][8 channels] bf16

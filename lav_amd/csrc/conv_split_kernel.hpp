@@ -1,9 +1,7 @@
-// Device side of the split-operand convolution kernels (conv_split.hpp has the description and the host side): operand splitting,
-// the warp-specialised workgroup body split_body<>.  Included - inside the including file's namespace - by conv.hip (bf16x6 kernels)
-// and by conv_f16.hip (the LAV_CONV_F16X3 kernels, a translation unit of their own since round 6: compile time).  Expects
-// MAX_CLASSES, MAX_TAPS and f32x16 from the including file.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// Device side of the split-operand convolution kernels (conv_split.hpp has the kernel structure and the host side, split_arith.hpp the
+// arithmetic): the warp-specialised workgroup body split_body<>.  Included - inside the including file's namespace - by conv.hip
+// (bf16x6 kernels) and by conv_f16.hip (the LAV_CONV_F16X3 kernels, a translation unit of their own since round 6: compile time).
+// Expects MAX_CLASSES and MAX_TAPS from the including file, which has included split_arith.hpp at file scope.
 
 constexpr int SPLIT_NT = 8;          // most staged positions per activation-loader thread (128 threads): plane <= 1024
 constexpr int SPLIT_NT_TP = 12;      // tap-pair mode (8-channel chunks: half the registers per position): plane <= 1536
@@ -45,51 +43,6 @@ __device__ __forceinline__ void dma_barrier() { asm volatile("s_waitcnt vmcnt(0)
 
 // barrier that adds the cycles spent in it to `acc` (trace builds of the loop only)
 #define SPLIT_TIMED(barrier_call, acc) do { if (a.trace) { const long long t_ = clock64(); barrier_call; acc += clock64() - t_; } else { barrier_call; } } while (0)
-
-// x -> three bf16 pieces (round half up on the dropped bits), returned in the HIGH halves of p0..p2.  Where the round-up would
-// carry into the Inf / NaN exponent (|x| within half a bf16 ulp of FLT_MAX) the first piece is truncated instead: the pieces still
-// sum to x exactly.  Non-finite x: the first piece keeps Inf / NaN and the rest become NaN (Inf - Inf), so the output is NaN where
-// the fp32 kernels (and the reference) propagate Inf - documented in lav_amd.h.  fp32 subnormals are flushed by the hardware.
-__device__ __forceinline__ void split3(float x, unsigned &p0, unsigned &p1, unsigned &p2) {
-    const unsigned u = __float_as_uint(x), r = u + 0x8000u;
-    p0 = ((r & 0x7f800000u) == 0x7f800000u ? u : r) & 0xffff0000u;
-    const float r1 = x - __uint_as_float(p0);          // exact
-    p1 = (__float_as_uint(r1) + 0x8000u) & 0xffff0000u;
-    const float r2 = r1 - __uint_as_float(p1);         // exact
-    p2 = __float_as_uint(r2) + 0x8000u;                // low half is dropped by the pack
-}
-// Two values at once on the conversion unit (round 4): v_cvt_pk_bf16_f32 rounds both to bf16 (nearest even) and packs them, so a
-// pair costs 13 instructions instead of ~25 - the activation loaders' conversion of a chunk sat in the critical path of its
-// barrier interval (in-kernel trace of the BEV layers: 2.4 k cycles per chunk).  q0..q2 = the three pieces of (x0, x1), x0 in the
-// low half.  Exactness as split3: x - bf16(x) and the second remainder are exact, the third piece has at most 8 significant bits
-// left.  The first piece of |x| > the largest finite bf16 is that bound (the remainder carries the rest): no finite input
-// overflows; Inf / NaN end in NaN outputs as documented in lav_amd.h.
-typedef __bf16 split_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float split_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split3_pair(float x0, float x1, unsigned &q0, unsigned &q1, unsigned &q2) {
-    constexpr float M = 3.3895313892515355e38f;   // 0x7f7f0000
-    const float c0 = __builtin_amdgcn_fmed3f(x0, -M, M), c1 = __builtin_amdgcn_fmed3f(x1, -M, M);
-    q0 = __builtin_bit_cast(unsigned, __builtin_convertvector(split_f32x2{c0, c1}, split_bf16x2));
-    const float r0 = x0 - __uint_as_float(q0 << 16), r1 = x1 - __uint_as_float(q0 & 0xffff0000u);
-    q1 = __builtin_bit_cast(unsigned, __builtin_convertvector(split_f32x2{r0, r1}, split_bf16x2));
-    const float s0 = r0 - __uint_as_float(q1 << 16), s1 = r1 - __uint_as_float(q1 & 0xffff0000u);
-    q2 = __builtin_bit_cast(unsigned, __builtin_convertvector(split_f32x2{s0, s1}, split_bf16x2));
-}
-// Round 5, LAV_CONV_F16X3: two values -> two fp16 pieces each, u = h0 + h1 + O(2^-22 |u|) (round to nearest; |u| <= 32768 by the caller's
-// power-of-two scale, so nothing overflows; what is below fp16's subnormal quantum 2^-24 - 2^-39 of the tensor's largest value - is lost).
-// With a . b ~ a0 b0 + a0 b1 + a1 b0 that is THREE v_mfma_f32_32x32x16_f16 per 16 k-steps instead of six bf16 ones, at 22 instead of
-// 24 bits per operand: the error of the dot product stays at the level of its fp32 accumulation (tests/test_gpu_conv.py).
-typedef _Float16 split_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void split2h_pair(float u0, float u1, unsigned &q0, unsigned &q1) {
-    const split_f16x2 h0 = __builtin_convertvector(split_f32x2{u0, u1}, split_f16x2);
-    const split_f32x2 f0 = __builtin_convertvector(h0, split_f32x2);
-    const split_f16x2 h1 = __builtin_convertvector(split_f32x2{u0 - f0[0], u1 - f0[1]}, split_f16x2);
-    q0 = __builtin_bit_cast(unsigned, h0);
-    q1 = __builtin_bit_cast(unsigned, h1);
-}
-// {hi half of odd, hi half of even} -> one dword of two bf16 (even in the low half)
-__device__ __forceinline__ unsigned pack_hi(unsigned even, unsigned odd) { return __builtin_amdgcn_perm(odd, even, 0x07060302u); }
 
 // scheduling hint: K-th of NR groups "some MFMAs, then one LDS read"
 template <int K, int NM, int NR>
@@ -145,21 +98,17 @@ __device__ __forceinline__ void split_body(const SplitArgs &a, unsigned char *sm
     if (F16 && (wid < 4 || wid >= 6)) {   // (the weight waves need no scale)
         float m = parts_absmax(a.f16_parts, a.f16_nparts, lane);
         m = fmaxf(m, finite_abs(a.pad_value));   // (out-of-image positions hold pad_value: it must fit the scale too)
+        // f16_scale_of(m) and f16_out_scales(sx, *a.f16_wscale, out_sx, out_sw) of split_arith.hpp, WRITTEN OUT: with either call in
+        // place of its text hipcc allocates this body's registers differently in all 14 k_conv_split_f16 kernels (same arithmetic,
+        // other code), and these kernels are to stay instruction for instruction what they were.  Change the rule there AND here.
         int e = 0;
-        (void)frexpf(m, &e);                       // m = f 2^e, f in [0.5, 1): m / 2^(e - 15) in [16384, 32768)
-        // (exponent floored at -100: a tensor whose largest value is below 2^-100 - or subnormal - would give a subnormal scale and an
-        //  infinite reciprocal.  With the floor such a tensor is divided by 2^-115: its values, fp32 subnormals included, are kept
-        //  down to 2^-140.)
+        (void)frexpf(m, &e);
         const float sx = ldexpf(1.f, m > 0.f ? max(e, -100) - 15 : 0);
         inv_sx = 1.f / sx;                         // (a power of two: exact)
-        // The epilogue multiplies by two powers of two one after the other: sx * sw alone can overflow (2^113 * 2^113), and so can
-        // acc * sx when the weights are small (activations near FLT_MAX: acc ~ 2^32, sx = 2^113).  Both factors are therefore the
-        // halves of sx * sw's exponent: acc * out_sx lies between acc and y, so it over- or underflows only where y does, and y is
-        // rounded once, as with any other split of the exponent.
         int ex = 0, ew = 0;
         (void)frexpf(sx, &ex);
         (void)frexpf(*a.f16_wscale, &ew);
-        const int et = ex + ew - 2;                // sx * sw = 2^et (both are powers of two in [2^-115, 2^113])
+        const int et = ex + ew - 2;
         out_sx = ldexpf(1.f, et >> 1); out_sw = ldexpf(1.f, et - (et >> 1));
     }
     const int ntaps_real = a.cls_ntaps[cls];
@@ -411,9 +360,7 @@ __device__ __forceinline__ void split_body(const SplitArgs &a, unsigned char *sm
             for (int pl = 0; pl < NPC; ++pl) o.b[mp][pl] = *reinterpret_cast<const u32x4 *>(bin + pl * pstride + base[mp] + to * 16);
     };
     auto mma = [&](const SplitOps<MP, MC, NPC> &o) {
-        // smallest terms first; consecutive instructions go to different accumulators
-        constexpr int PA[6] = {1, 2, 0, 1, 0, 0}, PB[6] = {1, 0, 2, 0, 1, 0};
-        constexpr int HA[3] = {1, 0, 0}, HB[3] = {0, 1, 0};   // fp16 pieces: a1 b0, a0 b1, a0 b0
+        // smallest terms first (split_arith.hpp); consecutive instructions go to different accumulators
 #pragma unroll
         for (int k = 0; k < NPROD; ++k)
 #pragma unroll
@@ -421,10 +368,10 @@ __device__ __forceinline__ void split_body(const SplitArgs &a, unsigned char *sm
 #pragma unroll
                 for (int mp = 0; mp < MP; ++mp) {
                     if constexpr (F16)
-                        acc[mc][mp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, o.a[mc][HA[k]]), __builtin_bit_cast(f16x8, o.b[mp][HB[k]]),
+                        acc[mc][mp] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, o.a[mc][F16X3_A[k]]), __builtin_bit_cast(f16x8, o.b[mp][F16X3_B[k]]),
                                                                              acc[mc][mp], 0, 0, 0);
                     else
-                        acc[mc][mp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, o.a[mc][PA[k]]), __builtin_bit_cast(bf16x8, o.b[mp][PB[k]]),
+                        acc[mc][mp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, o.a[mc][BF16X6_A[k]]), __builtin_bit_cast(bf16x8, o.b[mp][BF16X6_B[k]]),
                                                                               acc[mc][mp], 0, 0, 0);
                 }
     };

@@ -9,7 +9,7 @@
 //     dW[co][ci][ky][kx] = sum over (n, y, x) of dY[n][co][y][x] * X[n][ci][y + ky - 1][x + kx - 1]          (zero padding)
 //
 // A GEMM per tap with K = pixels.  fp32 operands are split exactly into three bf16 pieces each and the six leading partial products
-// run on v_mfma_f32_32x32x16_bf16 with fp32 accumulation ("bf16x6", conv_split.hpp: not less accurate than an fp32 fmaf chain).
+// run on v_mfma_f32_32x32x16_bf16 with fp32 accumulation ("bf16x6", split_arith.hpp: not less accurate than an fp32 fmaf chain).
 //
 //   workgroup   8 waves.  Waves 0-3 own the accumulators of a 64 co x 64 ci tile for all nine taps (wave = (co half, ci half): 9 x 16
 //               registers) and do nothing but ds_read_b128 + matrix instructions; waves 4-7 load, split and stage.
@@ -36,15 +36,10 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "split_arith.hpp"
 
 namespace {
 using namespace lav;
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wg_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float wg_f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int T_CO = 64, T_CI = 64, PX = 16;            // tile of the weight gradient, pixels per step
 constexpr int ENTRY = 16;                               // bytes of one lane operand (8 bf16 / fp16)
@@ -67,43 +62,15 @@ struct WgradArgs {
     int n_amax_x, n_amax_dy;
 };
 
-// x = q0 + q1 + q2 exactly (three bf16 pieces of two values at once; conv_split.hpp: split3_pair)
-__device__ __forceinline__ void split3x2(float x0, float x1, unsigned &q0, unsigned &q1, unsigned &q2) {
-    constexpr float M = 3.3895313892515355e38f;   // 0x7f7f0000: the first piece never rounds into the Inf exponent
-    const float c0 = __builtin_amdgcn_fmed3f(x0, -M, M), c1 = __builtin_amdgcn_fmed3f(x1, -M, M);
-    q0 = __builtin_bit_cast(unsigned, __builtin_convertvector(wg_f32x2{c0, c1}, wg_bf16x2));
-    const float r0 = x0 - __uint_as_float(q0 << 16), r1 = x1 - __uint_as_float(q0 & 0xffff0000u);
-    q1 = __builtin_bit_cast(unsigned, __builtin_convertvector(wg_f32x2{r0, r1}, wg_bf16x2));
-    const float s0 = r0 - __uint_as_float(q1 << 16), s1 = r1 - __uint_as_float(q1 & 0xffff0000u);
-    q2 = __builtin_bit_cast(unsigned, __builtin_convertvector(wg_f32x2{s0, s1}, wg_bf16x2));
-}
-
-typedef _Float16 wg_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-// the pieces of two values (x0 in the low half): three bf16 pieces of x exactly, or two fp16 pieces of x * inv (conv_split_kernel.hpp: split2h_pair)
-template <bool F16>
-__device__ __forceinline__ void split_pair(float x0, float x1, float inv, unsigned (&q)[F16 ? 2 : 3]) {
-    if constexpr (F16) {
-        const float u0 = x0 * inv, u1 = x1 * inv;
-        const wg_f16x2 h0 = __builtin_convertvector(wg_f32x2{u0, u1}, wg_f16x2);
-        const wg_f32x2 f0 = __builtin_convertvector(h0, wg_f32x2);
-        const wg_f16x2 h1 = __builtin_convertvector(wg_f32x2{u0 - f0[0], u1 - f0[1]}, wg_f16x2);
-        q[0] = __builtin_bit_cast(unsigned, h0);
-        q[1] = __builtin_bit_cast(unsigned, h1);
-    } else {
-        split3x2(x0, x1, q[0], q[1], q[2]);
-    }
-}
 // acc += A . B over the operands' pieces: the six leading products of three bf16 pieces, or the three of two fp16 pieces
 template <bool F16>
 __device__ __forceinline__ void mma_pieces(f32x16 &acc, const u32x4 (&av)[F16 ? 2 : 3], const u32x4 (&bv)[F16 ? 2 : 3]) {
     if constexpr (F16) {
-        constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};
 #pragma unroll
         for (int k = 0; k < 3; ++k)
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, av[PA[k]]), __builtin_bit_cast(f16x8, bv[PB[k]]), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, av[F16X3_A[k]]), __builtin_bit_cast(f16x8, bv[F16X3_B[k]]), acc, 0, 0, 0);
     } else {
-        constexpr int PA[6] = {0, 0, 1, 0, 1, 2}, PB[6] = {0, 1, 0, 2, 1, 0};
+        constexpr int PA[6] = {0, 0, 1, 0, 1, 2}, PB[6] = {0, 1, 0, 2, 1, 0};   // LARGEST first, unlike split_arith.hpp's BF16X6_A / _B: changing it would change dW
 #pragma unroll
         for (int k = 0; k < 6; ++k)
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av[PA[k]]), __builtin_bit_cast(bf16x8, bv[PB[k]]), acc, 0, 0, 0);

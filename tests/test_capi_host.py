@@ -523,6 +523,111 @@ def test_f16x3_plan_and_packing():
     assert np.array_equal(w.reshape(-1)[m16].astype(np.float64), ref)
 
 
+def _split_rule_tensors(shape):
+    """The five weight tensors of test_pair_packing_sections_are_the_split_rule."""
+    rng = np.random.default_rng(23)
+    wide = (rng.standard_normal(shape) * np.exp2(rng.uniform(-30, 10, shape))).astype(np.float32)
+    zeros = np.zeros(shape, np.float32)
+    tiny = (rng.uniform(-1, 1, shape) * 2.0 ** -121).astype(np.float32)
+    tiny.reshape(-1)[5] = 2.0 ** -120                                  # the largest magnitude: below the floor at 2^-100
+    huge = rng.standard_normal(shape).astype(np.float32)
+    huge.reshape(-1)[7] = np.array([0x7f7fffff], np.uint32).view(np.float32)[0]
+    inf = rng.standard_normal(shape).astype(np.float32)
+    inf.reshape(-1)[3] = np.inf
+    return {"wide": wide, "zeros": zeros, "tiny": tiny, "huge": huge, "inf": inf}
+
+
+def _f16_scale(w):
+    """split_arith.hpp's f16_scale_of on the largest finite |w|: the power of two that puts it into [16384, 32768), exponent floored at -100."""
+    a = np.abs(w[np.isfinite(w)])
+    m = np.float32(a.max()) if a.size else np.float32(0)
+    return np.float32(2.0 ** (max(int(np.frexp(m)[1]), -100) - 15)) if m > 0 else np.float32(1)
+
+
+def _bf16_pieces(w):
+    """three bf16 pieces (uint16) per float32: add 0x8000, truncate instead where that reaches the Inf exponent, remainder in float32"""
+    out, x = [], w.astype(np.float32)
+    for _ in range(3):
+        u = x.view(np.uint32)
+        r = u + np.uint32(0x8000)
+        p = np.where((r & np.uint32(0x7f800000)) == np.uint32(0x7f800000), u, r) & np.uint32(0xffff0000)
+        out.append((p >> np.uint32(16)).astype(np.uint16))
+        x = x - p.view(np.float32)
+    return out
+
+
+def _f16_pieces(w, sw):
+    """two fp16 pieces (bits) of float32(w * 1 / s_w)"""
+    v = w.astype(np.float32) * (np.float32(1) / sw)
+    h0 = v.astype(np.float16)
+    h1 = (v - h0.astype(np.float32)).astype(np.float16)
+    return h0.view(np.uint16), h1.view(np.uint16)
+
+
+def test_pair_packing_sections_are_the_split_rule():
+    """lav_conv1d_pair_pack_weights, every section bit for bit against the split rule restated in NumPy (split_arith.hpp: bf16_round,
+    f16_scale_of, two fp16 pieces of w / s_w): the fp32 section, three bf16 pieces, two fp16 pieces, the tail {s_w, largest L1 norm of a
+    filter x (1 + 1e-6) accumulated in float64, 0, 0}, zeros in the padded couts - C = 16 and C = 48 (CP = 64, three chunks) on a wide
+    exponent spread, all zeros (s_w = 1), a largest magnitude of 2^-120 (the floor: s_w = 2^-115), a weight at 0x7f7fffff (first bf16
+    piece truncated) and a +Inf weight (ignored by the maximum and the L1 norm).  The same tensors through lav_conv_pack_weights in
+    LAV_CONV_F16X3 (16 -> 32 channels, 3x3): fp16 section and scale word exactly."""
+    lib = _lib.load()
+    with np.errstate(all="ignore"):
+        for Cn in (16, 48):
+            CP, nchunk = (Cn + 31) // 32 * 32, Cn // 16
+            nf32, nbf, nh = 3 * nchunk * 2 * CP * 8, 3 * nchunk * (CP // 32) * 3 * 512, 3 * nchunk * (CP // 32) * 2 * 512   # floats, u16, u16
+            total = lib.lav_conv1d_pair_packed_weight_floats(Cn)
+            assert total == nf32 + nbf // 2 + nh // 2 + 4
+            t, ch, half, co, cp = np.meshgrid(np.arange(3), np.arange(nchunk), np.arange(2), np.arange(CP), np.arange(8), indexing="ij")
+            t2, ch2, blk, lane, el = np.meshgrid(np.arange(3), np.arange(nchunk), np.arange(CP // 32), np.arange(64), np.arange(8), indexing="ij")
+            co2, ci2 = blk * 32 + (lane & 31), ch2 * 16 + 8 * (lane >> 5) + el
+            for name, w in _split_rule_tensors((Cn, Cn, 3)).items():
+                packed = np.full(total, np.nan, np.float32)
+                assert lib.lav_conv1d_pair_pack_weights(Cn, w.ctypes.data, packed.ctypes.data) == 0
+                wp = np.zeros((CP, Cn, 3), np.float32)          # zeros in the padded couts
+                wp[:Cn] = w
+                want32 = wp[co, ch * 16 + 2 * cp + half, t]
+                assert np.array_equal(packed[:nf32].view(np.uint32), want32.reshape(-1).view(np.uint32)), (Cn, name, "fp32 section")
+                g = wp[co2, ci2, t2]                            # [tap][chunk][cout block][lane][8 channels]
+                got_bf = packed[nf32:nf32 + nbf // 2].view(np.uint16).reshape(3, nchunk, CP // 32, 3, 64, 8)
+                for i, p in enumerate(_bf16_pieces(g)):
+                    assert np.array_equal(got_bf[:, :, :, i], p), (Cn, name, "bf16 piece", i)
+                sw = _f16_scale(w)
+                if name == "zeros":
+                    assert sw == 1
+                if name == "tiny":
+                    assert sw == np.float32(2.0 ** -115)
+                got_h = packed[nf32 + nbf // 2:nf32 + nbf // 2 + nh // 2].view(np.uint16).reshape(3, nchunk, CP // 32, 2, 64, 8)
+                for i, p in enumerate(_f16_pieces(g, sw)):
+                    assert np.array_equal(got_h[:, :, :, i], p), (Cn, name, "fp16 piece", i)
+                a = np.abs(w.reshape(Cn, -1)).astype(np.float64)
+                acc = np.cumsum(np.where(np.isfinite(a), a, 0.0), axis=1)[:, -1]          # (in the packer's order: no pairwise sums)
+                l1 = np.float32(0)
+                for v in acc:
+                    l1 = max(l1, np.float32(v * (1.0 + 1e-6)))
+                tail = np.array([sw, l1, 0, 0], np.float32)
+                assert np.array_equal(packed[-4:].view(np.uint32), tail.view(np.uint32)), (Cn, name, "tail", packed[-4:], tail)
+        # lav_conv_pack_weights, LAV_CONV_F16X3: [cout block][tap][chunk][piece 2][lane][8 channels] fp16, then {s_w, 0, 0, 0}
+        cin, cout = 16, 32
+        d = Conv(1, cin, 0, cin, 16, 16, cout, 3, 3, 1, 1, 1, 1, 1, 0, 0, cout, 0, 0, 0, 0, 0, 0.0, _lib.CONV_F16X3)
+        total, off = lib.lav_conv_packed_weight_floats(C.byref(d)), lib.lav_conv_f16_weights_offset(C.byref(d))
+        assert off > 0 and (total - off - 4) * 4 % (9 * 2 * 1024) == 0
+        nblk = (total - off - 4) * 4 // (9 * 2 * 1024)           # cout blocks of 32 (cout_pad / 32), one 16-channel chunk
+        assert nblk >= 1
+        blk, tap, lane, el = np.meshgrid(np.arange(nblk), np.arange(9), np.arange(64), np.arange(8), indexing="ij")
+        for name, w in _split_rule_tensors((cout, cin, 3, 3)).items():
+            packed = np.full(total, np.nan, np.float32)
+            assert lib.lav_conv_pack_weights(C.byref(d), w.ctypes.data, packed.ctypes.data) == 0
+            wp = np.zeros((nblk * 32, cin, 3, 3), np.float32)
+            wp[:cout] = w
+            g = wp[blk * 32 + (lane & 31), 8 * (lane >> 5) + el, tap // 3, tap % 3]
+            sw = _f16_scale(w)
+            got_h = packed[off:-4].view(np.uint16).reshape(nblk, 9, 2, 64, 8)
+            for i, p in enumerate(_f16_pieces(g, sw)):
+                assert np.array_equal(got_h[:, :, i], p), ("conv", name, "fp16 piece", i)
+            assert np.array_equal(packed[-4:].view(np.uint32), np.array([sw, 0, 0, 0], np.float32).view(np.uint32)), ("conv", name, "scale word")
+
+
 def test_the_test_session_keeps_miopen_databases_to_itself():
     """tests/conftest.py: a GPU test session must not leave its (deterministic-mode) solver choices in MIOpen's default user database -
     the next process on the box inherits them (round 5: train_full at 634 instead of 128 ms per step, profiles/r05_miopen_db_poisoning.txt)."""
