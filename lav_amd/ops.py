@@ -575,7 +575,11 @@ class Amax:
 def tag_amax(t, am):
     """Attach the Amax whose parts bound |t| to the tensor OBJECT t (the producer's side of amax_of), stamped with the tensor's
     version and the Amax's generation: an in-place change of t, or a later call that resets the Amax (the same layers on another
-    input of the same shape), voids the bound."""
+    input of the same shape), voids the bound.  am None: t is returned untagged.  The only writer of these two attributes, for the
+    inference engines and the training layers (train.hipnn) alike: the training Amaxes are made fresh per launch and never reset(),
+    their generation stays 0 and the stamp comes down to the version check; one Amax may describe several tensors (hipnn.carry)."""
+    if am is None:
+        return t
     t._lav_amax = am
     t._lav_amax_stamp = (id(am), t._version, am.generation)
     return t
@@ -585,13 +589,10 @@ def amax_of(t):
     """The Amax a producer attached to the tensor OBJECT it returned (engine-internal hand-off between modules: backbone -> heads /
     crops), while it still bounds the tensor; None for anything else - the consumer then measures its input (one launch more,
     the same result).  A bound, not a measurement: valid for the tensor and for whatever is a max-pool, a crop or a bilinear
-    resampling of it.  Training-path tags (train.hipnn._tag) carry their version on the Amax."""
-    am = getattr(t, "_lav_amax", None)
-    if am is None:
+    resampling of it."""
+    am, stamp = getattr(t, "_lav_amax", None), getattr(t, "_lav_amax_stamp", None)
+    if am is None or stamp is None:
         return None
-    stamp = getattr(t, "_lav_amax_stamp", None)
-    if stamp is None:
-        return am if getattr(am, "version", None) == t._version else None
     return am if stamp == (id(am), t._version, am.generation) else None
 
 

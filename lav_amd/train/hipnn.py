@@ -45,27 +45,14 @@ def _bn_amax(B, C, hw, device):
     return am
 
 
-def _tag(t, am):
-    """Attach the bound to the tensor OBJECT it describes, with the tensor's version: a later in-place change (autograd accumulating a
-    second gradient into the buffer) voids it (_trusted)."""
-    if am is not None:
-        am.version = t._version
-        t._lav_amax = am
-    return t
-
-
-def _trusted(t):
-    am = getattr(t, "_lav_amax", None)
-    return am if am is not None and getattr(am, "version", None) == t._version else None
+# The bound a launch leaves on the tensor OBJECT it wrote is handed on by the inference engines' pair, ops.tag_amax / ops.amax_of: a
+# later in-place change (autograd accumulating a second gradient into the buffer) voids it.
+_trusted = ops_mod.amax_of      # (the name the tests ask by)
 
 
 def carry(out, src):
     """`out` holds a subset / a maximum of the values of `src` (a max-pooling): src's bound holds for it."""
-    am = _trusted(src)
-    if am is not None:
-        import copy
-        _tag(out, copy.copy(am))      # (shares the parts; its own version stamp)
-    return out
+    return ops_mod.tag_amax(out, ops_mod.amax_of(src))
 
 
 class _BnAct(torch.autograd.Function):
@@ -81,7 +68,7 @@ class _BnAct(torch.autograd.Function):
         check(_lib.load().lav_bn_train_forward_amax(_ptr(x), _ptr(res), _ptr(y), B, C, H * W, _ptr(gamma.contiguous()), _ptr(beta.contiguous()),
                                                     float(eps), int(relu_pre), int(relu_post), _ptr(save[0]), _ptr(save[1]), _ptr(save[2]),
                                                     _ptr(am.buf) if am is not None else None, _ptr(ws), ws.numel(), _stream()), "lav_bn_train_forward")
-        _tag(y, am)        # the convolution that reads y takes its scale from here (conv2d below)
+        ops_mod.tag_amax(y, am)        # the convolution that reads y takes its scale from here (conv2d below)
         ops_mod.train_work["bn_train_fwd_bytes"] += 4 * x.numel() * (3 + (res is not None))     # x twice, y once (+ the residual)
         ctx.save_for_backward(x, y if relu_post else None, gamma, save)
         ctx.cfg = (bool(relu_pre), bool(relu_post), residual is not None)
@@ -104,7 +91,7 @@ class _BnAct(torch.autograd.Function):
         check(_lib.load().lav_bn_train_backward_amax(_ptr(x), _ptr(y), _ptr(dy), B, C, H * W, _ptr(gamma.contiguous()), _ptr(save[0]), _ptr(save[2]),
                                                      int(relu_pre), int(relu_post), _ptr(dx), _ptr(dres), _ptr(dgb[0]), _ptr(dgb[1]),
                                                      _ptr(am.buf) if am is not None else None, _ptr(ws), ws.numel(), _stream()), "lav_bn_train_backward")
-        _tag(dx, am)       # the convolution whose output this BatchNorm read takes its gradient's scale from here (_Conv2d.backward)
+        ops_mod.tag_amax(dx, am)       # the convolution whose output this BatchNorm read takes its gradient's scale from here (_Conv2d.backward)
         # x and dy twice, dx once; relu_post reads y (twice without a residual, else once + the masked gradient written and re-read)
         ops_mod.train_work["bn_train_bwd_bytes"] += 4 * x.numel() * (5 + (2 if relu_post else 0))
         return dx, dgb[0], dgb[1], (dres if dres is not None else dy) if has_res else None, None, None, None
@@ -265,7 +252,7 @@ class _Conv2d(torch.autograd.Function):
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
         stride, padding, dilation = ctx.cfg
-        am_in = _trusted(dy)
+        am_in = ops_mod.amax_of(dy)
         dy = dy.contiguous()
         dx = dw = None
         am_dy = None
@@ -341,7 +328,7 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, stride: int = 1, padding=(0, 0), di
             or x.numel() == 0 or os.environ.get("LAV_TRAIN_CONV", "hip") == "torch"):
         return F.conv2d(x, w, None, stride, tuple(padding), tuple(dilation))
     # (the bound a producer left on x - a BatchNorm of this module, a max-pool of one - is read HERE, from the object the caller holds)
-    return _Conv2d.apply(x, w, int(stride), tuple(padding), tuple(dilation), _trusted(x))
+    return _Conv2d.apply(x, w, int(stride), tuple(padding), tuple(dilation), ops_mod.amax_of(x))
 
 
 class _ConvT2d(torch.autograd.Function):

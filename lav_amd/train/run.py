@@ -2,15 +2,18 @@
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import json
 import os
 import time
+from typing import Callable, Optional
 
 import torch
 import torch.distributed as dist
 
+from .brake import BRA_LABELS, BrakeTrainer
 from .lav import LAV, TrainConfig
-from .synthetic import synthetic_bev_batch, synthetic_lidar_batch, synthetic_seg_batch
+from .synthetic import synthetic_bev_batch, synthetic_bra_batch, synthetic_lidar_batch, synthetic_seg_batch
 
 
 def setup_distributed():
@@ -57,19 +60,9 @@ def train_loop(what, global_batch, steps, warmup, cfg=None, max_points=None, log
             dist.barrier()
 
     if wrap is not None:      # a context manager factory over the trainer (bench.py's CPU leg swaps the teacher's kernels for torch ops)
-        with wrap(lav):
-            return _run_steps(step, steps, warmup, device, world, rank, log) + ((rank, world),)
-    info = None
-    for _ in range(warmup):
-        info = step()
-    sync()
-    t0 = time.perf_counter()
-    for i in range(steps):
-        info = step()
-        if log and rank == 0:
-            log(i, info)
-    sync()
-    dt = time.perf_counter() - t0
+        with wrap(lav):       # (host work: no device sync, no all-reduce of the time)
+            return _run_steps(step, steps, warmup, rank, log) + ((rank, world),)
+    dt, info = _run_steps(step, steps, warmup, rank, log, sync)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -99,15 +92,18 @@ def train_loop(what, global_batch, steps, warmup, cfg=None, max_points=None, log
     return dt, info, (rank, world)
 
 
-def _run_steps(step, steps, warmup, device, world, rank, log):
+def _run_steps(step, steps, warmup, rank, log, sync=lambda: None):
+    """train_loop's warm-up and timed loop: (seconds for `steps`, last info); `sync` brackets the timed region."""
     info = None
     for _ in range(warmup):
         info = step()
+    sync()
     t0 = time.perf_counter()
     for i in range(steps):
         info = step()
         if log and rank == 0:
             log(i, info)
+    sync()
     return time.perf_counter() - t0, info
 
 
@@ -115,7 +111,6 @@ def load_config(path, **overrides) -> TrainConfig:
     """TrainConfig from the reference's YAML (config_v2.yaml): every key that TrainConfig has is taken from the file,
     the others (data paths, controller gains ...) are not part of the training step.  `distill` is read by
     lav_final_v2.py:244 but absent from config_v2.yaml (team_code_v2/config.yaml:11 says True): injected as True."""
-    import dataclasses
     import yaml
     fields = {f.name for f in dataclasses.fields(TrainConfig)}
     vals = {}
@@ -183,130 +178,6 @@ def other_weight_schedule(it, beta=0.8):
     return 1 - beta ** (it / 4000)
 
 
-def main(what):
-    """Command line of lav/train_full_v2.py:48-70 / lav/train_bev_v2.py:42-63 (same flags and defaults): the recorded routes
-    under the config's `data_dir` are read by lav_amd.data ('temporal_lidar_painted' / 'temporal_bev' loaders, every rank its
-    own shard of each epoch).  What this build adds: --synthetic / --steps-per-epoch (seeded synthetic batches instead of a
-    data set), --save-dir, --lidar / --bev / --uniplanner (checkpoints to start from), --max-points, --log-every, --bev-on-device
-    (the loaders hand over the decoded map planes and their warps, lav_bev_stack_u8 renders the batch's BEV stacks behind the upload)."""
-    if what == "seg":
-        return main_seg()
-    if what == "bra":
-        return main_bra()
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--config-path", default=None, help="the reference's config_v2.yaml (training keys are read from it)")
-    ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
-    ap.add_argument("--perceive-only", action="store_true")
-    ap.add_argument("--motion-only", action="store_true")
-    ap.add_argument("--num-epoch", type=int, default=64 if what == "lidar" else 160)
-    ap.add_argument("--num-per-log", type=int, default=100, help="log per iter")
-    ap.add_argument("--num-per-save", type=int, default=1, help="save per epoch")
-    ap.add_argument("--batch-size", type=int, default=32 if what == "lidar" else 256, help="GLOBAL batch, split over the ranks")
-    ap.add_argument("--lr", type=float, default=3e-4)
-    ap.add_argument("--weight-decay", type=float, default=2e-4, help="accepted for command-line compatibility; the reference never passes it to Adam")
-    ap.add_argument("--num-workers", type=int, default=16, help="DataLoader workers (recorded routes only)")
-    ap.add_argument("--seed", type=int, default=2021)
-    ap.add_argument("--synthetic", action="store_true", help="seeded synthetic batches instead of the config's data_dir")
-    ap.add_argument("--steps-per-epoch", type=int, default=20, help="iterations that make one epoch of synthetic data")
-    ap.add_argument("--save-dir", default="checkpoints")
-    ap.add_argument("--lidar", default=None, help="lidar_*.th to start from")
-    ap.add_argument("--bev", default=None, help="bev_*.th to start from / the teacher of train_full_v2")
-    ap.add_argument("--uniplanner", default=None, help="uniplanner_*.th to start from")
-    ap.add_argument("--max-points", type=int, default=None)
-    ap.add_argument("--log-every", type=int, default=None, help="steps between the eval-mode log inference (default: --num-per-log)")
-    ap.add_argument("--deterministic", action="store_true", help="bit-reproducible steps: deterministic torch / MIOpen algorithms "
-                    "(liblav_amd's own kernels always are); slower convolution gradients")
-    ap.add_argument("--bev-on-device", action="store_true",
-                    help="recorded routes only: the loaders return the decoded map planes with their warp coefficients "
-                         "(lav_amd.data.bev_stack) and the batch's BEV stacks are rendered after the uint8 upload, bit-identical to the "
-                         "loaders' own; no effect with --synthetic")
-    args = ap.parse_args()
-    if args.deterministic:
-        set_deterministic(True)
-    if not args.synthetic and not args.config_path:
-        raise SystemExit("recorded routes are read from the data_dir of --config-path (or pass --synthetic)")
-    rank, world, device = setup_distributed()
-    if args.device == "cpu":
-        device = torch.device("cpu")
-    cfg = load_config(args.config_path, lr=args.lr, perceive_only=args.perceive_only, motion_only=args.motion_only, seed=args.seed,
-                      log_every=args.log_every if args.log_every is not None else args.num_per_log)
-    if args.batch_size % world:
-        raise SystemExit(f"global batch {args.batch_size} is not divisible by {world} ranks")
-    per_rank = args.batch_size // world
-    paths = resolve_checkpoints(what, args)
-    ck = {k: torch.load(v, map_location="cpu") for k, v in paths.items() if v}
-    torch.manual_seed(cfg.seed + rank)
-    lav = LAV(cfg, device, what=what, checkpoints=ck)
-    log = lambda it, inf: print(it, {k: round(v, 4) for k, v in inf.items() if isinstance(v, float)}, flush=True)
-    loader = None
-    if not args.synthetic:
-        from ..data import get_data_loader
-        loader = get_data_loader("temporal_bev" if what == "bev" else "temporal_lidar_painted", args, rank=rank, world=world,
-                                 bev_on_device=args.bev_on_device)
-        if len(loader) == 0:
-            raise SystemExit(f"{args.config_path}: data_dir holds fewer frames than one batch of {args.batch_size}")
-
-    stacker, bev_at = None, 0 if what == "bev" else 5      # where the sample tuples hold `bev`
-    if loader is not None and args.bev_on_device:
-        from ..data.bev_stack import BevStacker
-        stacker = BevStacker()
-
-    def batches(epoch):
-        if loader is not None:
-            if world > 1:
-                loader.sampler.set_epoch(epoch)
-            for batch in loader:
-                if stacker is not None:      # the planes go up as uint8 (the bytes `bev` itself would take) and are rendered there
-                    batch = list(batch)
-                    batch[bev_at] = stacker(batch[bev_at], device=device)
-                yield batch
-            return
-        for it in range(args.steps_per_epoch):
-            seed = cfg.seed + 1000003 * epoch + 1009 * it + 100 * rank
-            if what == "bev":
-                yield synthetic_bev_batch(per_rank, seed=seed, device=device)
-            else:
-                yield synthetic_lidar_batch(per_rank, seed=seed, max_points=args.max_points or cfg.max_lidar_points, device=device)
-
-    global_it, t0 = 0, time.perf_counter()
-    for epoch in range(args.num_epoch):
-        for batch in batches(epoch):
-            if what == "bev":
-                info = lav.train_bev(*batch, other_weight=other_weight_schedule(global_it))
-            else:
-                info = lav.train_lidar(*batch)
-            if global_it % args.num_per_log == 0 and rank == 0:
-                log(global_it, info)
-            global_it += 1
-        (lav.bev_scheduler if what == "bev" else lav.lidar_scheduler).step()       # once per epoch (train_full_v2.py:33)
-        if (epoch + 1) % args.num_per_save == 0 and rank == 0:
-            os.makedirs(args.save_dir, exist_ok=True)
-            for name in (("bev",) if what == "bev" else ("lidar", "uniplanner")):
-                path = os.path.join(args.save_dir, f"{name}_{epoch + 1}.th")
-                torch.save(lav.state_dict(name), path)
-                print(f"saved to {path}", flush=True)
-    if device.type == "cuda":
-        torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    in_sync = None
-    if world > 1:   # data parallel keeps the replicas identical: compare a checksum of every trained parameter across the ranks
-        # (BatchNorm's running statistics are per-rank by design - DDP re-broadcasts rank 0's before each forward - and are left out)
-        mods = (lav.bev_planner,) if what == "bev" else (lav.lidar_model, lav.uniplanner)
-        mine = torch.stack([p_.detach().double().sum() for m in mods for p_ in m.parameters() if p_.requires_grad]).to(device)
-        every = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(every, mine)
-        in_sync = all(torch.equal(every[0], e) for e in every[1:])
-    if rank == 0:
-        print(json.dumps(dict(what=what, samples_per_s=round(args.batch_size * global_it / dt, 2), n_gpus=world, replicas_in_sync=in_sync,
-                              global_batch=args.batch_size, steps=global_it, epochs=args.num_epoch,
-                              data="synthetic batches" if loader is None else f"{len(loader.dataset)} recorded frames",
-                              lr=(lav.bev_optim if what == "bev" else lav.lidar_optim).param_groups[0]["lr"],
-                              scheduler_epochs=(lav.bev_scheduler if what == "bev" else lav.lidar_scheduler).last_epoch)))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-
-
 def _augmenters(args, rank, world, streams):
     """--augment PROB > 0: one lav_amd.data.augment.Augmenter per image stream (stream tags 0, 1, ...), every rank with its own sample
     ids; None for 0 (nothing changes: no uint8 upload, no launch)."""
@@ -323,51 +194,175 @@ def _as_u8_hwc(rgb):
     return rgb if rgb.dtype == torch.uint8 else rgb.round().clamp(0, 255).to(torch.uint8)
 
 
-def main_seg():
-    """Command line of lav/train_seg.py (same flags and defaults; --config-path defaults to the v2 agent's config, the consumer
-    of the segmenter): the camera images of the config's data_dir through the 'seg' loader, one Adam step per batch,
-    seg_{epoch}.th saved every --num-per-save epochs with RGBSegmentationModel's keys (the agent's `seg_model_dir`).  What this
-    build adds: --synthetic / --steps-per-epoch (seeded synthetic 288 x 256 images), --save-dir, --seg (a checkpoint to start from),
-    --augment PROB (the reference's augment(0.5) of every camera image, here on the device: lav_amd.data.augment)."""
+@dataclasses.dataclass
+class _Trainer:
+    """What one of the four command lines has of its own; main() is everything else.  The trainer object `build` returns names its
+    optimiser {what}_optim, its per-epoch scheduler {what}_scheduler if it has one, and saves state_dict(name) as {name}_{epoch}.th."""
+    num_epoch: int                  # defaults of --num-epoch, --batch-size, --config-path (None: a run on recorded routes must name one)
+    batch_size: int
+    config_path: Optional[str]
+    config_help: str
+    flags: dict                     # its own flags: {the shared flag they follow in --help: [(flag, add_argument keywords), ...]}
+    build: Callable                 # (args, cfg, device, rank) -> the trainer object, from the checkpoints the flags name
+    loader: str                     # lav_amd.data.get_data_loader's name, and what it counts
+    unit: str
+    synthetic: Callable             # (args, cfg, per_rank, seed, device) -> one seeded batch
+    stepper: Callable               # (trainer, args, rank, world, device, loader) -> step(batch, global_it) -> info; called once, after the loader
+    log: Callable                   # info -> what a log line shows of it
+    saves: tuple
+    replicas: tuple                 # the trainer's modules whose parameters the replica checksum covers; (): no check, no summary field
+    overrides: Callable = lambda args: {}       # TrainConfig keys taken from the command line besides lr and seed
+    loader_kwargs: Callable = lambda args: {}
+    guard_dt: bool = True
+
+
+def _lav(what):
+    """lav/train_bev_v2.py:42-63 ("bev") / lav/train_full_v2.py:48-70 ("lidar"), same flags and defaults, over the 'temporal_bev' /
+    'temporal_lidar_painted' loaders.  What this build adds: --lidar / --bev / --uniplanner (checkpoints to start from), --max-points,
+    --log-every, --deterministic, --bev-on-device (the loaders hand over the decoded map planes and their warps, lav_bev_stack_u8
+    renders the batch's BEV stacks behind the upload)."""
+    bev = what == "bev"
+
+    def build(args, cfg, device, rank):
+        ck = {k: torch.load(v, map_location="cpu") for k, v in resolve_checkpoints(what, args).items() if v}
+        torch.manual_seed(cfg.seed + rank)      # (kept as found: seeded per rank BEFORE the trainer is built; seg / bra seed after the loader)
+        return LAV(cfg, device, what=what, checkpoints=ck)
+
+    def stepper(lav, args, rank, world, device, loader):
+        stacker, bev_at = None, 0 if bev else 5      # where the sample tuples hold `bev`
+        if loader is not None and args.bev_on_device:
+            from ..data.bev_stack import BevStacker
+            stacker = BevStacker()
+
+        def step(batch, it):
+            if stacker is not None:      # the planes go up as uint8 (the bytes `bev` itself would take) and are rendered there
+                batch = list(batch)
+                batch[bev_at] = stacker(batch[bev_at], device=device)
+            return lav.train_bev(*batch, other_weight=other_weight_schedule(it)) if bev else lav.train_lidar(*batch)
+        return step
+
+    def synthetic(args, cfg, per_rank, seed, device):
+        if bev:
+            return synthetic_bev_batch(per_rank, seed=seed, device=device)
+        return synthetic_lidar_batch(per_rank, seed=seed, max_points=args.max_points or cfg.max_lidar_points, device=device)
+
+    flags = {
+        "--device": [("--perceive-only", dict(action="store_true")), ("--motion-only", dict(action="store_true"))],
+        "--lr": [("--weight-decay", dict(type=float, default=2e-4, help="accepted for command-line compatibility; the reference never passes it to Adam"))],
+        "--save-dir": [
+            ("--lidar", dict(default=None, help="lidar_*.th to start from")),
+            ("--bev", dict(default=None, help="bev_*.th to start from / the teacher of train_full_v2")),
+            ("--uniplanner", dict(default=None, help="uniplanner_*.th to start from")),
+            ("--max-points", dict(type=int, default=None)),
+            ("--log-every", dict(type=int, default=None, help="steps between the eval-mode log inference (default: --num-per-log)")),
+            ("--deterministic", dict(action="store_true", help="bit-reproducible steps: deterministic torch / MIOpen algorithms "
+                                     "(liblav_amd's own kernels always are); slower convolution gradients")),
+            ("--bev-on-device", dict(action="store_true",
+                                     help="recorded routes only: the loaders return the decoded map planes with their warp coefficients "
+                                          "(lav_amd.data.bev_stack) and the batch's BEV stacks are rendered after the uint8 upload, bit-identical to the "
+                                          "loaders' own; no effect with --synthetic"))]}
+    return _Trainer(
+        num_epoch=160 if bev else 64, batch_size=256 if bev else 32, config_path=None,
+        config_help="the reference's config_v2.yaml (training keys are read from it)", flags=flags, build=build,
+        loader="temporal_bev" if bev else "temporal_lidar_painted", unit="frames", synthetic=synthetic, stepper=stepper,
+        log=lambda info: {k: round(v, 4) for k, v in info.items() if isinstance(v, float)},
+        saves=("bev",) if bev else ("lidar", "uniplanner"), replicas=("bev_planner",) if bev else ("lidar_model", "uniplanner"),
+        overrides=lambda args: dict(perceive_only=args.perceive_only, motion_only=args.motion_only,
+                                    log_every=args.log_every if args.log_every is not None else args.num_per_log),
+        loader_kwargs=lambda args: dict(bev_on_device=args.bev_on_device),
+        guard_dt=False)     # (kept as found: these two divide by the bare elapsed time, seg / bra by max(dt, 1e-9))
+
+
+def _camera_stepper(images, train):
+    """seg / bra: --augment's Augmenters over a batch's first `images` tensors (one stream tag each), then train(trainer)(*batch)."""
+    def stepper(trainer, args, rank, world, device, loader):
+        torch.manual_seed(args.seed)        # (kept as found: after the trainer and the loader, the same seed on every rank)
+        aug = _augmenters(args, rank, world, images)
+
+        def step(batch, it):
+            if aug is not None:      # uploaded as uint8 and augmented there; the train step converts them as ever
+                batch = [a(_as_u8_hwc(x).to(device)) for a, x in zip(aug, batch)] + list(batch[images:])
+            return train(trainer)(*batch)
+        return step
+    return stepper
+
+
+_AUGMENT = ("--augment", dict(type=float, default=0.0, metavar="PROB",
+                              help="image augmentation (lav_amd.data.augment): each of the seven ops with this probability, on the device, after a "
+                                   "uint8 upload; the reference trains with 0.5 (augment(0.5)).  Default 0: no augmentation"))
+
+# lav/train_seg.py, same flags and defaults (--config-path defaults to the v2 agent's config, the consumer of the segmenter): the camera
+# images of the 'seg' loader or synthetic 288 x 256 ones, seg_{epoch}.th with RGBSegmentationModel's keys (the agent's `seg_model_dir`).
+# What this build adds: --seg (a checkpoint to start from), --augment PROB (the reference's augment(0.5) of every camera image).
+_SEG = _Trainer(
+    num_epoch=1, batch_size=256, config_path="config_v2.yaml", config_help="the reference's config_v2.yaml (seg_channels, data_dir)",
+    flags={"--save-dir": [("--seg", dict(default=None, help="seg_*.th to start from")), _AUGMENT]},
+    build=lambda args, cfg, device, rank: LAV(cfg, device, what="seg", checkpoints={"seg": torch.load(args.seg, map_location="cpu")} if args.seg else {}),
+    loader="seg", unit="camera images", stepper=_camera_stepper(1, lambda lav: lav.train_seg), saves=("seg",),
+    synthetic=lambda args, cfg, per_rank, seed, device: synthetic_seg_batch(per_rank, seed=seed, num_classes=len(cfg.seg_channels) + 1, device=device),
+    log=lambda info: dict(loss=round(info["loss"], 4)),
+    replicas=())        # (kept as found: no replica checksum, no replicas_in_sync in the summary)
+
+# lav/train_bra_v2.py, same flags and defaults: the 'bra' loader (the three front cameras side by side, the telephoto camera, their labels,
+# the brake flag) or synthetic 288 x 768 + 192 x 480 images, bra_{epoch}.th with RGBBrakePredictionModel([4, 10, 18])'s keys (the agent's
+# `bra_model_dir`).  What this build adds: --bra (a checkpoint to start from), --augment PROB (the wide and the telephoto image).
+_BRA = _Trainer(
+    num_epoch=10, batch_size=52, config_path="config_v2.yaml", config_help="the reference's config_v2.yaml (data_dir, camera_yaws, crop_tel_bottom)",
+    flags={"--save-dir": [("--bra", dict(default=None, help="bra_*.th to start from")), _AUGMENT]},
+    build=lambda args, cfg, device, rank: BrakeTrainer(cfg, device, checkpoints={"bra": torch.load(args.bra, map_location="cpu")} if args.bra else {}),
+    loader="bra", unit="frames", stepper=_camera_stepper(2, lambda trainer: trainer.train_bra), saves=("bra",),
+    synthetic=lambda args, cfg, per_rank, seed, device: synthetic_bra_batch(per_rank, seed=seed, num_classes=len(BRA_LABELS) + 1, device=device),
+    log=lambda info: dict(loss=round(info["loss"], 4), bra=info["bra"], pred_bra=round(info["pred_bra"], 4)), replicas=("bra_model",))
+
+
+def main(what):
+    """The command line of train_bev_v2.py ("bev"), train_full_v2.py ("lidar"), train_seg.py ("seg") and train_bra_v2.py ("bra"), from
+    the parser to the teardown: the recorded routes under the config's `data_dir` are read by lav_amd.data (every rank its own shard of
+    each epoch), one optimiser step per batch, checkpoints every --num-per-save epochs, one JSON summary line.  What this build adds to
+    the reference's flags: --synthetic / --steps-per-epoch (seeded synthetic batches instead of a data set), --save-dir, and what the
+    trainer's description (_lav, _SEG, _BRA) names."""
+    t = {"seg": _SEG, "bra": _BRA}.get(what) or _lav(what)
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config-path", default="config_v2.yaml", help="the reference's config_v2.yaml (seg_channels, data_dir)")
-    ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
-    ap.add_argument("--num-epoch", type=int, default=1)
-    ap.add_argument("--num-per-log", type=int, default=100, help="log per iter")
-    ap.add_argument("--num-per-save", type=int, default=1, help="save per epoch")
-    ap.add_argument("--batch-size", type=int, default=256, help="GLOBAL batch, split over the ranks")
-    ap.add_argument("--lr", type=float, default=3e-4)
-    ap.add_argument("--num-workers", type=int, default=16, help="DataLoader workers (recorded routes only)")
-    ap.add_argument("--seed", type=int, default=2021)
-    ap.add_argument("--synthetic", action="store_true", help="seeded synthetic batches instead of the config's data_dir")
-    ap.add_argument("--steps-per-epoch", type=int, default=20, help="iterations that make one epoch of synthetic data")
-    ap.add_argument("--save-dir", default="checkpoints")
-    ap.add_argument("--seg", default=None, help="seg_*.th to start from")
-    ap.add_argument("--augment", type=float, default=0.0, metavar="PROB",
-                    help="image augmentation (lav_amd.data.augment): each of the seven ops with this probability, on the device, after a "
-                         "uint8 upload; the reference trains with 0.5 (augment(0.5)).  Default 0: no augmentation")
+    for flag, kw in (
+            ("--config-path", dict(default=t.config_path, help=t.config_help)),
+            ("--device", dict(default="cuda", choices=["cuda", "cpu"])),
+            ("--num-epoch", dict(type=int, default=t.num_epoch)),
+            ("--num-per-log", dict(type=int, default=100, help="log per iter")),
+            ("--num-per-save", dict(type=int, default=1, help="save per epoch")),
+            ("--batch-size", dict(type=int, default=t.batch_size, help="GLOBAL batch, split over the ranks")),
+            ("--lr", dict(type=float, default=3e-4)),
+            ("--num-workers", dict(type=int, default=16, help="DataLoader workers (recorded routes only)")),
+            ("--seed", dict(type=int, default=2021)),
+            ("--synthetic", dict(action="store_true", help="seeded synthetic batches instead of the config's data_dir")),
+            ("--steps-per-epoch", dict(type=int, default=20, help="iterations that make one epoch of synthetic data")),
+            ("--save-dir", dict(default="checkpoints"))):
+        for f, k in [(flag, kw)] + t.flags.get(flag, []):
+            ap.add_argument(f, **k)
     args = ap.parse_args()
-    have_cfg = bool(args.config_path) and os.path.isfile(args.config_path)
+    if getattr(args, "deterministic", False):
+        set_deterministic(True)
+    # without a default (bev / lidar) the file named must exist, open() says so; a default that is not there (seg / bra) is no config
+    named = t.config_path is None
+    have_cfg = bool(args.config_path) and (named or os.path.isfile(args.config_path))
     if not args.synthetic and not have_cfg:
-        raise SystemExit(f"recorded routes are read from the data_dir of --config-path ({args.config_path} not found; or pass --synthetic)")
+        raise SystemExit("recorded routes are read from the data_dir of --config-path ("
+                         + ("" if named else f"{args.config_path} not found; ") + "or pass --synthetic)")
     rank, world, device = setup_distributed()
     if args.device == "cpu":
         device = torch.device("cpu")
-    cfg = load_config(args.config_path if have_cfg else None, lr=args.lr, seed=args.seed)
+    cfg = load_config(args.config_path if have_cfg else None, lr=args.lr, seed=args.seed, **t.overrides(args))
     if args.batch_size % world:
         raise SystemExit(f"global batch {args.batch_size} is not divisible by {world} ranks")
     per_rank = args.batch_size // world
-    ck = {"seg": torch.load(args.seg, map_location="cpu")} if args.seg else {}
-    lav = LAV(cfg, device, what="seg", checkpoints=ck)
+    trainer = t.build(args, cfg, device, rank)
     loader = None
     if not args.synthetic:
         from ..data import get_data_loader
-        loader = get_data_loader("seg", args, rank=rank, world=world)
+        loader = get_data_loader(t.loader, args, rank=rank, world=world, **t.loader_kwargs(args))
         if len(loader) == 0:
-            raise SystemExit(f"{args.config_path}: data_dir holds fewer camera images than one batch of {args.batch_size}")
-    torch.manual_seed(args.seed)
-    aug = _augmenters(args, rank, world, 1)
-    aug = aug[0] if aug else None
+            raise SystemExit(f"{args.config_path}: data_dir holds fewer {t.unit} than one batch of {args.batch_size}")
+    step = t.stepper(trainer, args, rank, world, device, loader)
+    scheduler = getattr(trainer, f"{what}_scheduler", None)
 
     def batches(epoch):
         if loader is not None:
@@ -376,121 +371,42 @@ def main_seg():
             yield from loader
             return
         for it in range(args.steps_per_epoch):
-            yield synthetic_seg_batch(per_rank, seed=cfg.seed + 1000003 * epoch + 1009 * it + 100 * rank,
-                                      num_classes=len(cfg.seg_channels) + 1, device=device)
+            yield t.synthetic(args, cfg, per_rank, cfg.seed + 1000003 * epoch + 1009 * it + 100 * rank, device)
 
     global_it, t0 = 0, time.perf_counter()
     for epoch in range(args.num_epoch):
-        for rgb, sem in batches(epoch):
-            if aug is not None:
-                rgb = aug(_as_u8_hwc(rgb).to(device))      # uploaded as uint8 and augmented there; train_seg converts it as ever
-            info = lav.train_seg(rgb, sem)
+        for batch in batches(epoch):
+            info = step(batch, global_it)
             if global_it % args.num_per_log == 0 and rank == 0:
-                print(global_it, dict(loss=round(info["loss"], 4)), flush=True)
+                print(global_it, t.log(info), flush=True)
             global_it += 1
+        if scheduler is not None:
+            scheduler.step()       # once per epoch (train_full_v2.py:33)
         if (epoch + 1) % args.num_per_save == 0 and rank == 0:
             os.makedirs(args.save_dir, exist_ok=True)
-            path = os.path.join(args.save_dir, f"seg_{epoch + 1}.th")
-            torch.save(lav.state_dict("seg"), path)
-            print(f"saved to {path}", flush=True)
+            for name in t.saves:
+                path = os.path.join(args.save_dir, f"{name}_{epoch + 1}.th")
+                torch.save(trainer.state_dict(name), path)
+                print(f"saved to {path}", flush=True)
     if device.type == "cuda":
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    summary = dict(what=what, samples_per_s=round(args.batch_size * global_it / (max(dt, 1e-9) if t.guard_dt else dt), 2), n_gpus=world)
+    if t.replicas:
+        summary["replicas_in_sync"] = None
+        if world > 1:   # data parallel keeps the replicas identical: compare a checksum of every trained parameter across the ranks
+            # (BatchNorm's running statistics are per-rank by design - DDP re-broadcasts rank 0's before each forward - and are left out)
+            mine = torch.stack([p_.detach().double().sum() for m in t.replicas for p_ in getattr(trainer, m).parameters() if p_.requires_grad]).to(device)
+            every = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(every, mine)
+            summary["replicas_in_sync"] = all(torch.equal(every[0], e) for e in every[1:])
+    summary.update(global_batch=args.batch_size, steps=global_it, epochs=args.num_epoch,
+                   data="synthetic batches" if loader is None else f"{len(loader.dataset)} recorded {t.unit}",
+                   lr=getattr(trainer, f"{what}_optim").param_groups[0]["lr"])
+    if scheduler is not None:
+        summary["scheduler_epochs"] = scheduler.last_epoch
     if rank == 0:
-        print(json.dumps(dict(what="seg", samples_per_s=round(args.batch_size * global_it / max(dt, 1e-9), 2), n_gpus=world,
-                              global_batch=args.batch_size, steps=global_it, epochs=args.num_epoch,
-                              data="synthetic batches" if loader is None else f"{len(loader.dataset)} recorded camera images",
-                              lr=lav.seg_optim.param_groups[0]["lr"])))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-
-
-def main_bra():
-    """Command line of lav/train_bra_v2.py (same flags and defaults): the 'bra' loader over the config's data_dir (the three front
-    cameras side by side, the telephoto camera, their labels, the brake flag), one Adam step per batch, bra_{epoch}.th saved every
-    --num-per-save epochs with RGBBrakePredictionModel([4, 10, 18])'s keys (the agent's `bra_model_dir`).  What this build adds:
-    --synthetic / --steps-per-epoch (seeded synthetic 288 x 768 + 192 x 480 images), --save-dir, --bra (a checkpoint to start from),
-    --augment PROB (the reference's augment(0.5) of the wide and the telephoto image, here on the device: lav_amd.data.augment)."""
-    from .brake import BRA_LABELS, BrakeTrainer
-    from .synthetic import synthetic_bra_batch
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--config-path", default="config_v2.yaml", help="the reference's config_v2.yaml (data_dir, camera_yaws, crop_tel_bottom)")
-    ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
-    ap.add_argument("--num-epoch", type=int, default=10)
-    ap.add_argument("--num-per-log", type=int, default=100, help="log per iter")
-    ap.add_argument("--num-per-save", type=int, default=1, help="save per epoch")
-    ap.add_argument("--batch-size", type=int, default=52, help="GLOBAL batch, split over the ranks")
-    ap.add_argument("--lr", type=float, default=3e-4)
-    ap.add_argument("--num-workers", type=int, default=16, help="DataLoader workers (recorded routes only)")
-    ap.add_argument("--seed", type=int, default=2021)
-    ap.add_argument("--synthetic", action="store_true", help="seeded synthetic batches instead of the config's data_dir")
-    ap.add_argument("--steps-per-epoch", type=int, default=20, help="iterations that make one epoch of synthetic data")
-    ap.add_argument("--save-dir", default="checkpoints")
-    ap.add_argument("--bra", default=None, help="bra_*.th to start from")
-    ap.add_argument("--augment", type=float, default=0.0, metavar="PROB",
-                    help="image augmentation (lav_amd.data.augment): each of the seven ops with this probability, on the device, after a "
-                         "uint8 upload; the reference trains with 0.5 (augment(0.5)).  Default 0: no augmentation")
-    args = ap.parse_args()
-    have_cfg = bool(args.config_path) and os.path.isfile(args.config_path)
-    if not args.synthetic and not have_cfg:
-        raise SystemExit(f"recorded routes are read from the data_dir of --config-path ({args.config_path} not found; or pass --synthetic)")
-    rank, world, device = setup_distributed()
-    if args.device == "cpu":
-        device = torch.device("cpu")
-    cfg = load_config(args.config_path if have_cfg else None, lr=args.lr, seed=args.seed)
-    if args.batch_size % world:
-        raise SystemExit(f"global batch {args.batch_size} is not divisible by {world} ranks")
-    per_rank = args.batch_size // world
-    ck = {"bra": torch.load(args.bra, map_location="cpu")} if args.bra else {}
-    trainer = BrakeTrainer(cfg, device, checkpoints=ck)
-    loader = None
-    if not args.synthetic:
-        from ..data import get_data_loader
-        loader = get_data_loader("bra", args, rank=rank, world=world)
-        if len(loader) == 0:
-            raise SystemExit(f"{args.config_path}: data_dir holds fewer frames than one batch of {args.batch_size}")
-    torch.manual_seed(args.seed)
-    aug = _augmenters(args, rank, world, 2)      # wide, tele: separate stream tags
-
-    def batches(epoch):
-        if loader is not None:
-            if world > 1:
-                loader.sampler.set_epoch(epoch)
-            yield from loader
-            return
-        for it in range(args.steps_per_epoch):
-            yield synthetic_bra_batch(per_rank, seed=cfg.seed + 1000003 * epoch + 1009 * it + 100 * rank, num_classes=len(BRA_LABELS) + 1,
-                                      device=device)
-
-    global_it, t0 = 0, time.perf_counter()
-    for epoch in range(args.num_epoch):
-        for rgb1, rgb2, sem1, sem2, bra in batches(epoch):
-            if aug is not None:
-                rgb1, rgb2 = aug[0](_as_u8_hwc(rgb1).to(device)), aug[1](_as_u8_hwc(rgb2).to(device))
-            info = trainer.train_bra(rgb1, rgb2, sem1, sem2, bra)
-            if global_it % args.num_per_log == 0 and rank == 0:
-                print(global_it, dict(loss=round(info["loss"], 4), bra=info["bra"], pred_bra=round(info["pred_bra"], 4)), flush=True)
-            global_it += 1
-        if (epoch + 1) % args.num_per_save == 0 and rank == 0:
-            os.makedirs(args.save_dir, exist_ok=True)
-            path = os.path.join(args.save_dir, f"bra_{epoch + 1}.th")
-            torch.save(trainer.state_dict("bra"), path)
-            print(f"saved to {path}", flush=True)
-    if device.type == "cuda":
-        torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    in_sync = None
-    if world > 1:   # as main(): a checksum of every trained parameter, compared across the ranks
-        mine = torch.stack([p_.detach().double().sum() for p_ in trainer.bra_model.parameters() if p_.requires_grad]).to(device)
-        every = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(every, mine)
-        in_sync = all(torch.equal(every[0], e) for e in every[1:])
-    if rank == 0:
-        print(json.dumps(dict(what="bra", samples_per_s=round(args.batch_size * global_it / max(dt, 1e-9), 2), n_gpus=world,
-                              replicas_in_sync=in_sync, global_batch=args.batch_size, steps=global_it, epochs=args.num_epoch,
-                              data="synthetic batches" if loader is None else f"{len(loader.dataset)} recorded frames",
-                              lr=trainer.bra_optim.param_groups[0]["lr"])))
+        print(json.dumps(summary))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

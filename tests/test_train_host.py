@@ -164,3 +164,37 @@ def test_decoder_caches_follow_load_state_dict_and_mode_toggles():
         assert torch.equal(m._dec(cpu)["cast"]["w_ih"][0], m._cast_modules()[0][0].weight_ih_l0), type(m).__name__
         assert not torch.equal(m._dec(cpu)["cast"]["w_ih"], after)
         assert m.offsets() == (2.0, 2.75)
+
+
+def test_amax_tag_has_one_definition_for_inference_and_training():
+    """ops.tag_amax / ops.amax_of are the only writer and reader of a tensor's f16x3 bound; hipnn._trusted and hipnn.carry (the training
+    side) are the same pair: the stamp lives on the tensor, so one Amax may describe several tensors and an edit of one voids only its own."""
+    from lav_amd import ops
+    from lav_amd.train import hipnn
+    assert hipnn._trusted is ops.amax_of
+    am = ops.Amax("cpu", capacity=4)
+    t = torch.zeros(4)
+    assert ops.tag_amax(t, am) is t and ops.amax_of(t) is am
+    t.add_(1)
+    assert ops.amax_of(t) is None                       # an in-place edit voids the bound
+    ops.tag_amax(t, am)
+    assert ops.amax_of(t) is am
+    am.reset()
+    assert ops.amax_of(t) is None                       # so does a reset of the Amax (its parts are about to be rewritten)
+    u = torch.zeros(4)
+    assert ops.tag_amax(u, None) is u and ops.amax_of(u) is None and not hasattr(u, "_lav_amax")
+    # carry: the pooled tensor takes its source's Amax itself, under its own stamp
+    src, out = ops.tag_amax(torch.ones(4), am), torch.ones(2)
+    assert hipnn.carry(out, src) is out and ops.amax_of(out) is ops.amax_of(src) is am
+    src.mul_(2)
+    assert ops.amax_of(src) is None and ops.amax_of(out) is am
+    out.mul_(2)
+    assert ops.amax_of(out) is None
+    assert ops.amax_of(hipnn.carry(torch.ones(2), torch.ones(4))) is None      # nothing to carry from an untagged source
+    # one Amax on two tensors is trusted on both
+    a, b = ops.tag_amax(torch.zeros(3), am), ops.tag_amax(torch.zeros(5), am)
+    assert ops.amax_of(a) is am and ops.amax_of(b) is am
+    # the bound alone, without the stamp tag_amax writes, is not trusted
+    bare = torch.zeros(3)
+    bare._lav_amax = am
+    assert ops.amax_of(bare) is None
