@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 35
+#define LAV_ABI_VERSION 36
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -865,6 +865,34 @@ int lav_debug_view(const unsigned char *rgb, int rgb_h, int rgb_w, const unsigne
                    int text_len, const unsigned char *font, const unsigned char *lut, const int *tables, double x_start, double x_stop,
                    int x_bins, double y_start, double y_stop, int y_bins, int w_rgb, int w_tel, unsigned *counts, unsigned char *out,
                    void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The trainers' visual logs (ABI 36; lav/utils/logger.py: log_bev_info, log_lidar_info, log_seg_info, log_bra_info), composed on the
+ * device from tensors a logged step left in HBM.  Specification: lav_amd.train.log_view.log_view_numpy, bit for bit.  Parity with
+ * matplotlib's rasterisation and figure scaling, its font and imshow's normalisation is UNPINNED (see there).
+ *
+ * panels  DEVICE [npanels <= 8] records of 16 int32: kind, x, y, w, h (the rectangle in the frame; the source has w x h pixels), channels,
+ *         colour (r | g << 8 | b << 16), palette offset, palette entries, bytes per label (1, 4 or 8), source address (low, high word),
+ *         4 unused.  Kinds: 0 image [h][w][3] uint8; 1 labels [h][w] integers, label i + 1 -> palette[offset + i], the rest black;
+ *         2 logits [channels][h][w] float32, np.argmax over the channels (first maximum, a NaN counts as one), then as labels;
+ *         3 planes [channels][h][w] float32, grey floor((m - lo) * 255 / (hi - lo)) of the float64 channel mean m (sum in channel order
+ *         over the count), lo / hi the smallest / largest finite mean of the panel; 0 where hi == lo or m is not finite; 4 the colour.
+ *         A pixel takes the last panel that holds it, black where none does.
+ * prims   DEVICE [nprims] records of 16 int32: kind (0 dot, 1 segment, 2 filled convex polygon), x0, y0, x1, y1, radius, colour, panel,
+ *         x2, y2, x3, y3, vertices (3 or 4; a triangle repeats its last vertex), 3 unused.  Coordinates of the named panel, within
+ *         +-2^20, in drawing order: a pixel takes the last record that covers it, and a record covers pixels of its panel's rectangle
+ *         only.  Dots and segments as lav_debug_view; a polygon covers the pixels of its bounding box for which every int64 edge
+ *         function is >= 0 or every one is <= 0.
+ * text    DEVICE [nrows][text_len] uint8, 7-bit characters; origins DEVICE [nrows][2] int32 (x, y) baseline-left of each row; font
+ *         DEVICE [128][7] uint8, 5 x 7 glyphs, bit 4 the leftmost pixel; glyphs 6 pixels apart, white, clipped to the frame.
+ * palette DEVICE [npalette][3] uint8.  minmax DEVICE workspace of 16 uint64, zeroed here.  out [frame_h][frame_w][3] uint8.
+ * Up to three operations on `stream`: the zeroing, one launch over the planes panels, one over the frame's 32 x 8 tiles.  Sizes and
+ * indices of the tables are checked or clamped on the device; the sources' extents are the caller's word (lav_amd.ops.log_view checks
+ * them against the tensors).
+ */
+int lav_log_view(const void *panels, int npanels, const void *prims, int nprims, const unsigned char *text, const int *origins, int nrows,
+                 int text_len, const unsigned char *font, const unsigned char *palette, int npalette, unsigned long long *minmax,
+                 int frame_h, int frame_w, unsigned char *out, void *stream);
 
 #ifdef __cplusplus
 }

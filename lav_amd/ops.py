@@ -356,6 +356,47 @@ def debug_view(rgb: torch.Tensor, tel_rgb: torch.Tensor, lidar: torch.Tensor, pr
     return out
 
 
+_log_view_font: dict = {}
+
+
+def log_view(panels, prims, text, sources, *, size=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A trainer's log frame on the device (lav_log_view; zeroing, minimum / maximum and compose launches on the current stream):
+    panels, prims and text the host tables of lav_amd.train.log_view (uploaded here in one copy), sources the tensors in HBM the
+    panels name; size = (height, width) of the frame, by default the extent of the panels.  Returns the (height, width, 3) uint8 frame
+    (`out` when given).  Bit-identical to lav_amd.train.log_view.log_view_numpy.  Wrong tables, shapes or dtypes raise ValueError
+    before anything is launched."""
+    from .train import log_view as V
+    sources = list(sources)
+    for i, t in enumerate(sources):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"log_view: source {i} must be a tensor in HBM (cuda/hip device); lav_amd.ops has no CPU path "
+                             "(lav_amd.train.log_view.log_view_numpy is the CPU specification)")
+    panels = V.check_panels(panels, sources)
+    prims, text = V.check_prims(prims, len(panels)), V.check_text(text)
+    shape = V.frame_size(panels, size) + (3,)
+    dev = sources[0].device if sources else (out.device if out is not None else torch.device("cuda", torch.cuda.current_device()))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()):
+        raise ValueError(f"log_view: out must be a contiguous uint8 tensor of shape {shape} in HBM")
+    lib = _lib.load()
+    sources = [t.contiguous() for t in sources]           # (kept alive until the launches are enqueued; the stream orders their reuse)
+    dpanels, palette = V.device_tables(panels, sources, [t.data_ptr() for t in sources])
+    font = _log_view_font.get(dev)
+    if font is None:
+        font = _log_view_font[dev] = torch.from_numpy(V.FONT.copy()).to(dev)
+    # one upload: [panels][primitives][origins][characters][palette], the first three 4-byte aligned by their sizes
+    parts = [dpanels.view(np.uint8).reshape(-1), prims.view(np.uint8).reshape(-1), np.ascontiguousarray(text["origin"]).view(np.uint8).reshape(-1),
+             np.ascontiguousarray(text["chars"]).reshape(-1), palette.reshape(-1)]
+    offs = np.cumsum([0] + [p.size for p in parts])
+    up = torch.from_numpy(np.concatenate(parts + [np.zeros(16, np.uint8)])).to(dev)
+    at = lambda k: up.data_ptr() + int(offs[k])
+    mm = _workspace("log_view", 128, dev)
+    check(lib.lav_log_view(at(0), len(panels), at(1), len(prims), at(3), at(2), len(text), V.TEXT_LEN, _ptr(font), at(4), len(palette),
+                           _ptr(mm), shape[0], shape[1], _ptr(out), _stream()), "lav_log_view")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ GRU decoders
 def gru_cast(embd, w_ih, w_hh, b_ih, b_hh, mlp_w, mlp_b, T: int):
     """embd (B, E); stacked per-command GRU/MLP weights -> (B, num_cmds, T, 2)."""

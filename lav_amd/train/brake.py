@@ -76,6 +76,7 @@ class BrakeTrainer:
         from ..rgb import RGBBrakePredictionModel
         self.cfg, self.device = cfg, torch.device(device)
         self.steps = 0
+        self.log_view = False           # set by the driver around a step whose picture is wanted (--log-dir): train_bra then returns "view"
         ck = checkpoints or {}
         self.bra_model = RGBBrakePredictionModel(BRA_LABELS)
         self.bra_model.load_state_dict(ck.get("bra") or synth.seeded_state_dict(self.bra_model, prefix="bra."))
@@ -113,6 +114,10 @@ class BrakeTrainer:
         self.steps += 1
         loss_v, bra_v, pred_v = torch.stack([loss.detach(), bra[0], pred_bra[0].detach()]).tolist()
         up = lambda a: a.repeat(SEG_SCALE, axis=0).repeat(SEG_SCALE, axis=1)   # nearest x4: the argmax of the upsampled logits
-        return dict(loss=loss_v, rgb1=rgb1[0].permute(1, 2, 0).byte().cpu().numpy(), rgb2=rgb2[0].permute(1, 2, 0).byte().cpu().numpy(),
+        info = dict(loss=loss_v, rgb1=rgb1[0].permute(1, 2, 0).byte().cpu().numpy(), rgb2=rgb2[0].permute(1, 2, 0).byte().cpu().numpy(),
                     bra=bra_v, pred_bra=pred_v, pred_sem1=up(logit1[0].detach().argmax(0).cpu().numpy()),
                     pred_sem2=up(logit2[0].detach().argmax(0).cpu().numpy()))
+        if self.log_view:      # (lav_amd.train.log_view.bra_frame) the logits of sample 0 stay on the device, at the resolution the heads emit
+            info["view"] = dict(rgb1=rgb1[0].permute(1, 2, 0).byte().contiguous(), rgb2=rgb2[0].permute(1, 2, 0).byte().contiguous(), bra=bra_v,
+                                pred_bra=pred_v, pred_sem1=logit1[0].detach().float().contiguous(), pred_sem2=logit2[0].detach().float().contiguous())
+        return info

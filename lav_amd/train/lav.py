@@ -97,6 +97,9 @@ class LAV:
             raise ValueError(f"LAV: unknown stage {what!r} (bev, lidar or seg)")
         self.cfg, self.device, self.what = cfg, torch.device(device), what
         self.steps = 0
+        # set by the driver around a step whose picture is wanted (--log-dir): the step then also returns "view", what
+        # lav_amd.train.log_view's frame builders draw from; the sources of its panels stay in HBM.  Off: nothing is computed or returned
+        self.log_view = False
         ck = checkpoints or {}
         if what == "seg":
             # the camera segmenter alone: ERFNet over 1 + len(seg_channels) classes, Adam(lr) over all of it (lav_privileged_v2.py:29, 45)
@@ -188,7 +191,34 @@ class LAV:
             self.bev_optim.zero_grad()
             loss.backward()
         self.bev_optim.step()
-        return _scalars(loss, terms)
+        info = _scalars(loss, terms)
+        if self.log_view:      # sample 0 as lav_privileged_v2.py:148-159 returns it; the BEV stack stays on the device
+            _, _, _, ego_plan_locs, ego_cast_locs, ego_cast_cmds = out
+            cmd = int(cmds[0])
+            info["view"] = dict(bev=bev[0].contiguous(), cmd=cmd, nxp=self._pixels(nxps[0]), ego_plan_locs=self._pixels(ego_plan_locs[0, -1, cmd]),
+                                ego_cast_locs=self._pixels(ego_cast_locs[0]), ego_cast_cmds=ego_cast_cmds[0].detach().cpu().numpy())
+        return info
+
+    def _pixels(self, locs):
+        """_numpy(locs) * pixels_per_meter + bev_center of the reference's opt_info: float32 metres -> float64 pixels."""
+        return locs.detach().cpu().numpy() * self.cfg.pixels_per_meter + self.bev_center
+
+    def _decode_dets(self, heat, size, ori, apply_sigmoid):
+        """det_inference of the reference (lav_final_v2.py:274-288) on one sample's maps: per class the peaks scored above 0.2 as
+        (x, y, w, h, cos, sin), with its size filter as Python parses it - (class 1 and w < 0.1 ppm) or h < 0.2 ppm.  The peaks come from
+        lav_extract_peaks (7 x 7 maxima, the best 20); the reference's 1e-7 tie-breaking noise on the predicted map is not drawn."""
+        from .. import ops
+        ppm = self.cfg.pixels_per_meter
+        rows = ops.extract_peaks(heat.detach().float(), size.detach().float(), ori.detach().float(), max_det=20, apply_sigmoid=apply_sigmoid).cpu().tolist()
+        dets = []
+        for i, cls in enumerate(rows):
+            det = []
+            for sc, x, y, w, h, cos, sin in cls:
+                if not sc > 0.2 or (i == 1 and w < 0.1 * ppm or h < 0.2 * ppm):
+                    continue
+                det.append((int(x), int(y), w, h, cos, sin))
+            dets.append(det)
+        return dets
 
     def train_seg(self, rgb, sem):
         """One Adam step of the camera segmenter on (B, H, W, 3) uint8 RGB images and (B, H, W) integer labels: pixel-wise
@@ -206,8 +236,11 @@ class LAV:
         loss.backward()
         self.seg_optim.step()
         self.steps += 1
-        return dict(loss=float(loss.detach()), rgb=rgb[0].permute(1, 2, 0).byte().cpu().numpy(), sem=sem[0].cpu().numpy(),
+        info = dict(loss=float(loss.detach()), rgb=rgb[0].permute(1, 2, 0).byte().cpu().numpy(), sem=sem[0].cpu().numpy(),
                     pred_sem=pred_sem[0].detach().cpu().numpy().argmax(0))
+        if self.log_view:      # the logits of sample 0 stay on the device: the frame's kernel takes their argmax
+            info["view"] = dict(rgb=rgb[0].permute(1, 2, 0).byte().contiguous(), sem=sem[0].contiguous(), pred_sem=pred_sem[0].detach().float().contiguous())
+        return info
 
     def train_lidar(self, lidars, num_points, heatmaps, sizemaps, orimaps, bev, ego_locs, cmds, nxps, bras, locs, oris, typs,
                     num_objs):
@@ -230,19 +263,29 @@ class LAV:
         # just-updated weights (~500 small copies), so it runs on the steps that are logged, not on all of them.
         # (round 6: enqueued BEFORE the loss terms are read back - its host work (eval(), the engines' refresh, ~100 launches) then runs
         # while the GPU is still in the backward pass instead of behind an empty queue)
-        log = None
-        if cfg.log_inference and self.steps % max(cfg.log_every, 1) == 0:
-            log = self.mot_inference(lidars[0], num_points[0], cmds[0], nxps[0])
+        log = view = None
+        if self.log_view or cfg.log_inference and self.steps % max(cfg.log_every, 1) == 0:
+            log = self.mot_inference(lidars[0], num_points[0], cmds[0], nxps[0], view=self.log_view)
+            view = log.pop("view", None)
         info = _scalars(loss, terms)
         if log is not None:
             info.update(log)
+        if view is not None:   # the rest of lav_final_v2.py:238-259's opt_info for sample 0; the two BEV stacks stay on the device
+            _, pred_heatmaps, pred_sizemaps, pred_orimaps, pred_bev = lidar_out
+            view.update(det=self._decode_dets(pred_heatmaps[0], pred_sizemaps[0], pred_orimaps[0], True),
+                        gt_det=self._decode_dets(heatmaps[0], sizemaps[0], orimaps[0], False),
+                        bev=bev[0].contiguous(), pred_bev=pred_bev[0].detach().float().contiguous(), cmd=int(cmds[0]), nxp=self._pixels(nxps[0]),
+                        ego_plan_locs=self._pixels(torch.as_tensor(log["ego_plan_locs"])), ego_next_locs=self._pixels(ego_locs[0]),
+                        other_next_locs=self._pixels(locs[0]))
+            info["view"] = view
         self.steps += 1
         return info
 
     @torch.no_grad()
-    def mot_inference(self, lidar, num_point, cmd, nxp):
+    def mot_inference(self, lidar, num_point, cmd, nxp, view=False):
         """One eval-mode inference of sample 0 on the HIP inference kernels, as the reference does every step for its
-        logs (lav_final_v2.py:228-236, 289-321)."""
+        logs (lav_final_v2.py:228-236, 289-321).  view: also return, under "view", the other vehicles' casts (in pixels) and their
+        command scores, which the inference computes either way."""
         from ..model_inference import InferModel  # noqa: F401  (decode rules live there)
         self.student.eval()
         try:
@@ -252,7 +295,10 @@ class LAV:
             rows = ops.extract_peaks(heat[0], size[0], ori[0], apply_sigmoid=True).cpu().tolist()
             det = [(int(x), int(y), w, h, c, s) for sc, x, y, w, h, c, s in rows[1] if sc > 0.2]
             plan, _, other_locs, other_cmds = self.uniplanner.infer(features[0], det, int(cmd), nxp)
-            return dict(ego_plan_locs=plan.cpu().numpy(), num_det=len(det))
+            out = dict(ego_plan_locs=plan.cpu().numpy(), num_det=len(det))
+            if view:
+                out["view"] = dict(other_cast_locs=self._pixels(other_locs), other_cast_cmds=other_cmds.cpu().numpy())
+            return out
         finally:
             self.student.train()
             self.bev_planner.eval()

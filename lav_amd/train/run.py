@@ -11,6 +11,7 @@ from typing import Callable, Optional
 import torch
 import torch.distributed as dist
 
+from . import log_view
 from .brake import BRA_LABELS, BrakeTrainer
 from .lav import LAV, TrainConfig
 from .synthetic import synthetic_bev_batch, synthetic_bra_batch, synthetic_lidar_batch, synthetic_seg_batch
@@ -320,7 +321,7 @@ def main(what):
     the parser to the teardown: the recorded routes under the config's `data_dir` are read by lav_amd.data (every rank its own shard of
     each epoch), one optimiser step per batch, checkpoints every --num-per-save epochs, one JSON summary line.  What this build adds to
     the reference's flags: --synthetic / --steps-per-epoch (seeded synthetic batches instead of a data set), --save-dir, and what the
-    trainer's description (_lav, _SEG, _BRA) names."""
+    trainer's description (_lav, _SEG, _BRA) names, and --log-dir (a picture of sample 0 per logged iteration)."""
     t = {"seg": _SEG, "bra": _BRA}.get(what) or _lav(what)
     ap = argparse.ArgumentParser()
     for flag, kw in (
@@ -335,7 +336,10 @@ def main(what):
             ("--seed", dict(type=int, default=2021)),
             ("--synthetic", dict(action="store_true", help="seeded synthetic batches instead of the config's data_dir")),
             ("--steps-per-epoch", dict(type=int, default=20, help="iterations that make one epoch of synthetic data")),
-            ("--save-dir", dict(default="checkpoints"))):
+            ("--save-dir", dict(default="checkpoints")),
+            ("--log-dir", dict(default=None, metavar="DIR",
+                               help="write the reference's visual log of sample 0 (lav/utils/logger.py) as DIR/{what}_{iteration:07d}.png at every "
+                                    "--num-per-log-th iteration, composed on the device (lav_amd.train.log_view).  Default: none, nothing changes"))):
         for f, k in [(flag, kw)] + t.flags.get(flag, []):
             ap.add_argument(f, **k)
     args = ap.parse_args()
@@ -373,10 +377,18 @@ def main(what):
         for it in range(args.steps_per_epoch):
             yield t.synthetic(args, cfg, per_rank, cfg.seed + 1000003 * epoch + 1009 * it + 100 * rank, device)
 
+    # --log-dir, rank 0: the logged steps also return their "view"; its frame is composed where the tensors are and handed to the writer,
+    # which encodes it when the next one arrives (and at the end) - the step never waits for its own picture
+    writer = log_view.FrameWriter(args.log_dir, what) if args.log_dir and rank == 0 else None
     global_it, t0 = 0, time.perf_counter()
     for epoch in range(args.num_epoch):
         for batch in batches(epoch):
+            drawn = writer is not None and global_it % args.num_per_log == 0
+            trainer.log_view = drawn
             info = step(batch, global_it)
+            if drawn:
+                trainer.log_view = False
+                writer.add(log_view.render(log_view.build_frame(what, info.pop("view"), cfg)), global_it)
             if global_it % args.num_per_log == 0 and rank == 0:
                 print(global_it, t.log(info), flush=True)
             global_it += 1
@@ -388,6 +400,8 @@ def main(what):
                 path = os.path.join(args.save_dir, f"{name}_{epoch + 1}.th")
                 torch.save(trainer.state_dict(name), path)
                 print(f"saved to {path}", flush=True)
+    if writer is not None:
+        writer.close()
     if device.type == "cuda":
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0
