@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 36
+#define LAV_ABI_VERSION 37
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -893,6 +893,42 @@ int lav_debug_view(const unsigned char *rgb, int rgb_h, int rgb_w, const unsigne
 int lav_log_view(const void *panels, int npanels, const void *prims, int nprims, const unsigned char *text, const int *origins, int nrows,
                  int text_len, const unsigned char *font, const unsigned char *palette, int npalette, unsigned long long *minmax,
                  int frame_h, int frame_w, unsigned char *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Open-loop metrics of one evaluated frame (ABI 37; eval_full_v2.py, lav_amd.train.evaluate), ADDED into an int64 accumulator that stays
+ * in HBM: one launch per frame, nothing is copied to the host.  Specification: lav_amd.train.evaluate.eval_frame_numpy, bit for bit -
+ * every counter is an integer and the distance sums add distances already quantised to 2^-20 m, so a route's result does not depend on
+ * any order.  The reference has no evaluator: the definitions are this project's, parity with a reference is UNPINNED.
+ *
+ * The accumulator has 41 + 4 nbins words, as the size function says: frames; seg [3 channels][tp, fp, fn]; n_gt [2 classes];
+ * det [2][tp, fp] at det_score; plan [6 commands][frames, sum of q, final q]; plan_nonfinite; others: matched, unmatched, nonfinite,
+ * sum of the best mode's, of the top mode's, of the top mode's final q; hist [2][tp, fp][nbins].  The size function returns 0 for
+ * nbins outside 1 .. 1024.
+ *
+ * pred_bev [3][h][w] float32 probabilities, labels [3][h][w] uint8 (the first planes of the loaders' BEV stack; non-zero = set), mask
+ *         [h][w] uint8: per channel the pixels with a non-zero mask are counted as pred & label, pred & ~label, ~pred & label,
+ *         pred = pred_bev > threshold.
+ * rows    [2][max_det <= 32][7] as lav_extract_peaks leaves them.  Per class, in order, a row with (double)score > min_score takes the
+ *         nearest free ground-truth actor of its class (squared pixel distance in float64, ties to the lowest index) if that lies within
+ *         radius_px: a true positive, else a false positive; both go to hist bin min(nbins - 1, (int)(score * nbins)) and, where
+ *         (double)score > det_score, to det.  Ground truth: locs [max_objs <= 64][num_plan + 1][2] float32 metres, typs [max_objs]
+ *         int32, the first num_objs of them; pixel = (double)loc * ppm + centre of frame 0, actors outside [0, w) x [0, h) are ignored,
+ *         n_gt counts the others.
+ * ego_plan [num_plan <= 64][2] against ego_locs [num_plan + 1][2] from index 1: q_t = llrint(sqrt(dx^2 + dy^2) * 2^20) in float64; a
+ *         plan with a distance that is not below 2^32 m (NaN, Inf) counts in plan_nonfinite only.  cmd in 0 .. 5.
+ * other_cast [num_others <= max_det][6][num_plan][2], other_cmds [num_others][6], other_row [num_others] int32: the row of class 1
+ *         each forecast came from.  A forecast of a row that took actor g is compared with locs[g] from index 1: S_m the sum of mode m's
+ *         q_t, the best mode's S, the S and the final q of the first maximum of other_cmds (a NaN counts as one); the forecast of a
+ *         false positive (or of a row outside the table) counts as unmatched, one with a non-finite distance as nonfinite.  All three
+ *         may be NULL when num_others is 0.
+ * Workgroups but the last count the segmentation, the last one does the rest; one 64-bit atomic per workgroup and counter.
+ */
+size_t lav_eval_acc_words(int nbins);
+int lav_eval_frame(const float *pred_bev, const unsigned char *labels, const unsigned char *mask, int h, int w, float threshold,
+                   const float *rows, int max_det, const float *locs, const int *typs, int max_objs, int num_objs, int num_plan,
+                   const float *ego_plan, const float *ego_locs, int cmd, const float *other_cast, const float *other_cmds,
+                   const int *other_row, int num_others, double ppm, double centre_x, double centre_y, double radius_px,
+                   double min_score, double det_score, int nbins, long long *acc, void *stream);
 
 #ifdef __cplusplus
 }

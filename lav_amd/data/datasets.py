@@ -159,11 +159,14 @@ class RouteFrames(Dataset):
 
     bev_on_device = False     # True: samples carry a bev_stack.BevRecord where the tuple holds `bev` (rendered behind the upload)
 
-    def __init__(self, config_path, close_txn=False, seed=2021):
+    def __init__(self, config_path, close_txn=False, seed=2021, overrides=None):
+        """overrides: keys set after the YAML's (eval_full_v2 --data-dir: held-out routes under another data_dir)."""
         super().__init__()
         with open(config_path, "r") as f:
             for key, value in yaml.safe_load(f).items():
                 setattr(self, key, value)
+        for key, value in (overrides or {}).items():
+            setattr(self, key, value)
         self.num_frames = 0
         self.txn_map, self.idx_map, self.dir_map = {}, {}, {}
         np.random.seed(seed)

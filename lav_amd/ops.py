@@ -397,6 +397,81 @@ def log_view(panels, prims, text, sources, *, size=None, out: Optional[torch.Ten
     return out
 
 
+def eval_acc_words(nbins: int = 256) -> int:
+    """Length of lav_eval_frame's accumulator (lav_eval_acc_words; host only, no device needed)."""
+    n = int(_lib.load().lav_eval_acc_words(int(nbins)))
+    if n == 0:
+        raise ValueError(f"eval_frame: {nbins} score bins (1 .. 1024)")
+    return n
+
+
+def eval_frame(acc: torch.Tensor, pred_bev: torch.Tensor, bev: torch.Tensor, mask: torch.Tensor, rows: torch.Tensor, locs: torch.Tensor,
+               typs: torch.Tensor, n: int, ego_plan: torch.Tensor, ego_locs: torch.Tensor, cmd: int, other_cast, other_cmds, other_row, *,
+               ppm: float, centre, radius_px: float, threshold: float = 0.5, min_score: float = 0.1, det_score: float = 0.2,
+               nbins: int = 256) -> torch.Tensor:
+    """The open-loop metrics of one frame, ADDED into `acc` (int64, ops.eval_acc_words(nbins) words, in HBM) by one launch on the current
+    stream (lav_eval_frame); nothing comes back to the host.  pred_bev (3, H, W) float32 probabilities; bev (>= 3, H, W) uint8, the
+    loaders' stack, of which the first three planes are the labels; mask (H, W) uint8; rows (2, D <= 32, 7) float32 of extract_peaks;
+    locs (G <= 64, T + 1, 2) float32, typs (G,) int32 and n: the ground truth as the loaders return it; ego_plan (T, 2), ego_locs
+    (T + 1, 2), cmd; other_cast (N, 6, T, 2), other_cmds (N, 6), other_row (N,) int32 - with N = 0 they may be None or empty tensors on
+    any device (UniPlanner.infer_all returns CPU zeros then).  centre = the ego pixel (x, y).  Bit-identical to
+    lav_amd.train.evaluate.eval_frame_numpy, which names the accumulator's slices (ACC).  Wrong shapes, dtypes or devices raise
+    ValueError before anything is launched."""
+    def need(name, t, dtype, shape):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"eval_frame: {name} must be a tensor in HBM (cuda/hip device); lav_amd.ops has no CPU path "
+                             "(lav_amd.train.evaluate.eval_frame_numpy is the CPU specification)")
+        if t.device != acc.device:
+            raise ValueError(f"eval_frame: {name} is on {t.device}, the accumulator on {acc.device}")
+        if t.dtype != dtype or t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
+            raise ValueError(f"eval_frame: {name} must be {dtype} of shape {tuple('*' if s is None else s for s in shape)}, got {t.dtype} {tuple(t.shape)}")
+        return t.contiguous()
+    words = eval_acc_words(nbins)
+    if not isinstance(acc, torch.Tensor) or not acc.is_cuda or acc.dtype != torch.int64 or tuple(acc.shape) != (words,) or not acc.is_contiguous():
+        raise ValueError(f"eval_frame: acc must be a contiguous int64 tensor of {words} words in HBM")
+    pred_bev = need("pred_bev", pred_bev, torch.float32, (3, None, None))
+    H, W = pred_bev.shape[1:]
+    bev = need("bev", bev, torch.uint8, (None, H, W))
+    if bev.shape[0] < 3:
+        raise ValueError(f"eval_frame: bev {tuple(bev.shape)} has fewer than three label planes")
+    mask = need("mask", mask, torch.uint8, (H, W))
+    rows = need("rows", rows, torch.float32, (2, None, 7))
+    D = rows.shape[1]
+    if not 1 <= D <= 32:
+        raise ValueError(f"eval_frame: {D} rows per class (1 .. 32)")
+    locs = need("locs", locs, torch.float32, (None, None, 2))
+    G, T = locs.shape[0], locs.shape[1] - 1
+    if G > 64 or not 1 <= T <= 64:
+        raise ValueError(f"eval_frame: locs {tuple(locs.shape)}: at most 64 actors, 1 .. 64 waypoints")
+    typs = need("typs", typs, torch.int32, (G,))
+    n, cmd = int(n), int(cmd)
+    if not 0 <= n <= G:
+        raise ValueError(f"eval_frame: n = {n} of {G} actors")
+    if not 0 <= cmd < 6:
+        raise ValueError(f"eval_frame: command {cmd} (0 .. 5)")
+    ego_plan = need("ego_plan", ego_plan, torch.float32, (T, 2))
+    ego_locs = need("ego_locs", ego_locs, torch.float32, (T + 1, 2))
+    count = lambda t: 0 if t is None else (t.shape[0] if t.dim() else 1)
+    N = count(other_cast)
+    if count(other_row) != N or count(other_cmds) != N:
+        raise ValueError(f"eval_frame: {count(other_row)} rows and {count(other_cmds)} command scores for {N} forecasts")
+    if N > 0:
+        other_cast = need("other_cast", other_cast, torch.float32, (N, 6, T, 2))
+        other_cmds = need("other_cmds", other_cmds, torch.float32, (N, 6))
+        other_row = need("other_row", other_row, torch.int32, (N,))
+        if N > D or G == 0:
+            raise ValueError(f"eval_frame: {N} forecasts from {D} rows and {G} actors")
+    else:
+        other_cast = other_cmds = other_row = None
+    scalars = [float(ppm), float(centre[0]), float(centre[1]), float(radius_px), float(min_score), float(det_score)]
+    if not all(np.isfinite(scalars)) or not np.isfinite(float(threshold)) or scalars[0] <= 0 or scalars[3] < 0:
+        raise ValueError("eval_frame: scalars must be finite, pixels per metre positive, the radius not negative")
+    check(_lib.load().lav_eval_frame(_ptr(pred_bev), _ptr(bev), _ptr(mask), H, W, float(threshold), _ptr(rows), D, _ptr(locs), _ptr(typs), G, n, T,
+                                     _ptr(ego_plan), _ptr(ego_locs), cmd, _ptr(other_cast), _ptr(other_cmds), _ptr(other_row), N, *scalars,
+                                     int(nbins), _ptr(acc), _stream()), "lav_eval_frame")
+    return acc
+
+
 # ------------------------------------------------------------------------------------------ GRU decoders
 def gru_cast(embd, w_ih, w_hh, b_ih, b_hh, mlp_w, mlp_b, T: int):
     """embd (B, E); stacked per-command GRU/MLP weights -> (B, num_cmds, T, 2)."""
