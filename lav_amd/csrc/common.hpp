@@ -25,40 +25,19 @@ inline int fail(int code, const char *fmt, ...) {
     return code;
 }
 
-// Finite-but-wrong results beside matrix + LDS heavy neighbours (round 4: profiles/r04_plan_stress.txt; resolved in round 5:
-// profiles/r05_coresidency.md, tools/lds_hazard.py).  What round 4 saw: the persistent plan kernel (and, rarely, lav_crop_rotate)
-// returned finite but wrong values whenever waves of a split-operand convolution, an ERFNet pair kernel or a synthetic bf16-matrix +
-// LDS neighbour shared its CUs.  It was taken for an LDS effect (a ds_write2_b64 whose data registers hipcc rewrites right behind it;
-// "more than one LDS operation in flight") and fenced with the helpers below and with LDS claims on the aggressors.  What it is:
-// a packed fp32 instruction (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) with an op_sel bit set - the low result takes the HIGH
-// register of a 64-bit source pair - returns wrong values in lanes 48-63 (the instruction's last pass) while such a neighbour shares
-// the SIMD.  One v_pk_mul_f32 ... op_sel:[0,1] op_sel_hi:[0,0] in a loop, evaluated twice on identical inputs with no memory access
-// at all, disagrees with itself 535 936 times in 1.26e10 beside ERFNet's 16-channel run and never alone; the same instruction without
-// op_sel, every LDS pattern tried (store / load write-after-read on data and address registers, 8 loads in flight, partial waits,
-// ds_write2_b64 with its data overwritten at once, ds_bpermute beside loads) and registers at rest never fail.  hipcc's SLP vectoriser
-// emits the form freely: the old plan kernel held exactly one (its waypoint sum), lav_crop_rotate three.  The library is therefore
+// Packed fp32 with op_sel (profiles/r05_coresidency.md): on gfx950 a v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 with an
+// op_sel bit set - the low result takes the HIGH register of a 64-bit source pair - returns wrong values in lanes 48-63 while waves of
+// a bf16-matrix + LDS heavy kernel share its SIMD, and never alone.  hipcc's SLP vectoriser emits that form freely, so the library is
 // built with -fno-slp-vectorize (lav_amd/build.py), writes the packed instructions it wants by hand with op_sel = 0 (deconv.hip), and
 // tests/test_capi_host.py rejects any packed fp32 instruction with an op_sel bit in the disassembly.
 //
-// The round-4 helpers stay where they are used (they cost nothing): lds_store_fence keeps two 64-bit LDS stores from being merged into
-// a ds_write2_b64 (tools/lds_hazard.py patterns 10 / 11 could not make that instruction fail, alone or beside any neighbour; the CPU
-// test that forbids it is kept as a tripwire, not as a known hazard), lds_commit / lds_keep wait for a wave's LDS stores with the
-// stored values pinned, lds_read_sync / lds_write_sync issue one LDS access at a time (-DLAV_PLAN_LDS_SYNC=1 builds of the old plan
-// kernel: "immune" in round 4 because the changed code no longer contained the packed instruction).
+// Round 4 took those wrong results for an LDS effect; its helpers stay where they are used (they cost nothing): lds_store_fence keeps
+// two 64-bit LDS stores from being merged into a ds_write2_b64 (tools/lds_hazard.py could not make that instruction fail; the CPU test
+// that forbids it is a tripwire, not a known hazard), lds_commit / lds_keep wait for a wave's LDS stores with the stored values pinned.
 __device__ __forceinline__ void lds_store_fence() { asm volatile("" ::: "memory"); }
 __device__ __forceinline__ void lds_commit() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 template <class T>
 __device__ __forceinline__ void lds_keep(T &v) { asm volatile("" : "+v"(v)); }
-__device__ __forceinline__ float lds_read_sync(const float *p) {
-    float v;
-    const unsigned a = (unsigned)(size_t)p;   // (low half of the generic address = the LDS offset)
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory");
-    return v;
-}
-__device__ __forceinline__ void lds_write_sync(float *p, float v) {
-    const unsigned a = (unsigned)(size_t)p;
-    asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" ::"v"(a), "v"(v) : "memory");
-}
 
 // LDS claims (round 4's fence, an opt-in since round 5): LAV_LDS_EXCLUSIVE=1 makes the split-operand convolutions and the ERFNet pair
 // kernels ask for all of their CU's LDS (half each where two workgroups share a CU), so that no kernel that uses LDS runs beside them;

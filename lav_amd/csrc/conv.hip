@@ -872,7 +872,7 @@ Choice decide(const lav_conv &c, const Plan &p, double tile_cost, double tile_ra
     }
     // LAV_CONV_F16X3: wherever the split kernel runs the layer (round 5: the head convolution's plan only); on the fp32 kernels the
     // precision means nothing
-    ch.sp.f16 = ch.kind == 2 && resolve_precision(c) == LAV_CONV_F16X3 && f16x3_layer(c, p) && !ch.sp.sk_w ? 1 : 0;
+    ch.sp.f16 = ch.kind == 2 && resolve_precision(c) == LAV_CONV_F16X3 && f16x3_layer(c, p) ? 1 : 0;
     if (smallcin_applies(c)) ch.kind = 3;   // camera stems: K = 3 x taps on packed fp32 FMAs (conv_smallcin.hpp)
     static const bool dbg = getenv("LAV_CONV_PLAN_DEBUG") != nullptr;
     if (dbg)
@@ -904,7 +904,7 @@ extern "C" int lav_conv_tile_info(const lav_conv *c, int *info) {
     }
     if (ch.kind == 2) {   // split kernel: info[0] = -1, then MP, MC, pixel waves, tile width (0 = linearised), LDS, split-K, tap group, tile rows
         info[0] = -1; info[1] = ch.sp.MP; info[2] = ch.sp.MC; info[3] = ch.sp.WPX; info[4] = ch.sp.tw; info[5] = (int)ch.sp.lds;
-        info[6] = ch.sp.sk_w ? -ch.sp.sk_w : ch.sp.ksplit; info[7] = ch.sp.tap_group + 100 * ch.sp.tp + 200 * ch.sp.f16; info[8] = ch.sp.th;   // (tap group + 100 in tap-pair mode; split-K < 0: stream-K over that many workgroups)
+        info[6] = ch.sp.ksplit; info[7] = ch.sp.tap_group + 100 * ch.sp.tp + 200 * ch.sp.f16; info[8] = ch.sp.th;   // (tap group + 100 in tap-pair mode, + 200 on the f16x3 kernel)
         return LAV_OK;
     }
     if (ch.kind == 1) {   // direct path: info[0] = 0, info[1] = waves per workgroup
@@ -1208,7 +1208,7 @@ extern "C" size_t lav_conv_workspace_bytes(const lav_conv *c) {
     if (ch.kind == 1) a.ksplit = ch.dp.ksplit;
     if (ch.kind == 2) a.ksplit = ch.sp.ksplit;
     if (ch.kind == 3) return 0;
-    const int slabs = ch.kind == 2 && ch.sp.sk_w ? 2 : (a.ksplit > 1 ? a.ksplit : 0);   // stream-K: head and tail parts of the cut tiles
+    const int slabs = a.ksplit > 1 ? a.ksplit : 0;
     // LAV_CONV_F16X3: F16_PARTS floats behind the slabs for the launch that measures x when no producer maxima are handed in
     return (size_t)slabs * c->batch * c->cout * p.OH * p.OW * sizeof(float) + (ch.kind == 2 && ch.sp.f16 ? (size_t)F16_PARTS * sizeof(float) : 0);
 }
@@ -1220,7 +1220,7 @@ struct AmaxPlan { int count; bool in_kernel; };
 AmaxPlan amax_plan(const lav_conv &c, const Plan &p, const Choice &ch, int tiled_ksplit) {
     const long reduce_blocks = ((long)c.batch * c.cout * p.OH * p.OW + 255) / 256;
     long n = 0;
-    if (ch.kind == 2 && !ch.sp.sk_w) {
+    if (ch.kind == 2) {
         const int NBLK = (4 / ch.sp.WPX) * ch.sp.MC;
         n = ch.sp.ksplit > 1 ? reduce_blocks : (long)((c.cout + NBLK * 32 - 1) / (NBLK * 32)) * ch.sp.tiles * c.batch * p.nclasses;
     } else if (ch.kind == 1) {
@@ -1280,7 +1280,7 @@ extern "C" int lav_conv2d_amax(const lav_conv *c, const float *x, const float *w
     const bool direct = ch.kind == 1;
     if (direct) a.ksplit = dp.ksplit;
     if (ch.kind == 2) a.ksplit = ch.sp.ksplit;
-    const int slabs = ch.kind == 2 && ch.sp.sk_w ? 2 : (a.ksplit > 1 ? a.ksplit : 0);
+    const int slabs = a.ksplit > 1 ? a.ksplit : 0;
     const size_t slab_bytes = (size_t)slabs * c->batch * c->cout * p.OH * p.OW * sizeof(float);
     AmaxIO io{amax_in, amax_in_count, nullptr, nullptr};
     if (ch.kind == 2 && ch.sp.f16 && !amax_in) {   // the launch that measures x writes behind the slabs

@@ -27,8 +27,8 @@ __global__ __launch_bounds__(512) void k_conv_split_f16(SplitArgs a) {
     const int cls = (blockIdx.z / a.ksplit) % a.nclasses, n = blockIdx.z / (a.ksplit * a.nclasses);
     const int nchunks_k = TP ? 2 * a.nchunks : a.nchunks;
     const long wg = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    split_body<MP, MC, WPX, NT, G, TP, false, true>(a, smem_raw, blockIdx.x, blockIdx.y, cls, n, gridDim.z / (a.ksplit * a.nclasses), ks * nchunks_k / a.ksplit,
-                                                    (ks + 1) * nchunks_k / a.ksplit, a.ksplit > 1 ? ks : -1, wg);
+    split_body<MP, MC, WPX, NT, G, TP, true>(a, smem_raw, blockIdx.x, blockIdx.y, cls, n, gridDim.z / (a.ksplit * a.nclasses), ks * nchunks_k / a.ksplit,
+                                             (ks + 1) * nchunks_k / a.ksplit, a.ksplit > 1 ? ks : -1, wg);
 }
 
 // workgroup g writes the largest FINITE |x| of its share of the layer's input channels to parts[g] (no atomics, nothing to zero);

@@ -28,72 +28,12 @@ __global__ __launch_bounds__(512) void k_conv_split(SplitArgs a) {
     const int cls = (blockIdx.z / a.ksplit) % a.nclasses, n = blockIdx.z / (a.ksplit * a.nclasses);
     const int nchunks_k = TP ? 2 * a.nchunks : a.nchunks;
     const long wg = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    split_body<MP, MC, WPX, NT, G, TP, false>(a, smem_raw, blockIdx.x, blockIdx.y, cls, n, gridDim.z / (a.ksplit * a.nclasses), ks * nchunks_k / a.ksplit,
-                                              (ks + 1) * nchunks_k / a.ksplit, a.ksplit > 1 ? ks : -1, wg);
+    split_body<MP, MC, WPX, NT, G, TP>(a, smem_raw, blockIdx.x, blockIdx.y, cls, n, gridDim.z / (a.ksplit * a.nclasses), ks * nchunks_k / a.ksplit,
+                                       (ks + 1) * nchunks_k / a.ksplit, a.ksplit > 1 ? ks : -1, wg);
 }
 
 // LAV_CONV_F16X3: the same body on two fp16 pieces per operand and three products lives in conv_f16.hip (k_conv_split_f16, k_absmax_parts).
-// Stream-K launch of a single-image, single-class layer (round 5).  The head convolution's 400 tiles ran as two rounds of a 256-CU
-// chip with the second round 56 % full (0.78 of the tile time wasted).  Here W persistent workgroups (one per CU) share
-// the layer's U = tiles x chunks units of K work evenly: workgroup i takes units [i U / W, (i + 1) U / W) of the linear order (tile,
-// chunk), i.e. the tail of one tile, whole tiles, and the head of another.  With U / W >= chunks per tile a tile is cut at most once:
-// its head part (chunks [0, c)) goes to slab 0 of a.partial, its tail part to slab 1, and k_conv_sk_fixup adds the two in that order
-// and applies the epilogue - fixed cuts, fixed order: bit-reproducible.  Whole tiles take the ordinary epilogue.
-template <int MP, int MC, int WPX, int NT, int G>
-__global__ __launch_bounds__(512) void k_conv_split_sk(SplitArgs a, int nbx, int ntiles) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int nck = a.nchunks;
-    const long U = (long)ntiles * nck;
-    const int W = gridDim.x, npx = ntiles / nbx;
-    // The tiles are ordered cout tile first (tile = bx * npx + by), and the workgroups of one XCD (workgroup b is dispatched to XCD b % 8)
-    // take neighbouring ranges of that order: an XCD's L2 then streams the weights of ONE cout tile (2.6 MB of the head convolution's
-    // 5.3 MB; both do not fit its 4 MB - the first version, workgroup b on range b, was slower than whole tiles).
-    int j = blockIdx.x;
-    if (8 % nbx == 0 && W % 8 == 0) {
-        const int x = blockIdx.x & 7, slot = blockIdx.x >> 3;
-        j = (x % nbx) * (W / nbx) + (x / nbx) * (W / 8) + slot;
-    }
-    long u = (long)j * U / W;
-    const long u1 = (long)(j + 1) * U / W;
-    while (u < u1) {
-        const int tile = (int)(u / nck), c_lo = (int)(u - (long)tile * nck);
-        const int c_hi = (int)(u1 - u < (long)(nck - c_lo) ? c_lo + (u1 - u) : nck);
-        const int part = c_lo == 0 && c_hi == nck ? -1 : (c_lo == 0 ? 0 : 1);
-        split_body<MP, MC, WPX, NT, G, false, true>(a, smem_raw, tile / npx, tile % npx, 0, 0, 1, c_lo, c_hi, part, 0);
-        u += c_hi - c_lo;
-    }
-}
-
-struct SkFixupArgs {
-    const float *partial, *bias, *scale, *shift, *res;
-    const int *n_valid;
-    float *y;
-    int cout, out_c_total, out_c_offset, OH, OW;
-    int tw, th, tiles_x, couts_per_tile, nbx, nck, ntiles, W;
-    int relu_pre, relu_post, sigmoid;
-};
-// y = epilogue(slab 0 + slab 1) for the outputs of the tiles that k_conv_split_sk cut (the same arithmetic as k_conv_reduce)
-__global__ __launch_bounds__(256) void k_conv_sk_fixup(SkFixupArgs a) {
-    const long plane_o = (long)a.OH * a.OW, total = (long)a.cout * plane_o;
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
-    if (a.n_valid && *a.n_valid < 1) return;
-    const int co = (int)(e / plane_o);
-    const int pix = (int)(e - (long)co * plane_o), oy = pix / a.OW, ox = pix - oy * a.OW;
-    const int tile = (co / a.couts_per_tile) * (a.ntiles / a.nbx) + (oy / a.th) * a.tiles_x + ox / a.tw;
-    const long U = (long)a.ntiles * a.nck, lo = (long)tile * a.nck;
-    const long i0 = lo * a.W / U + 1, b = i0 * U / a.W;   // the first workgroup boundary past the tile's first unit
-    if (!(i0 < a.W && b > lo && b < lo + a.nck)) return;  // the tile was not cut
-    float v = a.partial[e] + a.partial[total + e];
-    if (a.bias) v += a.bias[co];
-    if (a.relu_pre) v = v > 0.f ? v : 0.f;
-    if (a.scale) v = fmaf(v, a.scale[co], a.shift[co]);
-    const long idx = ((long)a.out_c_offset + co) * plane_o + pix;
-    if (a.res) v += a.res[idx];
-    if (a.relu_post) v = v > 0.f ? v : 0.f;
-    if (a.sigmoid && co >= a.sigmoid - 1) v = 1.f / (1.f + expf(-v));
-    a.y[idx] = v;
-}
+// A stream-K launch of the head convolution (round 5, no faster on this power-bound chip) is kept as tools/probes/split_stream_k_r5.diff.
 
 // ------------------------------------------------------------------------------------------------ host side
 // bytes of the split packed weights of one plan
@@ -185,7 +125,6 @@ struct SplitPlan {
     size_t lds;
     double cost;
     int tp;   // tap-pair mode (k_conv_split<..., TP = true>)
-    int sk_w; // > 0: stream-K launch with this many persistent workgroups (k_conv_split_sk)
     int f16;  // LAV_CONV_F16X3 applies: two fp16 pieces per operand, three products (k_conv_split_f16)
 };
 
@@ -275,21 +214,6 @@ inline SplitPlan choose_split(const lav_conv &c, const Plan &p) {
             }
         }
     }
-    // Stream-K (k_conv_split_sk) where whole-tile rounds waste a large part of the chip: a single image, one class, the 2x2/w2 G = 2
-    // kernel (the head convolution: 400 tiles on 256 CUs = two rounds, the second 56 % full), at least one tile's worth of K per
-    // workgroup (a tile is then cut at most once).  OPT-IN (LAV_SPLIT_SK=1, read at every plan): measured no faster than whole tiles -
-    // 282 vs 281 us on the head convolution, with and without the XCD-aware order - because the chip is POWER bound under this kernel
-    // (tools/clock_probe.py: 1330 W of the 1400 W socket limit at 2.11 GHz; the half-empty second round of whole tiles simply runs at a
-    // higher clock), so evening out the work buys nothing.  Kept for parts / clocks where it is not (profiles/r05_clock_power.txt).
-    const char *sk_env = getenv("LAV_SPLIT_SK");
-    const bool sk_on = sk_env && atoi(sk_env) != 0;
-    if (sk_on && best.ok && !best.tp && best.MP == 2 && best.MC == 2 && best.WPX == 2 && best.tap_group == 2 && best.ksplit == 1 && best.tw > 0 &&
-        c.batch == 1 && p.nclasses == 1 && ncu == 256 && !(c.target_cus >= 16 && c.target_cus < 256)) {
-        const int NBLK = (4 / best.WPX) * best.MC;
-        const long wgs = (long)best.tiles * ((c.cout + NBLK * 32 - 1) / (NBLK * 32));
-        const long rounds = (wgs + ncu - 1) / ncu;
-        if (wgs > ncu && rounds * ncu * 100 >= wgs * 115 && rounds <= 4) best.sk_w = (int)ncu;
-    }
     return best;
 }
 
@@ -371,9 +295,8 @@ inline int launch_split(const lav_conv &c, const Plan &p, const SplitPlan &sp, c
     dim3 grid((c.cout + NBLK * 32 - 1) / (NBLK * 32), sp.tiles, c.batch * p.nclasses * sp.ksplit);
     const int tok = timer_begin("conv2d", st);
     int rc = LAV_EINVAL;
-    // the workgroups' output maxima come from the kernel's epilogue (whole-K launches) or from k_conv_reduce (split-K); the stream-K
-    // launch has neither (lav_conv2d measures its output with a launch)
-    s.amax_out = sp.ksplit == 1 && !sp.sk_w ? io.out : nullptr;
+    // the workgroups' output maxima come from the kernel's epilogue (whole-K launches) or from k_conv_reduce (split-K)
+    s.amax_out = sp.ksplit == 1 ? io.out : nullptr;
     s.sync_off = (int)((sp.lds + 15) / 16 * 16);
     auto print_trace = [&]() {
         static int runs = 0;
@@ -441,29 +364,6 @@ inline int launch_split(const lav_conv &c, const Plan &p, const SplitPlan &sp, c
         timer_end(tok, st);
         LAV_LAUNCH_CHECK();
         print_trace();
-        return LAV_OK;
-    }
-    if (sp.sk_w) {
-        const size_t lds_sk = sp.lds;
-        const int nbx = (int)grid.x, ntiles = (int)(grid.x * grid.y);
-        const bool small = s.plane <= SPLIT_LOADERS * 2;
-        static bool attr = false;
-        if (!attr) {
-            LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_split_sk<2, 2, 2, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_split_sk<2, 2, 2, SPLIT_NT, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr = true;
-        }
-        if (small) hipLaunchKernelGGL((k_conv_split_sk<2, 2, 2, 2, 2>), dim3(sp.sk_w), dim3(512), lds_sk, st, s, nbx, ntiles);
-        else hipLaunchKernelGGL((k_conv_split_sk<2, 2, 2, SPLIT_NT, 2>), dim3(sp.sk_w), dim3(512), lds_sk, st, s, nbx, ntiles);
-        SkFixupArgs f;
-        f.partial = a.partial; f.bias = a.bias; f.scale = a.scale; f.shift = a.shift; f.res = a.res; f.n_valid = a.n_valid; f.y = a.y;
-        f.cout = a.cout; f.out_c_total = a.out_c_total; f.out_c_offset = a.out_c_offset; f.OH = a.OH; f.OW = a.OW;
-        f.tw = sp.tw; f.th = sp.th; f.tiles_x = sp.tiles_x; f.couts_per_tile = NBLK * 32; f.nbx = nbx; f.nck = s.nchunks; f.ntiles = ntiles; f.W = sp.sk_w;
-        f.relu_pre = a.relu_pre; f.relu_post = a.relu_post; f.sigmoid = a.sigmoid;
-        const long total = (long)a.cout * p.OH * p.OW;
-        hipLaunchKernelGGL(k_conv_sk_fixup, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, f);
-        timer_end(tok, st);
-        LAV_LAUNCH_CHECK();
         return LAV_OK;
     }
     if (sp.tp) {

@@ -75,10 +75,8 @@ struct SplitOps {
 // its 16 bytes from tap 2p + h, channel half (chunk & 1) of the ordinary layout; the odd tap out (49 = 24 pairs + 1) is
 // zeroed on its way into LDS.  A chunk is 8 channels, a step one tap pair.
 // The work of one workgroup on one tile: pixel tile `by`, cout tile `bx`, class `cls`, image `n`, chunks [chunk_lo, chunk_hi) of the K
-// loop; part < 0: the tile's whole K range, epilogue applied and written to y; part >= 0: raw partial sums into slab `part` of
-// a.partial.  SK (stream-K, k_conv_split_sk): the function is called for one segment after the other - every role ends on one more
-// LDS barrier, so that the loaders enter the next segment while the compute waves write this one out.
-template <int MP, int MC, int WPX, int NT, int G, bool TP, bool SK, bool F16 = false>
+// loop; part < 0: the tile's whole K range, epilogue applied and written to y; part >= 0: raw partial sums into slab `part` of a.partial.
+template <int MP, int MC, int WPX, int NT, int G, bool TP, bool F16 = false>
 __device__ __forceinline__ void split_body(const SplitArgs &a, unsigned char *smem_raw, const int bx, const int by, const int cls, const int n, const int batch,
                                            const int chunk_lo, const int chunk_hi, const int part, const long wg) {
     constexpr int WCO = 4 / WPX, NBLK = WCO * MC, PIXW = WPX * MP * 32;
@@ -214,7 +212,6 @@ __device__ __forceinline__ void split_body(const SplitArgs &a, unsigned char *sm
             }
         }
         if (a.trace && tid == 256) a.trace[wg * 8 + 7] = waited;
-        if constexpr (SK) lds_barrier();
         return;
     }
     if (wid >= 6) {
@@ -316,7 +313,6 @@ __device__ __forceinline__ void split_body(const SplitArgs &a, unsigned char *sm
         }
         for (int k = ngroups; k < ngroups_pad; ++k) lds_barrier();
         if (a.trace && tid == 384) { a.trace[wg * 8 + 5] = conv; a.trace[wg * 8 + 6] = waited; }
-        if constexpr (SK) lds_barrier();
         return;
     }
     // -------------------------------------------------------------------------------------- compute waves
@@ -430,7 +426,6 @@ __device__ __forceinline__ void split_body(const SplitArgs &a, unsigned char *sm
         }
         for (; bars < ngroups_pad; ++bars) lds_barrier();
     }
-    if constexpr (SK) lds_barrier();   // the LDS of this segment is free: the loaders go on to the next one
     if (a.trace && tid == 0) { a.trace[wg * 8 + 2] = clock64(); a.trace[wg * 8 + 4] = waited; }
 
     // -------------------------------------------------------------------------------------- epilogue (as k_conv)

@@ -51,8 +51,6 @@ __device__ __forceinline__ float row_allsum(float x) {   // xor butterfly 8, 4, 
     x = dpp_add<0x121>(x);   // row_ror:1
     return x;
 }
-// the xor butterfly 32, 16, 8, 4, 2, 1 of one value on those instructions: bit-identical to wave_sum (fp addition is commutative)
-__device__ __forceinline__ float wave_sum_valu(float v) { return row_allsum(fold16(fold32(v, v), fold32(v, v))); }
 
 // ------------------------------------------------------------------------------------------------- cast
 // H = 64 fixed by the register layout (one W_hh row of 64 floats per thread, 3H = 192 threads)
@@ -386,294 +384,19 @@ __global__ __launch_bounds__(256) void k_plan_poison(const int *__restrict__ sta
 // kernel, [2] 1 + workgroup / [3] wave / [4] epoch of the FIRST wave that gave up, [5] its spin count, [6] the granule index
 // it was waiting for, [7] the tag it last saw there, [8] microseconds between its kernel entry and the abort, [9] workgroups
 // that ran to completion.  The words are cleared with the granule tags at every launch.
-// POLL = 0: every wave sweeps all R*H granules itself (rounds 1-3).  POLL = 1 (H a multiple of 256): a wave polls only its quarter
-// of the state and the four quarters meet in LDS - a quarter of the polling traffic per workgroup (the chip's other streams pay
-// for every poll: MI355X guide, "polling-cost"), two loads instead of eight per lane and poll round.
-// -DLAV_PLAN_LDS_SYNC=1: every LDS access of the persistent kernel one at a time, instruction + wait in one asm block - the build that
-// was immune to matrix + LDS heavy neighbours on its CUs in round 4 (+60 us per plan).  Round 5 found the real cause of those wrong
-// results - packed fp32 instructions with an op_sel bit, not LDS (common.hpp) - removed them from the library and moved the
-// frame to k_plan_wave, which has no LDS at all; this kernel and the switch stay as the known victim for tools/coresidency.py.
-#ifndef LAV_PLAN_LDS_SYNC
-#define LAV_PLAN_LDS_SYNC 0
-#endif
-// -DLAV_PLAN_VARIANT=bits: experiments on this kernel as the known victim (tools/plan_variants.sh, profiles/r05_coresidency.md):
-// 1 no s_sleep between poll rounds, 2 the wave sums on v_permlane swaps + DPP instead of ds_bpermute_b32 (no DS instruction but the
-// kernel's own LDS reads and writes), 4 abort flag read once per step instead of three times.
-#ifndef LAV_PLAN_VARIANT
-#define LAV_PLAN_VARIANT 0
-#endif
-#if LAV_PLAN_LDS_SYNC
-#define LDSR(x) lav::lds_read_sync(&(x))
-#define LDSW(x, v) lav::lds_write_sync(&(x), (v))
-#else
-#define LDSR(x) (x)
-#define LDSW(x, v) ((x) = (v))
-#endif
-template <int POLL, int RC>   // RC: state rows held per register pass (1 for the frame's single commanded branch, else RC)
-__global__ __launch_bounds__(256) void k_plan_persistent(PlanArgs a, unsigned long long *__restrict__ gran, int *__restrict__ status,
-                                                         long long spin_limit) {
-    const int H = a.H, T = a.T, R = a.R;
-    const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nk = H / 64;
-    const unsigned long long t_entry = wall_clock64();
-    if (tid == 0) atomicAdd(status + 1, 1);
-    __shared__ float gh_s[3 * PLAN_UNITS][RC];
-    __shared__ float loc_s[2][RC][64][2];
-    __shared__ float run_s[RC][2];
-    __shared__ int abort_s;
-    __shared__ float h_s[POLL ? RC : 1][POLL ? 64 * PLAN_MAXK : 1];
-    const int j0 = blockIdx.x * PLAN_UNITS;
-    float w[6][PLAN_MAXK], bh[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-        const int lr = wid * 6 + q;
-        const int row = (lr / PLAN_UNITS) * H + j0 + (lr % PLAN_UNITS);
-        const float *wr = a.w_hh + (long)row * H;
-#pragma unroll
-        for (int i = 0; i < PLAN_MAXK; ++i) w[q][i] = i < nk ? wr[lane + 64 * i] : 0.f;
-        bh[q] = a.b_hh[row];
-    }
-    float m0[PLAN_MAXK], m1[PLAN_MAXK];
-#pragma unroll
-    for (int i = 0; i < PLAN_MAXK; ++i) {
-        m0[i] = i < nk ? a.mlp_w[lane + 64 * i] : 0.f;
-        m1[i] = i < nk ? a.mlp_w[H + lane + 64 * i] : 0.f;
-    }
-    for (int e = tid; e < R * T; e += 256) {  // iteration 0 refines the cast waypoints
-        const int r = e / T, t = e - r * T;
-        int b, ci, c;
-        row_decode(a, r, b, ci, c);
-        const float *src = a.cast_locs + (((long)b * a.num_cmds + c) * T + t) * 2;
-        float l0 = src[0], l1 = src[1];
-        LDSW(loc_s[0][r][t][0], l0);
-        LDSW(loc_s[0][r][t][1], l1);
-        lav::lds_commit();
-        lav::lds_keep(l0); lav::lds_keep(l1);
-    }
-    if (tid == 0) abort_s = 0;
-    // this thread's gate job (tid < 8*R): unit u of state row rr
-    const int gu = tid % PLAN_UNITS, grr = tid / PLAN_UNITS;
-    const bool gate_thread = tid < PLAN_UNITS * R;
-    int gb = 0, gci = 0, gc = 0;
-    if (gate_thread) row_decode(a, grr, gb, gci, gc);
-    float wih[3][4], bih[3];
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-        const int row = g * H + j0 + gu;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) wih[g][k] = a.w_ih[row * 4 + k];
-        bih[g] = a.b_ih[row];
-    }
-    const float u0 = gate_thread ? a.nxp[gb * 2 + 0] * a.ppm / a.crop * 2.f - 1.f : 0.f;
-    const float u1 = gate_thread ? a.nxp[gb * 2 + 1] * a.ppm / a.crop * 2.f - 1.f : 0.f;
-    float hself = 0.f;
-    __syncthreads();
-
-    int cur = 0;
-    for (int it = 0; it < a.iters; ++it) {
-        if (tid < R * 2) LDSW(run_s[tid >> 1][tid & 1], 0.f);
-        for (int t = 0; t <= T; ++t) {  // t == T only gathers h_{T-1} to finish the iteration's waypoints
-            const unsigned epoch = (unsigned)(it * T + t);  // the state published by the previous step carries this tag
-            float hv[RC][PLAN_MAXK];
-            if (t == 0) {
-#pragma unroll
-                for (int rr = 0; rr < RC; ++rr) {
-                    int b, ci, c;
-                    row_decode(a, min(rr, R - 1), b, ci, c);
-#pragma unroll
-                    for (int i = 0; i < PLAN_MAXK; ++i) hv[rr][i] = i < nk ? a.embd[(long)b * H + lane + 64 * i] : 0.f;
-                }
-            } else {
-                const unsigned long long *g = gran + (long)((epoch - 1) & 1) * R * H;
-                long long spins = 0;
-                bool ok;
-                constexpr int NP = POLL ? PLAN_MAXK / 4 : PLAN_MAXK;   // granules per lane and row in one poll round
-                const int np = POLL ? nk / 4 : nk;
-                const int base = POLL ? wid * (H / 4) : 0;              // first unit of this wave's share
-                float pv[RC][NP];
-                do {
-                    ok = true;
-#pragma unroll
-                    for (int rr = 0; rr < RC; ++rr) {
-                        if (rr < R) {
-#pragma unroll
-                            for (int i = 0; i < NP; ++i) {
-                                if (i < np) {
-                                    const unsigned long long x = __hip_atomic_load(g + (long)rr * H + base + lane + 64 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                    ok = ok && (unsigned)(x >> 32) == epoch;
-                                    pv[rr][i] = __uint_as_float((unsigned)x);
-                                }
-                            }
-                        }
-                    }
-                    const unsigned long long bad = __ballot(!ok);
-                    ok = bad == 0;
-                    if (!ok) {
-                        if (++spins > spin_limit || *(volatile int *)&abort_s) {
-                            abort_s = 1;
-                            if (lane == (int)__builtin_ctzll(bad)) {
-                                atomicExch(status, 1);
-                                if (atomicCAS(status + 2, 0, (int)blockIdx.x + 1) == 0) {   // the first wave of the grid to give up
-                                    int bi = 0;
-                                    unsigned bt = 0;
-                                    for (int rr = R - 1; rr >= 0; --rr)
-                                        for (int i = np - 1; i >= 0; --i) {
-                                            const unsigned long long x = __hip_atomic_load(g + (long)rr * H + base + lane + 64 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                            if ((unsigned)(x >> 32) != epoch) { bi = rr * H + base + lane + 64 * i; bt = (unsigned)(x >> 32); }
-                                        }
-                                    status[3] = wid; status[4] = (int)epoch; status[5] = (int)min(spins, 0x7fffffffll);
-                                    status[6] = bi; status[7] = (int)bt;
-                                    status[8] = (int)((wall_clock64() - t_entry) / 100);   // 100 MHz constant clock
-                                }
-                            }
-                            break;
-                        }
-                        if (!(LAV_PLAN_VARIANT & 1)) __builtin_amdgcn_s_sleep(2);
-                    }
-                } while (!ok);
-                if constexpr (POLL) {   // the four quarters meet in LDS (also the rendezvous of an abort: every wave leaves together)
-#pragma unroll
-                    for (int rr = 0; rr < RC; ++rr)
-                        if (rr < R) {
-#pragma unroll
-                            for (int i = 0; i < NP; ++i)
-                                if (i < np) LDSW(h_s[rr][base + lane + 64 * i], pv[rr][i]);
-                        }
-                    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#pragma unroll
-                    for (int rr = 0; rr < RC; ++rr)
-#pragma unroll
-                        for (int i = 0; i < NP; ++i) lav::lds_keep(pv[rr][i]);   // (common.hpp: pinned until the stores have left)
-                    if (*(volatile int *)&abort_s) return;
-#pragma unroll
-                    for (int rr = 0; rr < RC; ++rr)
-                        if (rr < R) {
-#pragma unroll
-                            for (int i = 0; i < PLAN_MAXK; ++i) hv[rr][i] = i < nk ? LDSR(h_s[rr][lane + 64 * i]) : 0.f;
-                        }
-                } else {
-#pragma unroll
-                    for (int rr = 0; rr < RC; ++rr)
-#pragma unroll
-                        for (int i = 0; i < NP; ++i) hv[rr][i] = pv[rr][i];
-                }
-                if (*(volatile int *)&abort_s) return;   // give up: never hang the device (k_plan_poison, next on the stream, voids the output)
-                // waypoint t-1 of this iteration from h_{t-1} (every workgroup needs it as next iteration's input)
-                if (wid == 0) {
-#pragma unroll
-                    for (int rr = 0; rr < RC; ++rr) {
-                        if (rr < R) {
-                            float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-                            for (int i = 0; i < PLAN_MAXK; ++i) {
-                                s0 = fmaf(m0[i], hv[rr][i], s0);
-                                s1 = fmaf(m1[i], hv[rr][i], s1);
-                            }
-                            if (LAV_PLAN_VARIANT & 2) {
-                                s0 = wave_sum_valu(s0);
-                                s1 = wave_sum_valu(s1);
-                            } else {
-#pragma unroll
-                                for (int d = 32; d >= 1; d >>= 1) {
-                                    s0 += __shfl_xor(s0, d, 64);
-                                    s1 += __shfl_xor(s1, d, 64);
-                                }
-                            }
-                            if (lane == 0) {
-                                float r0 = LDSR(run_s[rr][0]) + (s0 + a.mlp_b[0]), r1 = LDSR(run_s[rr][1]) + (s1 + a.mlp_b[1]);
-                                float o0 = r0 + LDSR(loc_s[cur][rr][t - 1][0]), o1 = r1 + LDSR(loc_s[cur][rr][t - 1][1]);
-                                LDSW(run_s[rr][0], r0);
-                                LDSW(run_s[rr][1], r1);
-                                LDSW(loc_s[cur ^ 1][rr][t - 1][0], o0);
-                                LDSW(loc_s[cur ^ 1][rr][t - 1][1], o1);
-                                lav::lds_commit();   // (common.hpp)
-                                lav::lds_keep(r0); lav::lds_keep(r1); lav::lds_keep(o0); lav::lds_keep(o1);
-                                if (blockIdx.x == 0) {
-                                    int b, ci, c;
-                                    row_decode(a, rr, b, ci, c);
-                                    float *o = a.out + ((((long)b * a.iters + it) * a.NC + ci) * T + (t - 1)) * 2;
-                                    o[0] = o0;
-                                    o[1] = o1;
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            if (t == T) break;
-#pragma unroll
-            for (int rr = 0; rr < RC; ++rr) {
-                if (rr < R) {
-                    float acc[6];
-#pragma unroll
-                    for (int q = 0; q < 6; ++q) {
-                        acc[q] = 0.f;
-#pragma unroll
-                        for (int i = 0; i < PLAN_MAXK; ++i) acc[q] = fmaf(w[q][i], hv[rr][i], acc[q]);
-                    }
-                    if (LAV_PLAN_VARIANT & 2) {
-#pragma unroll
-                        for (int q = 0; q < 6; ++q) acc[q] = wave_sum_valu(acc[q]);
-                    } else {
-#pragma unroll
-                        for (int d = 32; d >= 1; d >>= 1)
-#pragma unroll
-                            for (int q = 0; q < 6; ++q) acc[q] += __shfl_xor(acc[q], d, 64);
-                    }
-                    if (lane == 0) {
-                        {   // committed LDS stores (common.hpp: ds_write data hazards beside matrix-heavy neighbours)
-                            float gv[6];
-#pragma unroll
-                            for (int q = 0; q < 6; ++q) gv[q] = acc[q] + bh[q];
-#pragma unroll
-                            for (int q = 0; q < 6; ++q) { LDSW(gh_s[wid * 6 + q][rr], gv[q]); lav::lds_store_fence(); }
-                            lav::lds_commit();
-#pragma unroll
-                            for (int q = 0; q < 6; ++q) lav::lds_keep(gv[q]);
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            if (gate_thread) {
-                if (t == 0) hself = a.embd[(long)gb * H + j0 + gu];
-                const float uu[4] = {u0, u1, LDSR(loc_s[cur][grr][t][0]), LDSR(loc_s[cur][grr][t][1])};
-                float gi[3];
-#pragma unroll
-                for (int g = 0; g < 3; ++g) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) acc = fmaf(wih[g][k], uu[k], acc);
-                    gi[g] = acc + bih[g];
-                }
-                const float rg = sigmoidf_(gi[0] + LDSR(gh_s[0 * PLAN_UNITS + gu][grr]));
-                const float zg = sigmoidf_(gi[1] + LDSR(gh_s[1 * PLAN_UNITS + gu][grr]));
-                const float ng = tanhf(gi[2] + rg * LDSR(gh_s[2 * PLAN_UNITS + gu][grr]));
-                hself = (1.f - zg) * ng + zg * hself;
-                const unsigned long long x = ((unsigned long long)(epoch + 1) << 32) | __float_as_uint(hself);
-                __hip_atomic_store(gran + (long)(epoch & 1) * R * H + (long)grr * H + j0 + gu, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            __syncthreads();
-        }
-        __syncthreads();
-        cur ^= 1;
-    }
-    if (tid == 0) atomicAdd(status + 9, 1);
-}
-#undef LDSR
-#undef LDSW
 
 // ------------------------------------------------------------------------------------------------- plan, persistent, LDS-free (round 5)
-// The default since round 5.  One WAVE per workgroup, H/8 workgroups: the wave holds all three gates of its 8 hidden units (24 rows of
+// The persistent kernel since round 5 (rounds 2-4's four-wave LDS kernel: tools/probes/plan_persistent_r4.diff).
+// One WAVE per workgroup, H/8 workgroups: the wave holds all three gates of its 8 hidden units (24 rows of
 // W_hh + the two rows of Linear(H->2): 208 registers per lane), so that a unit's r / z / n pre-activations meet inside the wave and
 // nothing of the recurrence ever goes through LDS: no DS instruction (the cross-lane sums are v_permlane32_swap / v_permlane16_swap /
 // DPP adds, not ds_bpermute), no barrier, no LDS allocation - the victim surface of DESIGN 4.4c (LDS-dependent results going wrong beside
 // matrix + LDS heavy neighbours) does not exist in this kernel, and tests/test_capi_host.py disassembles the library to keep it so.
 // The waypoints of the previous iteration live in registers (lane t holds waypoint t; v_readlane feeds the gate inputs).
-// Same arithmetic as k_plan_step / k_plan_persistent: per lane an 8-term fmaf chain over k = lane + 64 i, then the xor butterfly
+// Same arithmetic as k_plan_step: per lane an 8-term fmaf chain over k = lane + 64 i, then the xor butterfly
 // 32, 16, 8, 4, 2, 1 - the swaps + adds below ARE that butterfly (fp addition is commutative, both partners of a pair end up with the
 // same bits), 26 sums folded 32 -> 16 -> 8 registers on the way down instead of 26 x 6 exchanges: bit-identical results.
-// Polling traffic per workgroup = the quarter-poll scheme's (every granule is read once per round by one wave).
+// Every granule is read once per poll round and workgroup (the chip's other streams pay for every poll).
 // p[q][j]: this lane's partial sum of slot (quarter q, j): j < 6 -> unit 2q + j / 3, gate j % 3; (0, 6) and (0, 7): the two waypoint rows.
 // Returns in z[j] the complete sum of slot (Q, j), where Q is the quarter of this lane's row of 16 lanes (kernel entry calibrates Q).
 __device__ __forceinline__ void plan_fold(const float (&p)[4][6], float s0, float s1, float (&z)[8]) {
@@ -953,7 +676,7 @@ int plan_launch(bool allow_persistent, const float *embd, const float *nxp, cons
     if (!workspace || workspace_bytes < need) return lav::fail(LAV_EWORKSPACE, "lav_gru_plan: workspace %zu < %zu bytes", workspace_bytes, need);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int tok = timer_begin("gru_plan", st);
-    const char *impl = getenv("LAV_PLAN_IMPL");
+    const char *impl = getenv("LAV_PLAN_IMPL");   // A/B knob: steps = one launch per step; v (below); anything else: the persistent kernel
     if (allow_persistent && a.R <= PLAN_RC && !(impl && impl[0] == 's')) {
         // persistent kernel: its H/8 workgroups (64 of 256 CUs) must become co-resident while other streams' kernels hold the
         // chip - not guaranteed by HIP, hence the bounded spins, the status / diagnosis words and the NaN poisoning
@@ -969,33 +692,12 @@ int plan_launch(bool allow_persistent, const float *embd, const float *nxp, cons
         hipLaunchKernelGGL(k_plan_reset, dim3((reset_words / 4 + 255) / 256), dim3(256), 0, st, reinterpret_cast<uint4 *>(status), reset_words / 4);
         const char *lim = getenv("LAV_PLAN_SPIN_LIMIT");   // test knob: 1 forces the time-out path
         const long long spin_limit = lim && atoll(lim) > 0 ? atoll(lim) : PLAN_SPIN_LIMIT;
-        // quarter (default where H allows it) | all.  History (profiles/r04_plan_stress.txt): round 4's golden drive showed finite but
-        // WRONG plans on random ticks once the 7x7 crop stems ran on the tap-pair split kernel.  tools/plan_stress.py reproduced it on
-        // every launch, for BOTH polling variants, whenever this kernel's waves shared CUs with workgroups that issue matrix
-        // instructions and LDS traffic (the stem kernel, or the synthetic neighbour of tools/probes/lds_hog.hip); the hidden state
-        // exchanged between the workgroups was always right (instrumented), the damage was inside a workgroup: (1) a ds_write2_b64
-        // whose data registers hipcc overwrote with the next instructions (common.hpp: lds_store_fence - with that alone a neighbour
-        // that only issues matrix instructions is harmless), (2) something that committing the LDS stores (lds_commit / lds_keep) did
-        // NOT cure - round 5: packed fp32 instructions with an op_sel bit on their second source, which hipcc's SLP vectoriser had put into
-        // this kernel's reductions, go wrong in lanes 48-63 beside such neighbours (common.hpp; the library is built without them and
-        // tests/test_capi_host.py scans the ISA).  Round 4 kept the aggressors away with LDS claims (now an opt-in, LAV_LDS_EXCLUSIVE=1).
-        // tests/test_gpu_paint_gru.py compares every implementation with the step path, and bench.py re-computes the plans of frames
-        // after its timed ones on the step path (`plan_vs_step_path_max_abs`).
-        // Default: k_plan_wave (round 5, no LDS at all).  LAV_PLAN_IMPL=lds: rounds 2-4's four-wave kernel (quarter poll, LAV_PLAN_POLL=all:
-        // every wave polls everything) - kept as the known victim of tools/coresidency.py, not used by the frame.
-        static const char *poll_env = getenv("LAV_PLAN_POLL");
-        const bool quarter = H % 256 == 0 && !(poll_env && poll_env[0] == 'a');
-        if (impl && impl[0] == 'l') {
-#define LAV_PLAN_CASE(P_, RC_) hipLaunchKernelGGL((k_plan_persistent<P_, RC_>), dim3(H / PLAN_UNITS), dim3(256), 0, st, a, gran, status, spin_limit)
-            if (a.R == 1) { if (quarter) LAV_PLAN_CASE(1, 1); else LAV_PLAN_CASE(0, 1); }
-            else { if (quarter) LAV_PLAN_CASE(1, PLAN_RC); else LAV_PLAN_CASE(0, PLAN_RC); }
-#undef LAV_PLAN_CASE
-        } else {
+        // k_plan_wave keeps nothing of its recurrence in LDS.  tests/test_gpu_paint_gru.py compares it with the step path, and
+        // bench.py re-computes the plans of frames after its timed ones on the step path (`plan_vs_step_path_max_abs`).
 #define LAV_PLAN_CASE(RC_, NK_) hipLaunchKernelGGL((k_plan_wave<RC_, NK_>), dim3(H / PLAN_UNITS), dim3(64), 0, st, a, gran, status, spin_limit)
-            if (a.R == 1) { if (H == 512) LAV_PLAN_CASE(1, 8); else LAV_PLAN_CASE(1, 0); }
-            else { if (H == 512) LAV_PLAN_CASE(PLAN_RC, 8); else LAV_PLAN_CASE(PLAN_RC, 0); }
+        if (a.R == 1) { if (H == 512) LAV_PLAN_CASE(1, 8); else LAV_PLAN_CASE(1, 0); }
+        else { if (H == 512) LAV_PLAN_CASE(PLAN_RC, 8); else LAV_PLAN_CASE(PLAN_RC, 0); }
 #undef LAV_PLAN_CASE
-        }
         const long n_out = (long)a.B * a.iters * a.NC * T * 2;
         hipLaunchKernelGGL(k_plan_poison, dim3((unsigned)std::min<long>((n_out + 255) / 256, 64)), dim3(256), 0, st, status, sticky, a.out, n_out);
         timer_end(tok, st);

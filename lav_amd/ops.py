@@ -846,7 +846,7 @@ class ConvLayer:
 
     def uses_amax(self, B: int, h: int, w: int) -> bool:
         """Whether this layer on a (B, ., h, w) input runs the fp16 three-product plan, i.e. has a use for its producers' maxima."""
-        key = ("f16", B, h, w, _os.environ.get("LAV_CONV_SPLIT"), _os.environ.get("LAV_SPLIT_SK"))
+        key = ("f16", B, h, w, _os.environ.get("LAV_CONV_SPLIT"))
         v = self._ws_bytes.get(key)
         if v is None:
             v = False
@@ -877,7 +877,7 @@ class ConvLayer:
             if residual.shape != out.shape:
                 raise RuntimeError("residual shape mismatch")
         lib = _lib.load()
-        key = (B, h, w, _os.environ.get("LAV_CONV_SPLIT"), _os.environ.get("LAV_SPLIT_SK"))   # lav_conv2d re-reads the plan knobs per call: the cached size follows them
+        key = (B, h, w, _os.environ.get("LAV_CONV_SPLIT"))   # lav_conv2d re-reads the plan knobs per call: the cached size follows them
         nbytes = self._ws_bytes.get(key)
         if nbytes is None:
             nbytes = self._ws_bytes[key] = lib.lav_conv_workspace_bytes(C.byref(d))
@@ -890,7 +890,7 @@ class ConvLayer:
         a_in = amax_in.buf if amax_in is not None and amax_in.count > 0 else None
         a_out = None
         if amax_out is not None:
-            ck = ("amax", B, h, w, _os.environ.get("LAV_CONV_SPLIT"), _os.environ.get("LAV_SPLIT_SK"))
+            ck = ("amax", B, h, w, _os.environ.get("LAV_CONV_SPLIT"))
             n_out = self._ws_bytes.get(ck)
             if n_out is None:
                 n_out = self._ws_bytes[ck] = lib.lav_conv_amax_count(C.byref(d))

@@ -1,5 +1,5 @@
 """What clock and power does the chip run at under the head convolution?  The 384 -> 256 3x3 convolution (bf16x6, k_conv_split<2,2>) is
-launched back to back for a few seconds while rocm-smi is polled; the same for the stream-K launch and for an idle chip.  The roofline
+launched back to back for a few seconds while rocm-smi is polled; the same for hipBLASLt's bf16 GEMM and for an idle chip.  The roofline
 fractions in bench.py are against the 2.4 GHz peak of /opt/skills/guides/MI355X_MICROARCH.md.    python tools/clock_probe.py"""
 import os
 import subprocess
@@ -48,6 +48,6 @@ def run(label, seconds, fn):
 
 
 run("idle", 2.0, lambda: None)
-run(f"head convolution (LAV_SPLIT_SK={os.environ.get('LAV_SPLIT_SK', '1')})", 6.0, lambda: layer(x))
+run("head convolution", 6.0, lambda: layer(x))
 a = torch.randn((8192, 8192), device=dev, dtype=torch.bfloat16)
 run("torch bf16 8192^3 matmul (hipBLASLt)", 6.0, lambda: a @ a)

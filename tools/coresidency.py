@@ -49,7 +49,6 @@ def _plan(impl):
 
 
 victims["plan (k_plan_wave, no LDS)"] = _plan("wave")
-victims["plan (k_plan_persistent, LDS: rounds 2-4)"] = _plan("lds")
 victims["plan (k_plan_step x 100)"] = _plan("steps")
 
 _cw = (g(NC, 192, 512, sc=512 ** -0.5), g(NC, 192, 64, sc=0.125), g(NC, 192, sc=0.1), g(NC, 192, sc=0.1), g(NC, 2, 64, sc=0.1), g(NC, 2, sc=0.1))

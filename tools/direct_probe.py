@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Calibration of the direct small-layer convolution: every shape timed on the tiled plan and on the direct kernel for
-each (waves, split-K) it admits (HIP events around back-to-back launches).
+"""The small-layer convolution shapes of the frame, each timed on the plan the library chooses for it (HIP events around back-to-back
+launches), with that plan.  The sweep over waves x split-K x cout blocks that calibrated the direct kernel's cost model
+went with the knobs that pinned those choices.
 
     python tools/direct_probe.py [name-substring ...]
 """
@@ -73,32 +74,13 @@ def main():
         w = torch.randn((cin, cout, k, k) if tr else (cout, cin, k, k)) * 0.05
         for B in batches:
             x = torch.randn((B, cin, H, W), device=dev)
-            res = {}
-            for cfg in ["tiled", "auto"] + [f"w{wv}k{ks}m{mc}" for mc in (1, 2) for wv in (4, 8, 16) for ks in (1, 2, 4, 8, 16)]:
-                os.environ.pop("LAV_CONV_DIRECT_WAVES", None); os.environ.pop("LAV_CONV_DIRECT_KS", None); os.environ.pop("LAV_CONV_DIRECT_MC", None)
-                if cfg == "tiled":
-                    os.environ["LAV_CONV_DIRECT"] = "0"
-                elif cfg == "auto":
-                    os.environ["LAV_CONV_DIRECT"] = "1"
-                else:
-                    wv, rest = cfg[1:].split("k")
-                    ks, mc = rest.split("m")
-                    if cin % (8 * int(wv) * int(ks)) or (mc == "2" and (cout < 64 or int(wv) > 8)):
-                        continue
-                    os.environ.update(LAV_CONV_DIRECT="2", LAV_CONV_DIRECT_WAVES=wv, LAV_CONV_DIRECT_KS=ks, LAV_CONV_DIRECT_MC=mc)
-                layer = ConvLayer(w, stride=s, padding=p, relu_post=True, transposed=tr, output_padding=1 if (tr and k == 3) else 0, device=dev)
-                try:
-                    res[cfg] = timed(layer, x)
-                except RuntimeError as e:
-                    res[cfg] = float("nan")
-            best = min((v, c) for c, v in res.items() if c not in ("tiled", "auto") and v == v)
+            layer = ConvLayer(w, stride=s, padding=p, relu_post=True, transposed=tr, output_padding=1 if (tr and k == 3) else 0, device=dev)
+            us = timed(layer, x)
             d = Conv.from_buffer_copy(layer.desc); d.batch, d.h, d.w = B, H, W
             info = (ctypes.c_int * 9)()
-            os.environ["LAV_CONV_DIRECT"] = "1"; os.environ.pop("LAV_CONV_DIRECT_WAVES", None); os.environ.pop("LAV_CONV_DIRECT_KS", None); os.environ.pop("LAV_CONV_DIRECT_MC", None)
             lib.lav_conv_tile_info(ctypes.byref(d), info)
-            plan = f"w{info[1]}k{info[6]}m{info[2]}" if info[0] == 0 else f"tile{info[0]}x{info[1]}k{info[6]}"
-            print(f"{name:24s} B={B}  tiled {res['tiled']:6.1f}  auto {res['auto']:6.1f} ({plan:10s})  best direct {best[1]:6s} {best[0]:6.1f} | " +
-                  " ".join(f"{c}:{v:.1f}" for c, v in sorted(res.items(), key=lambda cv: cv[1])[:8] if c not in ("tiled", "auto")), flush=True)
+            plan = f"direct w{info[1]}k{info[6]}m{info[2]}" if info[0] == 0 else f"split {info[1]}x{info[2]}/w{info[3]}k{info[6]}" if info[0] == -1 else f"tile {info[0]}x{info[1]}k{info[6]}"
+            print(f"{name:24s} B={B}  {us:6.1f} us  ({plan})", flush=True)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,7 @@ Alternates two different inputs (so that a value left over from the previous lau
 step-per-launch path (lav_gru_plan_steps) of the same input, with and without a hog stream (the others branch's 7x7 stem at
 capacity 15: 150 KB of LDS per workgroup, one workgroup per CU), eager and as a replayed HIP graph.
 
-    [LAV_PLAN_POLL=all] python tools/plan_stress.py [launches]
+    python tools/plan_stress.py [launches]
 """
 import os
 import sys

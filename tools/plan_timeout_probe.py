@@ -1,4 +1,4 @@
-"""Where do un-forced time-outs of k_plan_persistent come from?  
+"""Where do un-forced time-outs of the persistent plan kernel come from?  
 
 Drives the HIP-graph agent over the ticks of tests/test_gpu_agent.py and prints, per tick: host wall time of the step, NaN
 count of the plan, the kernel's diagnosis words (lav_gru_plan_diag), whether graphs were captured on this tick.
