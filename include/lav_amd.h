@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 37
+#define LAV_ABI_VERSION 38
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -929,6 +929,29 @@ int lav_eval_frame(const float *pred_bev, const unsigned char *labels, const uns
                    const float *ego_plan, const float *ego_locs, int cmd, const float *other_cast, const float *other_cmds,
                    const int *other_row, int num_others, double ppm, double centre_x, double centre_y, double radius_px,
                    double min_score, double det_score, int nbins, long long *acc, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Held-out metrics of the camera checkpoints (ABI 38; eval_seg.py, eval_bra_v2.py, lav_amd.train.evaluate_camera).  Each call is one
+ * launch on `stream` that ADDS integers into a caller-owned section of 64-bit words in HBM; nothing is copied to the host.
+ * Specifications: lav_amd.train.evaluate_camera.eval_seg_numpy / eval_scores_numpy, word for word.  The reference has no evaluator:
+ * the definitions are this project's, parity with a reference is UNPINNED.
+ *
+ * lav_eval_seg: the confusion matrix of labels [n][h scale][w scale] uint8 against logits [n][k][h][w] float32, 2 <= k <= 8, scale in
+ *         {1, 2, 4, 8}: label pixel (y, x) is judged by logit pixel (y / scale, x / scale) - F.interpolate(logits, scale_factor=scale)
+ *         (nearest) followed by argmax, without the up-sampled logits.  The prediction of a logit pixel is the FIRST maximum of its k
+ *         channels (p = 0; for c in 1 .. k - 1: if x[c] > x[p]: p = c).  A logit pixel with a channel that is not finite adds its
+ *         scale^2 label pixels to `nonfinite` and to nothing else; otherwise a label >= k adds 1 to `ignored` and to nothing else.
+ *         The section has 68 words whatever k is: images, pixels (label pixels seen), ignored, nonfinite, conf [8][8] (row = label,
+ *         column = prediction).  n h w scale^2 must not exceed 2^31 (a workgroup counts in 32 bits before its 64-bit atomics).
+ * lav_eval_scores: scores [n] float32 against flags [n] uint8, one workgroup.  The section has 6 + 2 nbins words, 1 <= nbins <= 1024:
+ *         samples, nonfinite, at [flag != 0][(double)score > threshold], hist [flag != 0][bin] with
+ *         bin = clamp((int)(score * (float)nbins), 0, nbins - 1) in float32 (lav_eval_frame's rule).  A NaN or infinite score counts in
+ *         samples and nonfinite only.
+ */
+int lav_eval_seg(const float *logits, const unsigned char *labels, int n, int k, int h, int w, int scale, unsigned long long *acc,
+                 void *stream);
+int lav_eval_scores(const float *scores, const unsigned char *flags, int n, double threshold, int nbins, unsigned long long *acc,
+                    void *stream);
 
 #ifdef __cplusplus
 }

@@ -472,6 +472,70 @@ def eval_frame(acc: torch.Tensor, pred_bev: torch.Tensor, bev: torch.Tensor, mas
     return acc
 
 
+EVAL_SEG_WORDS = 68            # lav_eval_seg's section: images, pixels, ignored, nonfinite, conf [8][8]
+
+
+def _eval_tensor(op, name, t, dtype, shape, like):
+    """eval_seg's / eval_scores' check of one argument: in HBM, on the section's device, of the dtype and shape, contiguous."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{op}: {name} must be a tensor in HBM (cuda/hip device); lav_amd.ops has no CPU path "
+                         f"(lav_amd.train.evaluate_camera.{op}_numpy is the CPU specification)")
+    if t.device != like.device:
+        raise ValueError(f"{op}: {name} is on {t.device}, the accumulator on {like.device}")
+    if t.dtype != dtype or t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
+        raise ValueError(f"{op}: {name} must be {dtype} of shape {tuple('*' if s is None else s for s in shape)}, got {t.dtype} {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{op}: {name} must be contiguous (the kernel reads it where it is)")
+    return t
+
+
+def _eval_section(op, acc_section, words):
+    if (not isinstance(acc_section, torch.Tensor) or not acc_section.is_cuda or acc_section.dtype != torch.int64
+            or tuple(acc_section.shape) != (words,) or not acc_section.is_contiguous()):
+        raise ValueError(f"{op}: the section must be a contiguous int64 tensor (or slice of one) of {words} words in HBM")
+
+
+def eval_seg(acc_section: torch.Tensor, logits: torch.Tensor, labels: torch.Tensor, scale: int = 1) -> torch.Tensor:
+    """The confusion matrix of labels (n, h * scale, w * scale) uint8 against logits (n, k, h, w) float32, 2 <= k <= 8, scale in
+    {1, 2, 4, 8}, ADDED into `acc_section` (int64, 68 words, in HBM) by one launch on the current stream (lav_eval_seg); nothing comes
+    back to the host.  Label pixel (y, x) is judged by logit pixel (y // scale, x // scale): F.interpolate(logits, scale_factor=scale)
+    followed by argmax (the first maximum), without the up-sampled logits.  Word for word lav_amd.train.evaluate_camera.eval_seg_numpy,
+    which has the definitions.  Wrong shapes, dtypes or devices raise ValueError before anything is launched."""
+    _eval_section("eval_seg", acc_section, EVAL_SEG_WORDS)
+    logits = _eval_tensor("eval_seg", "logits", logits, torch.float32, (None, None, None, None), acc_section)
+    n, k, h, w = logits.shape
+    scale = int(scale)
+    if scale not in (1, 2, 4, 8):
+        raise ValueError(f"eval_seg: scale {scale} (1, 2, 4 or 8)")
+    if not 2 <= k <= 8:
+        raise ValueError(f"eval_seg: {k} classes (2 .. 8)")
+    if n < 1 or h < 1 or w < 1 or h > 16384 or w > 16384 or n * h * w * scale * scale > 1 << 31:
+        raise ValueError(f"eval_seg: logits {tuple(logits.shape)} at scale {scale}: at least one pixel, sides up to 16384, at most 2^31 label pixels")
+    labels = _eval_tensor("eval_seg", "labels", labels, torch.uint8, (n, h * scale, w * scale), acc_section)
+    check(_lib.load().lav_eval_seg(_ptr(logits), _ptr(labels), n, k, h, w, scale, _ptr(acc_section), _stream()), "lav_eval_seg")
+    return acc_section
+
+
+def eval_scores(acc_section: torch.Tensor, scores: torch.Tensor, flags: torch.Tensor, threshold: float, nbins: int) -> torch.Tensor:
+    """scores (n,) float32 against flags (n,) uint8, ADDED into `acc_section` (int64, 6 + 2 nbins words, in HBM) by one launch on the
+    current stream (lav_eval_scores): samples, nonfinite, at [flag != 0][float64(score) > threshold], hist [flag != 0][bin].  Word for
+    word lav_amd.train.evaluate_camera.eval_scores_numpy.  Wrong shapes, dtypes or devices raise ValueError before anything is launched."""
+    nbins = int(nbins)
+    if not 1 <= nbins <= 1024:
+        raise ValueError(f"eval_scores: {nbins} score bins (1 .. 1024)")
+    _eval_section("eval_scores", acc_section, 6 + 2 * nbins)
+    scores = _eval_tensor("eval_scores", "scores", scores, torch.float32, (None,), acc_section)
+    n = scores.shape[0]
+    if n < 1:
+        raise ValueError("eval_scores: no scores")
+    flags = _eval_tensor("eval_scores", "flags", flags, torch.uint8, (n,), acc_section)
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("eval_scores: the threshold must be a number")
+    check(_lib.load().lav_eval_scores(_ptr(scores), _ptr(flags), n, threshold, nbins, _ptr(acc_section), _stream()), "lav_eval_scores")
+    return acc_section
+
+
 # ------------------------------------------------------------------------------------------ GRU decoders
 def gru_cast(embd, w_ih, w_hh, b_ih, b_hh, mlp_w, mlp_b, T: int):
     """embd (B, E); stacked per-command GRU/MLP weights -> (B, num_cmds, T, 2)."""
