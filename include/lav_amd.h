@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 38
+#define LAV_ABI_VERSION 39
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -952,6 +952,35 @@ int lav_eval_seg(const float *logits, const unsigned char *labels, int n, int k,
                  void *stream);
 int lav_eval_scores(const float *scores, const unsigned char *flags, int n, double threshold, int nbins, unsigned long long *acc,
                     void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Held-out metrics of the privileged BEV teacher (ABI 39; eval_bev_v2.py, lav_amd.train.evaluate_bev): one launch per LOADER BATCH on
+ * `stream` that ADDS integers into an int64 accumulator in HBM; nothing is copied to the host.  Specification:
+ * lav_amd.train.evaluate_bev.eval_plans_numpy, word for word.  The reference has no evaluator: the definitions are this project's,
+ * parity with a reference is UNPINNED.
+ *
+ * ego_plan [batch][iters][6][num_plan][2], ego_cast [batch][6][num_plan][2], ego_cmds [batch][6], ego_locs [batch][num_plan + 1][2],
+ * cmds [batch] int32, bras [batch] uint8 (non-zero = the frame brakes); other_cast [num_others][6][num_plan][2], other_cmds
+ * [num_others][6], other_locs [num_others][num_plan][2] (each forecast's target in its vehicle's own frame), all three may be NULL when
+ * num_others is 0.  batch >= 1, num_others >= 0, 1 <= num_plan <= 64, 1 <= iters <= 8.
+ *
+ * S = iters + 1 stages: stage 0 is ego_cast at the frame's command, stage s is ego_plan[.][s - 1] at the frame's command.
+ * q_t = llrint(sqrt(dx^2 + dy^2) * 2^20) in float64, lav_eval_frame's rule.  The accumulator has 57 + 37 S words, as the size function
+ * says (0 for iters outside 1 .. 8), in this order:
+ *   frames; bad_cmd: frames whose command is outside 0 .. 5, which add to nothing else;
+ *   plan [bra != 0][S][6 commands][frames, sum of q_t, q_{T-1}] against ego_locs[.][1 ..];
+ *   plan_nonfinite [S]: a stage with a distance that is not below 2^32 m counts here and not in plan, every stage on its own;
+ *   cmd_conf [command][first maximum of ego_cmds; a NaN counts as a maximum];
+ *   others: forecasts scored; oth_nonfinite: forecasts with a non-finite distance in any mode, which add to nothing else;
+ *   oth [4]: sums of the min mode's sum of q_t, of the top mode's, of the top mode's q_{T-1}, of the min mode's q_{T-1};
+ *   oth_min_mode [6], oth_top_mode [6]: histograms of the mode with the smallest sum (the first minimum) and of the first maximum of
+ *   other_cmds; oth_top_is_min: forecasts whose top mode is the min mode.
+ * One wave per frame and per forecast, four to a workgroup; one 64-bit atomic per workgroup and counter.
+ */
+size_t lav_eval_plans_words(int iters);
+int lav_eval_plans(const float *ego_plan, const float *ego_cast, const float *ego_cmds, const float *ego_locs, const int *cmds,
+                   const unsigned char *bras, int batch, int iters, int num_plan, const float *other_cast, const float *other_cmds,
+                   const float *other_locs, int num_others, long long *acc, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LAV_AMD_LIB") or os.path.join(HERE, "liblav_amd.so")   # LAV_AMD_LIB: A/B a second build
 
-ABI_VERSION = 38
+ABI_VERSION = 39
 MAX_CAM = 4
 MAX_CAM_F64 = 8
 
@@ -164,6 +164,8 @@ SIGNATURES = {
     "lav_eval_frame": (_I, [_P, _P, _P, _I, _I, _F, _P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I] + [C.c_double] * 6 + [_I, _P, _P]),
     "lav_eval_seg": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "lav_eval_scores": (_I, [_P, _P, _I, C.c_double, _I, _P, _P]),
+    "lav_eval_plans_words": (_Z, [_I]),
+    "lav_eval_plans": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
 }
 
 _lib = None

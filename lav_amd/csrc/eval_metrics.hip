@@ -13,7 +13,7 @@
 //
 // Floating point: float64 from the float32 inputs, contraction off (lav_amd/build.py), so that (double)loc * ppm + centre,
 // dx * dx + dy * dy and sqrt(.) * 2^20 round as NumPy rounds them; llrint rounds to nearest even like np.rint.
-#include "common.hpp"
+#include "eval_quantum.hpp"      // quantum(), wave_sum(), first_max(): shared with eval_plans.hip
 
 #pragma clang fp contract(off)
 
@@ -21,12 +21,10 @@ namespace {
 using namespace lav;
 constexpr int THREADS = 256, WAVES = THREADS / WAVE;
 constexpr int MAX_DET = 32, MAX_OBJS = 64, MAX_PLAN = 64, MAX_BINS = 1024, MAX_SEG_GROUPS = 256;
-constexpr int CMDS = 6;                // LAV's commands: the plan's per-command counters and the modes of a forecast
+constexpr int CMDS = EVAL_CMDS;
 // the accumulator's words; lav_amd.train.evaluate.ACC names the same slices (tests/test_eval_host.py compares the lengths)
 enum { A_FRAMES = 0, A_SEG = 1, A_NGT = 10, A_DET = 12, A_PLAN = 16, A_PLAN_NONFINITE = 34, A_OTH_MATCHED = 35, A_OTH_UNMATCHED = 36,
        A_OTH_NONFINITE = 37, A_OTH_MIN = 38, A_OTH_TOP = 39, A_OTH_TOP_FINAL = 40, A_HIST = 41 };
-constexpr double Q = 1048576.0;        // 2^20 quanta per metre
-constexpr double FAR = 4294967296.0;   // 2^32 m: a distance that is not below it (NaN, Inf, absurd) makes its plan "non-finite"
 
 struct Args {
     const float *pred;
@@ -54,21 +52,6 @@ __device__ __forceinline__ unsigned count_of(bool b) { return (unsigned)__popcll
 __device__ __forceinline__ void lds_put(long long *p, long long v) {
     *p = v;
     lds_store_fence();
-}
-
-__device__ __forceinline__ long long wave_sum(long long v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// q = llrint(|a - b| * 2^20) in float64; false where the distance is not below 2^32 m
-__device__ __forceinline__ bool quantum(const float *a, const float *b, long long &q) {
-    const double dx = (double)a[0] - (double)b[0], dy = (double)a[1] - (double)b[1];
-    const double d = sqrt(dx * dx + dy * dy);
-    const bool ok = d < FAR;
-    q = ok ? llrint(d * Q) : 0;
-    return ok;
 }
 
 __device__ void segmentation(const Args &a, int groups) {
@@ -191,13 +174,7 @@ __device__ void actors(const Args &a) {
         const int r = a.other_row[k];
         const int g = r >= 0 && r < D ? s_match[1][r] : -1;
         if (g < 0) { o_unmatched += 1; continue; }
-        const float *cmds = a.other_cmds + (size_t)k * CMDS;
-        float bv = cmds[0];
-        int top = 0;                                   // np.argmax: the first maximum, and a NaN counts as one
-        for (int m = 1; m < CMDS && bv == bv; ++m) {
-            const float v = cmds[m];
-            if (v > bv || v != v) { bv = v; top = m; }
-        }
+        const int top = first_max(a.other_cmds + (size_t)k * CMDS);
         long long s_min = 0, s_top = 0, q_top = 0;
         bool finite = true;
         for (int m = 0; m < CMDS; ++m) {

@@ -476,10 +476,10 @@ EVAL_SEG_WORDS = 68            # lav_eval_seg's section: images, pixels, ignored
 
 
 def _eval_tensor(op, name, t, dtype, shape, like):
-    """eval_seg's / eval_scores' check of one argument: in HBM, on the section's device, of the dtype and shape, contiguous."""
+    """eval_seg's / eval_scores' / eval_plans' check of one argument: in HBM, on the section's device, of the dtype and shape, contiguous."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise ValueError(f"{op}: {name} must be a tensor in HBM (cuda/hip device); lav_amd.ops has no CPU path "
-                         f"(lav_amd.train.evaluate_camera.{op}_numpy is the CPU specification)")
+                         f"(lav_amd.train.{'evaluate_bev' if op == 'eval_plans' else 'evaluate_camera'}.{op}_numpy is the CPU specification)")
     if t.device != like.device:
         raise ValueError(f"{op}: {name} is on {t.device}, the accumulator on {like.device}")
     if t.dtype != dtype or t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
@@ -534,6 +534,57 @@ def eval_scores(acc_section: torch.Tensor, scores: torch.Tensor, flags: torch.Te
         raise ValueError("eval_scores: the threshold must be a number")
     check(_lib.load().lav_eval_scores(_ptr(scores), _ptr(flags), n, threshold, nbins, _ptr(acc_section), _stream()), "lav_eval_scores")
     return acc_section
+
+
+def eval_plans_words(iters: int) -> int:
+    """Length of lav_eval_plans' accumulator for `iters` plan iterations, 57 + 37 (iters + 1) (lav_eval_plans_words; host only, no
+    device needed)."""
+    n = int(_lib.load().lav_eval_plans_words(int(iters)))
+    if n == 0:
+        raise ValueError(f"eval_plans: {iters} plan iterations (1 .. 8)")
+    return n
+
+
+def eval_plans(acc: torch.Tensor, ego_plan: torch.Tensor, ego_cast: torch.Tensor, ego_cmds: torch.Tensor, ego_locs: torch.Tensor,
+               cmds: torch.Tensor, bras: torch.Tensor, other_cast=None, other_cmds=None, other_locs=None) -> torch.Tensor:
+    """The teacher's metrics over one loader batch, ADDED into `acc` (int64, ops.eval_plans_words(I) words, in HBM) by one launch on the
+    current stream (lav_eval_plans); nothing comes back to the host.  ego_plan (B, I, 6, T, 2), ego_cast (B, 6, T, 2), ego_cmds (B, 6),
+    ego_locs (B, T + 1, 2) float32; cmds (B,) int32; bras (B,) uint8; other_cast (K, 6, T, 2), other_cmds (K, 6), other_locs (K, T, 2)
+    float32 - with K = 0 they may be None or empty tensors.  B >= 1, 1 <= T <= 64, 1 <= I <= 8.  Word for word
+    lav_amd.train.evaluate_bev.eval_plans_numpy, which names the accumulator's slices (PlanLayout).  Wrong shapes, dtypes, devices or
+    an accumulator of another length raise ValueError before anything is launched."""
+    if not isinstance(acc, torch.Tensor) or not acc.is_cuda or acc.dtype != torch.int64 or acc.dim() != 1 or not acc.is_contiguous():
+        raise ValueError("eval_plans: acc must be a contiguous int64 tensor in HBM (lav_amd.train.evaluate_bev.eval_plans_numpy is the CPU specification)")
+    need = lambda name, t, dtype, shape: _eval_tensor("eval_plans", name, t, dtype, shape, acc)
+    if not isinstance(ego_plan, torch.Tensor) or ego_plan.dim() != 5:
+        raise ValueError("eval_plans: ego_plan must be a float32 tensor of shape (B, I, 6, T, 2)")
+    B, I, _, T, _ = ego_plan.shape
+    if B < 1 or B > 1 << 20 or not 1 <= T <= 64 or not 1 <= I <= 8:
+        raise ValueError(f"eval_plans: ego_plan {tuple(ego_plan.shape)}: at least one frame, 1 .. 8 iterations, 1 .. 64 waypoints")
+    words = eval_plans_words(I)
+    if acc.shape[0] != words:
+        raise ValueError(f"eval_plans: acc has {acc.shape[0]} words, {I} plan iterations take {words}")
+    ego_plan = need("ego_plan", ego_plan, torch.float32, (B, I, 6, T, 2))
+    ego_cast = need("ego_cast", ego_cast, torch.float32, (B, 6, T, 2))
+    ego_cmds = need("ego_cmds", ego_cmds, torch.float32, (B, 6))
+    ego_locs = need("ego_locs", ego_locs, torch.float32, (B, T + 1, 2))
+    cmds = need("cmds", cmds, torch.int32, (B,))
+    bras = need("bras", bras, torch.uint8, (B,))
+    count = lambda t: 0 if t is None else (t.shape[0] if t.dim() else 1)
+    K = count(other_cast)
+    if count(other_cmds) != K or count(other_locs) != K:
+        raise ValueError(f"eval_plans: {count(other_cmds)} command scores and {count(other_locs)} targets for {K} forecasts")
+    if K > 1 << 24:
+        raise ValueError(f"eval_plans: {K} forecasts (at most 2^24)")
+    if K > 0:
+        other_cast = need("other_cast", other_cast, torch.float32, (K, 6, T, 2))
+        other_cmds = need("other_cmds", other_cmds, torch.float32, (K, 6))
+        other_locs = need("other_locs", other_locs, torch.float32, (K, T, 2))
+    else:
+        other_cast = other_cmds = other_locs = None
+    check(_lib.load().lav_eval_plans(_ptr(ego_plan), _ptr(ego_cast), _ptr(ego_cmds), _ptr(ego_locs), _ptr(cmds), _ptr(bras), B, I, T,
+                                     _ptr(other_cast), _ptr(other_cmds), _ptr(other_locs), K, _ptr(acc), _stream()), "lav_eval_plans")
+    return acc
 
 
 # ------------------------------------------------------------------------------------------ GRU decoders

@@ -83,25 +83,43 @@ def random_sample(binaries, size):
     return cut
 
 
+def select_others(ego_locs, locs, typs, ahead=True):
+    """The selection half of sample_others, no random draw: which of locs[:, 1:] are vehicles (typs == 1) and, with `ahead`, pass
+    filter_cars.  (B, N) bool."""
+    vehicles = typs[:, 1:] == 1          # 1 = vehicle
+    return filter_cars(ego_locs, locs[:, 1:], vehicles) if ahead else vehicles
+
+
+def picked_others(ego_locs, locs, oris, picked, jitter):
+    """The geometry of the picked vehicles (`picked`: (B, N) bool over locs[:, 1:]): their crops in the ego frame and their future in
+    their own.  jitter(K, device) -> ((K, 2), (K,)) is called once, after the gathers - where sample_others has always drawn -, and
+    zeros there give the un-jittered quantities by the same arithmetic."""
+    ego_oris = oris[:, :1]
+    locs, oris = locs[:, 1:], oris[:, 1:]
+    flat_locs = (locs[:, :, 1:] - locs[:, :, :1])[picked]
+    rel_loc0 = (locs[:, :, 0] - ego_locs[:, None, 0])[picked]
+    rel_ori0 = (oris - ego_oris)[picked]
+    locs_jitter, oris_jitter = jitter(flat_locs.size(0), locs.device)
+    other_locs = transform_points(flat_locs - locs_jitter[:, None], -rel_ori0 - oris_jitter)
+    where = torch.nonzero(picked)         # which sample's maps each picked vehicle is cropped from, and which of its actors it is
+    return dict(typs=picked, sample=where[:, 0].int(), actor=where[:, 1].int(), crop_locs=rel_loc0 + locs_jitter,
+                crop_oris=rel_ori0 + oris_jitter, other_locs=other_locs)
+
+
 def sample_others(self, ego_locs, locs, oris, typs):
     """Shared front half of BEVPlanner.forward / UniPlanner.forward (bev_planner_v2.py:74-101, uniplanner.py:58-86):
     pick the vehicles to train on and draw their crop jitter.  Returns None when no vehicle qualifies."""
-    ego_oris = oris[:, :1]
-    locs, oris = locs[:, 1:], oris[:, 1:]
-    typs = filter_cars(ego_locs, locs, typs[:, 1:] == 1)          # 1 = vehicle
+    typs = select_others(ego_locs, locs, typs)
     if int(typs.float().sum()) == 0:
-        return None, locs.size(1)
+        return None, locs.size(1) - 1
     typs = random_sample(typs, size=self.max_num_cars)
-    flat_locs = (locs[:, :, 1:] - locs[:, :, :1])[typs]
-    rel_loc0 = (locs[:, :, 0] - ego_locs[:, None, 0])[typs]
-    rel_ori0 = (oris - ego_oris)[typs]
-    K = flat_locs.size(0)
-    locs_jitter = (torch.rand((K, 2)) * 2 - 1).float().to(locs.device) * self.feature_x_jitter
-    locs_jitter[:, 1] = 0
-    oris_jitter = (torch.rand((K,)) * 2 - 1).float().to(oris.device) * self.feature_angle_jitter
-    other_locs = transform_points(flat_locs - locs_jitter[:, None], -rel_ori0 - oris_jitter)
-    sample = torch.nonzero(typs)[:, 0].int()      # which sample's maps each picked vehicle is cropped from
-    return dict(typs=typs, sample=sample, crop_locs=rel_loc0 + locs_jitter, crop_oris=rel_ori0 + oris_jitter, other_locs=other_locs), locs.size(1)
+
+    def jitter(K, device):
+        locs_jitter = (torch.rand((K, 2)) * 2 - 1).float().to(device) * self.feature_x_jitter
+        locs_jitter[:, 1] = 0
+        oris_jitter = (torch.rand((K,)) * 2 - 1).float().to(device) * self.feature_angle_jitter
+        return locs_jitter, oris_jitter
+    return picked_others(ego_locs, locs, oris, typs, jitter), locs.size(1) - 1
 
 
 class DecoderMixin:
