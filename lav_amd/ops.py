@@ -417,18 +417,8 @@ def eval_frame(acc: torch.Tensor, pred_bev: torch.Tensor, bev: torch.Tensor, mas
     any device (UniPlanner.infer_all returns CPU zeros then).  centre = the ego pixel (x, y).  Bit-identical to
     lav_amd.train.evaluate.eval_frame_numpy, which names the accumulator's slices (ACC).  Wrong shapes, dtypes or devices raise
     ValueError before anything is launched."""
-    def need(name, t, dtype, shape):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"eval_frame: {name} must be a tensor in HBM (cuda/hip device); lav_amd.ops has no CPU path "
-                             "(lav_amd.train.evaluate.eval_frame_numpy is the CPU specification)")
-        if t.device != acc.device:
-            raise ValueError(f"eval_frame: {name} is on {t.device}, the accumulator on {acc.device}")
-        if t.dtype != dtype or t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
-            raise ValueError(f"eval_frame: {name} must be {dtype} of shape {tuple('*' if s is None else s for s in shape)}, got {t.dtype} {tuple(t.shape)}")
-        return t.contiguous()
-    words = eval_acc_words(nbins)
-    if not isinstance(acc, torch.Tensor) or not acc.is_cuda or acc.dtype != torch.int64 or tuple(acc.shape) != (words,) or not acc.is_contiguous():
-        raise ValueError(f"eval_frame: acc must be a contiguous int64 tensor of {words} words in HBM")
+    _eval_section("eval_frame", acc, eval_acc_words(nbins), "acc")
+    need = _eval_tensor("eval_frame", "evaluate.eval_frame_numpy", acc, copy=True)
     pred_bev = need("pred_bev", pred_bev, torch.float32, (3, None, None))
     H, W = pred_bev.shape[1:]
     bev = need("bev", bev, torch.uint8, (None, H, W))
@@ -475,24 +465,40 @@ def eval_frame(acc: torch.Tensor, pred_bev: torch.Tensor, bev: torch.Tensor, mas
 EVAL_SEG_WORDS = 68            # lav_eval_seg's section: images, pixels, ignored, nonfinite, conf [8][8]
 
 
-def _eval_tensor(op, name, t, dtype, shape, like):
-    """eval_seg's / eval_scores' / eval_plans' check of one argument: in HBM, on the section's device, of the dtype and shape, contiguous."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError(f"{op}: {name} must be a tensor in HBM (cuda/hip device); lav_amd.ops has no CPU path "
-                         f"(lav_amd.train.{'evaluate_bev' if op == 'eval_plans' else 'evaluate_camera'}.{op}_numpy is the CPU specification)")
-    if t.device != like.device:
-        raise ValueError(f"{op}: {name} is on {t.device}, the accumulator on {like.device}")
-    if t.dtype != dtype or t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)):
-        raise ValueError(f"{op}: {name} must be {dtype} of shape {tuple('*' if s is None else s for s in shape)}, got {t.dtype} {tuple(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{op}: {name} must be contiguous (the kernel reads it where it is)")
-    return t
+def _eval_tensor(op, spec, like, copy=False):
+    """The evaluation kernels' check of one argument, need(name, t, dtype, shape) -> t: in HBM, on the device of the accumulator `like`, of
+    the dtype and shape (None: any size), and contiguous - or, with `copy`, made so.  `spec` names the CPU specification under
+    lav_amd.train.  The checks are most of what a launch costs with its wrapper (tools/eval_probe.py), hence a closure per call rather
+    than eight arguments per tensor, the device read once, and a loop over the sizes rather than any() of a generator."""
+    device = like.device
+
+    def need(name, t, dtype, shape):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{op}: {name} must be a tensor in HBM (cuda/hip device); lav_amd.ops has no CPU path "
+                             f"(lav_amd.train.{spec} is the CPU specification)")
+        if t.device != device:
+            raise ValueError(f"{op}: {name} is on {t.device}, the accumulator on {device}")
+        got = t.shape
+        ok = t.dtype == dtype and len(got) == len(shape)
+        if ok:
+            for want, size in zip(shape, got):
+                if want is not None and want != size:
+                    ok = False
+                    break
+        if not ok:
+            raise ValueError(f"{op}: {name} must be {dtype} of shape {tuple('*' if s is None else s for s in shape)}, got {t.dtype} {tuple(got)}")
+        if copy:
+            return t.contiguous()
+        if not t.is_contiguous():
+            raise ValueError(f"{op}: {name} must be contiguous (the kernel reads it where it is)")
+        return t
+    return need
 
 
-def _eval_section(op, acc_section, words):
+def _eval_section(op, acc_section, words, name="the section"):
     if (not isinstance(acc_section, torch.Tensor) or not acc_section.is_cuda or acc_section.dtype != torch.int64
             or tuple(acc_section.shape) != (words,) or not acc_section.is_contiguous()):
-        raise ValueError(f"{op}: the section must be a contiguous int64 tensor (or slice of one) of {words} words in HBM")
+        raise ValueError(f"{op}: {name} must be a contiguous int64 tensor (or slice of one) of {words} words in HBM")
 
 
 def eval_seg(acc_section: torch.Tensor, logits: torch.Tensor, labels: torch.Tensor, scale: int = 1) -> torch.Tensor:
@@ -502,7 +508,8 @@ def eval_seg(acc_section: torch.Tensor, logits: torch.Tensor, labels: torch.Tens
     followed by argmax (the first maximum), without the up-sampled logits.  Word for word lav_amd.train.evaluate_camera.eval_seg_numpy,
     which has the definitions.  Wrong shapes, dtypes or devices raise ValueError before anything is launched."""
     _eval_section("eval_seg", acc_section, EVAL_SEG_WORDS)
-    logits = _eval_tensor("eval_seg", "logits", logits, torch.float32, (None, None, None, None), acc_section)
+    need = _eval_tensor("eval_seg", "evaluate_camera.eval_seg_numpy", acc_section)
+    logits = need("logits", logits, torch.float32, (None, None, None, None))
     n, k, h, w = logits.shape
     scale = int(scale)
     if scale not in (1, 2, 4, 8):
@@ -511,7 +518,7 @@ def eval_seg(acc_section: torch.Tensor, logits: torch.Tensor, labels: torch.Tens
         raise ValueError(f"eval_seg: {k} classes (2 .. 8)")
     if n < 1 or h < 1 or w < 1 or h > 16384 or w > 16384 or n * h * w * scale * scale > 1 << 31:
         raise ValueError(f"eval_seg: logits {tuple(logits.shape)} at scale {scale}: at least one pixel, sides up to 16384, at most 2^31 label pixels")
-    labels = _eval_tensor("eval_seg", "labels", labels, torch.uint8, (n, h * scale, w * scale), acc_section)
+    labels = need("labels", labels, torch.uint8, (n, h * scale, w * scale))
     check(_lib.load().lav_eval_seg(_ptr(logits), _ptr(labels), n, k, h, w, scale, _ptr(acc_section), _stream()), "lav_eval_seg")
     return acc_section
 
@@ -524,11 +531,12 @@ def eval_scores(acc_section: torch.Tensor, scores: torch.Tensor, flags: torch.Te
     if not 1 <= nbins <= 1024:
         raise ValueError(f"eval_scores: {nbins} score bins (1 .. 1024)")
     _eval_section("eval_scores", acc_section, 6 + 2 * nbins)
-    scores = _eval_tensor("eval_scores", "scores", scores, torch.float32, (None,), acc_section)
+    need = _eval_tensor("eval_scores", "evaluate_camera.eval_scores_numpy", acc_section)
+    scores = need("scores", scores, torch.float32, (None,))
     n = scores.shape[0]
     if n < 1:
         raise ValueError("eval_scores: no scores")
-    flags = _eval_tensor("eval_scores", "flags", flags, torch.uint8, (n,), acc_section)
+    flags = need("flags", flags, torch.uint8, (n,))
     threshold = float(threshold)
     if threshold != threshold:
         raise ValueError("eval_scores: the threshold must be a number")
@@ -555,7 +563,7 @@ def eval_plans(acc: torch.Tensor, ego_plan: torch.Tensor, ego_cast: torch.Tensor
     an accumulator of another length raise ValueError before anything is launched."""
     if not isinstance(acc, torch.Tensor) or not acc.is_cuda or acc.dtype != torch.int64 or acc.dim() != 1 or not acc.is_contiguous():
         raise ValueError("eval_plans: acc must be a contiguous int64 tensor in HBM (lav_amd.train.evaluate_bev.eval_plans_numpy is the CPU specification)")
-    need = lambda name, t, dtype, shape: _eval_tensor("eval_plans", name, t, dtype, shape, acc)
+    need = _eval_tensor("eval_plans", "evaluate_bev.eval_plans_numpy", acc)
     if not isinstance(ego_plan, torch.Tensor) or ego_plan.dim() != 5:
         raise ValueError("eval_plans: ego_plan must be a float32 tensor of shape (B, I, 6, T, 2)")
     B, I, _, T, _ = ego_plan.shape

@@ -28,23 +28,19 @@ Every term is an integer before it is added, so the sums do not depend on the or
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import time
-
 import numpy as np
 import torch
 
-QUANTA = 1 << 20            # quanta per metre of the distance sums
-FAR = 2.0 ** 32             # metres; a distance that is not below it makes its plan / forecast "non-finite"
-NUM_CMDS = 6
+from .eval_common import (FAR, NUM_CMDS, PRECISION_NAMES, QUANTA, AccLayout, EvaluatorBase, SeededFrames, _np, _quanta, _ratio,  # noqa: F401
+                          average_precision, run_cli, synthetic_batches)                   # (re-exported: the tests and tools read them here)
+
 NBINS = 256
 MAX_DET = 20
 
 
-class Layout:
-    """The accumulator's named slices, in words of int64: lav_eval_frame's layout (csrc/eval_metrics.hip, include/lav_amd.h)."""
+class Layout(AccLayout):
+    """The accumulator's named slices, in words of int64: lav_eval_frame's layout (csrc/eval_metrics.hip, include/lav_amd.h).
+    seg [channel][tp, fp, fn]; det [class][tp, fp]; plan [cmd][frames, sum, final]; hist [class][tp, fp][bin]."""
     FIELDS = (("frames", ()), ("seg", (3, 3)), ("n_gt", (2,)), ("det", (2, 2)), ("plan", (NUM_CMDS, 3)), ("plan_nonfinite", ()),
               ("oth_matched", ()), ("oth_unmatched", ()), ("oth_nonfinite", ()), ("oth_min", ()), ("oth_top", ()), ("oth_top_final", ()))
 
@@ -52,28 +48,7 @@ class Layout:
         if not 1 <= int(nbins) <= 1024:
             raise ValueError(f"{nbins} score bins (1 .. 1024)")
         self.nbins = int(nbins)
-        self.fields, at = {}, 0
-        for name, shape in self.FIELDS + (("hist", (2, 2, self.nbins)),):
-            size = int(np.prod(shape, dtype=np.int64))
-            self.fields[name] = (slice(at, at + size), shape)
-            at += size
-        self.words = at
-
-    def __len__(self):
-        return self.words
-
-    def zeros(self) -> np.ndarray:
-        return np.zeros(self.words, np.int64)
-
-    def view(self, acc, name):
-        """The named slice of `acc`, shaped (seg [channel][tp, fp, fn]; det [class][tp, fp]; plan [cmd][frames, sum, final]; hist
-        [class][tp, fp][bin]); a view, so that adding to it adds to `acc`."""
-        sl, shape = self.fields[name]
-        return acc[sl].reshape(shape)
-
-    def named(self, acc) -> dict:
-        """The raw counters as nested lists (the JSON output)."""
-        return {name: self.view(np.asarray(acc), name).tolist() for name in self.fields}
+        super().__init__(self.FIELDS + (("hist", (2, 2, self.nbins)),))
 
     @classmethod
     def of(cls, acc) -> "Layout":
@@ -84,22 +59,6 @@ class Layout:
 
 
 ACC = Layout(NBINS)
-
-
-def _np(t, dtype):
-    if isinstance(t, torch.Tensor):
-        t = t.detach().cpu().numpy()
-    return np.ascontiguousarray(np.asarray(t), dtype=dtype)
-
-
-def _quanta(a, b):
-    """q_t of (T, 2) float32 points against their targets, or None where a distance is not below FAR."""
-    d = a.astype(np.float64) - b.astype(np.float64)
-    with np.errstate(all="ignore"):
-        dist = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
-        if not (dist < FAR).all():
-            return None
-        return np.rint(dist * float(QUANTA)).astype(np.int64)
 
 
 def eval_frame_numpy(acc, pred_bev, bev, mask, rows, locs, typs, n, ego_plan, ego_locs, cmd, other_cast, other_cmds, other_row, *, ppm,
@@ -194,36 +153,6 @@ def eval_frame_numpy(acc, pred_bev, bev, mask, rows, locs, typs, n, ego_plan, eg
     return acc
 
 
-def _ratio(a, b):
-    return None if b == 0 else float(a) / float(b)
-
-
-def average_precision(tp_hist, fp_hist, n_gt):
-    """AP from the score histograms.  The rule: walk the bins from the highest score down, accumulating true and false positives; after
-    every bin that holds a detection there is an operating point (recall = TP / n_gt, precision = TP / (TP + FP)); the precision at a
-    point is replaced by the largest precision at that or any LOWER-score point (the monotone envelope); AP is the area under the
-    resulting recall steps, sum over points of (recall - previous recall) * envelope precision, with recall 0 before the first point.
-    None when there is no ground truth."""
-    if n_gt == 0:
-        return None
-    tp = fp = 0
-    points = []
-    for b in range(len(tp_hist) - 1, -1, -1):
-        if tp_hist[b] == 0 and fp_hist[b] == 0:
-            continue
-        tp, fp = tp + int(tp_hist[b]), fp + int(fp_hist[b])
-        points.append((tp / n_gt, tp / (tp + fp)))
-    env = 0.0
-    for i in range(len(points) - 1, -1, -1):
-        env = max(env, points[i][1])
-        points[i] = (points[i][0], env)
-    ap, prev = 0.0, 0.0
-    for recall, prec in points:
-        ap += (recall - prev) * prec
-        prev = recall
-    return ap
-
-
 def summarise(acc, num_plan: int = 20) -> dict:
     """Metrics from an accumulator (array or tensor); a zero denominator gives None, never a NaN.  Distances in metres:
     sum of q / (2^20 * num_plan * count) for the averages (ADE), final q / (2^20 * count) for the final displacement (FDE)."""
@@ -259,15 +188,6 @@ def summarise(acc, num_plan: int = 20) -> dict:
 PRECISIONS = ("f16x3", "bf16x6", "f32")
 
 
-def _precision_code(name):
-    from .. import _lib, ops
-    if name is None:
-        return ops.frame_precision()
-    if isinstance(name, int):
-        return name
-    return {"f16x3": _lib.CONV_F16X3, "bf16x6": _lib.CONV_BF16X6, "f32": _lib.CONV_F32}[name]
-
-
 def forecast_rows(infer, rows: np.ndarray, dets1) -> np.ndarray:
     """For each forecast UniPlanner.infer_all makes of `dets1` (= det_decode_fast(rows)[0][1]) the row of rows[1] it came from.
     det_decode_fast keeps rows in order and others_from_detections drops the ego's own box, so the forecasts are the kept detections
@@ -284,15 +204,14 @@ def forecast_rows(infer, rows: np.ndarray, dets1) -> np.ndarray:
     return np.asarray(out, np.int32)
 
 
-class Evaluator:
+class Evaluator(EvaluatorBase):
     """Runs frames of loader batches through the student and accumulates their metrics.
 
         ev = Evaluator(lav)                  # a lav_amd.train.LAV of stage "lidar", or (lidar_model, uniplanner)
         ev.run(loader, max_frames=None)      # -> frames evaluated
         ev.counters()                        # the accumulator, read once
 
-    device "cpu" keeps the accumulator on the host and calls eval_frame_numpy on copies of the tensors (the models still run on the
-    GPU: there is no CPU inference path); that is how the tests capture what the kernel saw."""
+    device "cpu": eval_frame_numpy on the host (EvaluatorBase)."""
 
     def __init__(self, lav_or_modules, precision=None, device=None, *, cfg=None, match_radius=2.0, threshold=0.5, min_score=0.1,
                  det_score=0.2, nbins=NBINS):
@@ -304,20 +223,17 @@ class Evaluator:
             cfg = cfg or TrainConfig()
         else:
             lidar_model, uniplanner, cfg = lav_or_modules.lidar_model, lav_or_modules.uniplanner, cfg or lav_or_modules.cfg
-        self.model_device = next(lidar_model.parameters()).device
-        self.device = torch.device(device) if device is not None else self.model_device
-        self.infer = InferModel(lidar_model.eval(), uniplanner.eval(), 1.5, 2.4, self.model_device, precision=_precision_code(precision))
+        self.nbins = int(nbins)
+        super().__init__(lidar_model, Layout(self.nbins), precision, device)
+        self.infer = InferModel(self.model, uniplanner.eval(), 1.5, 2.4, self.model_device, precision=self.code)
         self.ppm = float(cfg.pixels_per_meter)
         H, W = int((cfg.max_x - cfg.min_x) * cfg.pixels_per_meter), int((cfg.max_y - cfg.min_y) * cfg.pixels_per_meter)
         # LAV.bev_center
         self.centre = (W / 2 + (cfg.min_y + cfg.max_y) / 2 * cfg.pixels_per_meter, H / 2 + (cfg.min_x + cfg.max_x) / 2 * cfg.pixels_per_meter)
         self.mask = (build_seg_mask(h=H, w=W, cx=self.centre[0], cy=self.centre[1]) > 0).to(torch.uint8).to(self.model_device)
         self.num_plan = int(cfg.num_plan)
-        self.nbins = int(nbins)
         self.kw = dict(ppm=self.ppm, centre=self.centre, radius_px=float(match_radius) * self.ppm, threshold=float(threshold),
                        min_score=float(min_score), det_score=float(det_score), nbins=self.nbins)
-        self.layout = Layout(self.nbins)
-        self.acc = torch.zeros(len(self.layout), dtype=torch.int64, device=self.device)
         self.frames = 0
         self._batch = None
 
@@ -349,45 +265,21 @@ class Evaluator:
             _, ego_plan, _, other_cast, other_cmds = up.infer_all(features[0], dets[1], cmd, b["nxps"][i], amax=ops.amax_of(features))
         n = min(b["n"][i], b["locs"].shape[1])
         args = (pred_bev[0], b["bev"][i], self.mask, rows, b["locs"][i], b["typs"][i], n, ego_plan, b["ego_locs"][i], cmd, other_cast, other_cmds)
-        if self.device.type == "cpu":
-            acc = self.acc.numpy()
-            eval_frame_numpy(acc, *args, other_row, **self.kw)
-        else:
-            ops.eval_frame(self.acc, *args, torch.from_numpy(other_row).to(self.acc.device), **self.kw)
+        self._add("eval_frame", eval_frame_numpy, None, *args, torch.from_numpy(other_row).to(self.device), **self.kw)
         self.frames += 1
 
     def run(self, batches, max_frames=None) -> int:
-        for batch in batches:
-            if max_frames is not None and self.frames >= max_frames:
-                break
-            for i in range(self.upload(batch)):
-                if max_frames is not None and self.frames >= max_frames:
-                    break
+        for batch, left in self._budget(batches, max_frames, lambda: self.frames):
+            for i in range(self.upload(batch))[:left]:
                 self.frame(i)
         return self.frames
 
-    def counters(self) -> np.ndarray:
-        return self.acc.cpu().numpy()
+    def precision(self) -> str:
+        """The arithmetic asked for: InferModel runs every engine at it."""
+        return PRECISION_NAMES.get(self.code, "default")
 
 
 # ------------------------------------------------------------------------------------------------------------ command line
-class SeededFrames(torch.utils.data.Dataset):
-    """dataset[idx] with NumPy's and torch's generators seeded from (seed, idx) first: what a sample draws (the point shuffle, once the
-    jitters are 0) then depends on the sample alone, not on which worker loads it or on what was loaded before."""
-
-    def __init__(self, dataset, seed):
-        self.dataset, self.seed = dataset, int(seed)
-
-    def __len__(self):
-        return len(self.dataset)
-
-    def __getitem__(self, idx):
-        s = (self.seed * 1000003 + int(idx) * 7919 + 12345) % (1 << 32)
-        np.random.seed(s)
-        torch.manual_seed(s)
-        return self.dataset[idx]
-
-
 def held_out_frames(config_path, data_dir=None, seed=2021):
     """The 'temporal_lidar_painted' loader's dataset over `data_dir` (default: the config's) with every augmentation at 0, seeded
     per sample."""
@@ -397,80 +289,35 @@ def held_out_frames(config_path, data_dir=None, seed=2021):
     return SeededFrames(ds, seed)
 
 
-def _synthetic_batches(frames, seed, max_points, batch_size):
+def _build(args, cfg, device):
+    from .lav import LAV
+    ck = {k: torch.load(getattr(args, k), map_location="cpu") for k in TOOL["checkpoints"] if getattr(args, k)}
+    lav = LAV(cfg, device, what="lidar", checkpoints=ck)
+    lav.student.eval()
+    return lav
+
+
+def _batches(args, cfg):
     from .synthetic import synthetic_lidar_batch
-    done = 0
-    while done < frames:
-        b = min(batch_size, frames - done)
-        yield synthetic_lidar_batch(b, seed=seed + 1009 * done, max_points=max_points)
-        done += b
+    if args.synthetic:
+        return synthetic_batches(synthetic_lidar_batch, args.frames, args.batch_size, args.seed, max_points=args.max_points or cfg.max_lidar_points)
+    return held_out_frames(args.config_path, args.data_dir, args.seed)
+
+
+TOOL = dict(
+    name="eval_full_v2", what="eval_full", about="open-loop metrics of a LiDAR student + planner checkpoint on recorded routes", unit="frames",
+    checkpoints=dict(lidar="lidar_model_dir", uniplanner="uniplanner_dir", bev="bev_model_dir"), precisions=PRECISIONS, batch_size=8, frames=8,
+    synthetic="synthetic_lidar_batch samples",
+    flags=[("--max-points", dict(type=int, default=None, help="--synthetic: points per cloud (default: the config's max_lidar_points)")),
+           ("--match-radius", dict(type=float, default=2.0, help="metres within which a detection matches a ground-truth actor"))],
+    build=_build, batches=_batches, make_evaluator=lambda lav, name, args: Evaluator(lav, precision=name, match_radius=args.match_radius),
+    line=lambda ev, acc, args, cfg: dict(match_radius_m=args.match_radius, summary=summarise(acc, cfg.num_plan)),
+    keys=("what", "precision", "data", "frames_per_s", "match_radius_m", "summary", "counters"))
 
 
 def main(argv=None):
     """eval_full_v2.py: one JSON line per precision - the summary, the raw counters and the frames per second of the evaluation."""
-    from .lav import LAV
-    from .run import load_config, resolve_checkpoints
-    ap = argparse.ArgumentParser(description="open-loop metrics of a LiDAR student + planner checkpoint on recorded routes")
-    ap.add_argument("--config-path", default=None, help="the reference's config_v2.yaml; required unless --synthetic")
-    ap.add_argument("--data-dir", default=None, help="held-out routes; overrides the config's data_dir")
-    ap.add_argument("--lidar", default=None, help="lidar_*.th (default: the config's lidar_model_dir)")
-    ap.add_argument("--uniplanner", default=None, help="uniplanner_*.th (default: the config's uniplanner_dir)")
-    ap.add_argument("--bev", default=None, help="bev_*.th (default: the config's bev_model_dir)")
-    ap.add_argument("--precision", default=None, choices=PRECISIONS + ("all",),
-                    help="arithmetic of the convolutions (default: the frame's); all: the same frames three times, three summaries")
-    ap.add_argument("--max-frames", type=int, default=None)
-    ap.add_argument("--num-workers", type=int, default=4)
-    ap.add_argument("--batch-size", type=int, default=8, help="loader batch; inference is per frame")
-    ap.add_argument("--seed", type=int, default=2021)
-    ap.add_argument("--synthetic", action="store_true", help="synthetic_lidar_batch samples and seeded random weights (smoke runs)")
-    ap.add_argument("--frames", type=int, default=8, help="--synthetic: how many frames")
-    ap.add_argument("--max-points", type=int, default=None, help="--synthetic: points per cloud (default: the config's max_lidar_points)")
-    ap.add_argument("--match-radius", type=float, default=2.0, help="metres within which a detection matches a ground-truth actor")
-    ap.add_argument("--out", default=None, metavar="FILE", help="also write the JSON there")
-    args = ap.parse_args(argv)
-    if not args.synthetic and not args.config_path:
-        raise SystemExit("recorded routes are read from --data-dir or the data_dir of --config-path (or pass --synthetic)")
-    if not torch.cuda.is_available():
-        raise SystemExit("eval_full_v2: no GPU visible; the models have no CPU inference path")
-    device = torch.device("cuda", torch.cuda.current_device())
-    keys = dict(lidar="lidar_model_dir", uniplanner="uniplanner_dir", bev="bev_model_dir")
-    for name, key in keys.items():
-        path = getattr(args, name)
-        if path and not os.path.isfile(path):
-            raise SystemExit(f"--{name} {path}: no such file (the checkpoint the config calls `{key}`)")
-    args.perceive_only = args.motion_only = False
-    paths = resolve_checkpoints("lidar", args)
-    ck = {k: torch.load(v, map_location="cpu") for k, v in paths.items() if v}
-    cfg = load_config(None if args.synthetic and not args.config_path else args.config_path, seed=args.seed)
-    torch.manual_seed(cfg.seed)
-    lav = LAV(cfg, device, what="lidar", checkpoints=ck)
-    lav.student.eval()
-    if args.synthetic:
-        data = f"{args.frames} synthetic frames"
-        batches = lambda: _synthetic_batches(args.frames, args.seed, args.max_points or cfg.max_lidar_points, args.batch_size)
-    else:
-        frames = held_out_frames(args.config_path, args.data_dir, args.seed)
-        if len(frames) == 0:
-            raise SystemExit(f"no recorded frames under {args.data_dir or 'the data_dir of ' + args.config_path}")
-        data = f"{len(frames)} recorded frames"
-        batches = lambda: torch.utils.data.DataLoader(frames, batch_size=args.batch_size, shuffle=False, drop_last=False, num_workers=args.num_workers)
-    lines = []
-    for name in (PRECISIONS if args.precision == "all" else (args.precision,)):
-        ev = Evaluator(lav, precision=name, match_radius=args.match_radius)
-        t0 = time.perf_counter()
-        n = ev.run(batches(), args.max_frames)
-        acc = ev.counters()                      # (the one copy; it also waits for the last launch)
-        dt = time.perf_counter() - t0
-        code = ev.infer.precision
-        line = dict(what="eval_full", precision=name or {3: "f16x3", 2: "bf16x6", 1: "f32"}.get(code, "default"), data=data, frames_per_s=round(n / max(dt, 1e-9), 2),
-                    match_radius_m=args.match_radius, summary=summarise(acc, cfg.num_plan), counters=ev.layout.named(acc))
-        lines.append(line)
-        print(json.dumps(line), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
-    return lines
+    return run_cli(TOOL, argv)
 
 
 if __name__ == "__main__":

@@ -12,7 +12,7 @@ nothing to pin it to.  What is pinned: the kernel to this specification, the spe
 (tests/test_eval_bev_host.py), infer_batch to BEVPlanner.forward with its jitters at zero, bit for bit.
 
 Definitions (DESIGN 4.7i has the reasons).  S = I + 1 stages, I = num_plan_iter: stage 0 is the cast at the frame's command, stage s the
-s-th refinement of the plan at the frame's command.  q_t = rint(sqrt(dx^2 + dy^2) * 2^20), float64 (evaluate._quanta).
+s-th refinement of the plan at the frame's command.  q_t = rint(sqrt(dx^2 + dy^2) * 2^20), float64 (eval_common._quanta).
   frames, bad_cmd   frames seen; frames whose command is outside 0 .. 5, which add to nothing else.
   plan              [bra != 0][stage][cmd][frames, sum_t q_t, q_{T-1}] against ego_locs[:, 1:].
   plan_nonfinite    [stage]: a stage with a distance that is not below 2^32 m (NaN, Inf) counts here and not in `plan`; the stages of a
@@ -28,54 +28,28 @@ any order, given the teacher's outputs; BevEvaluator.run keeps those independent
 """
 from __future__ import annotations
 
-import argparse
-import json
-import os
-import time
-
 import numpy as np
 import torch
 
-from .evaluate import FAR, NUM_CMDS, QUANTA, SeededFrames, _np, _quanta, _ratio  # noqa: F401  (FAR: the rule's other constant, for readers)
+from .eval_common import FAR, NUM_CMDS, QUANTA, AccLayout, EvaluatorBase, SeededFrames, _np, _quanta, _ratio, run_cli, synthetic_batches  # noqa: F401  (FAR: the rule's other constant, for readers)
 
 MAX_ITERS = 8
 OTHERS = ("ahead", "all")
 
 
-class PlanLayout:
+class PlanLayout(AccLayout):
     """The accumulator's named slices, in words of int64: lav_eval_plans' layout for `iters` plan iterations (csrc/eval_plans.hip,
-    include/lav_amd.h), 57 + 37 (iters + 1) words."""
+    include/lav_amd.h), 57 + 37 (iters + 1) words.  plan [bra][stage][cmd][frames, sum, final]; cmd_conf [cmd][predicted]; oth [min sum,
+    top sum, top final, min final]."""
 
     def __init__(self, iters: int):
         if not 1 <= int(iters) <= MAX_ITERS:
             raise ValueError(f"{iters} plan iterations (1 .. {MAX_ITERS})")
         self.iters = int(iters)
         self.stages = S = self.iters + 1
-        spec = (("frames", ()), ("bad_cmd", ()), ("plan", (2, S, NUM_CMDS, 3)), ("plan_nonfinite", (S,)), ("cmd_conf", (NUM_CMDS, NUM_CMDS)),
-                ("others", ()), ("oth_nonfinite", ()), ("oth", (4,)), ("oth_min_mode", (NUM_CMDS,)), ("oth_top_mode", (NUM_CMDS,)),
-                ("oth_top_is_min", ()))
-        self.fields, at = {}, 0
-        for name, shape in spec:
-            size = int(np.prod(shape, dtype=np.int64))
-            self.fields[name] = (slice(at, at + size), shape)
-            at += size
-        self.words = at
-
-    def __len__(self):
-        return self.words
-
-    def zeros(self) -> np.ndarray:
-        return np.zeros(self.words, np.int64)
-
-    def view(self, acc, name):
-        """The named slice of `acc`, shaped (plan [bra][stage][cmd][frames, sum, final]; cmd_conf [cmd][predicted]; oth [min sum, top sum,
-        top final, min final]); a view, so that adding to it adds to `acc`."""
-        sl, shape = self.fields[name]
-        return acc[sl].reshape(shape)
-
-    def named(self, acc) -> dict:
-        """The raw counters as nested lists (the JSON output)."""
-        return {name: self.view(np.asarray(acc), name).tolist() for name in self.fields}
+        super().__init__((("frames", ()), ("bad_cmd", ()), ("plan", (2, S, NUM_CMDS, 3)), ("plan_nonfinite", (S,)), ("cmd_conf", (NUM_CMDS, NUM_CMDS)),
+                          ("others", ()), ("oth_nonfinite", ()), ("oth", (4,)), ("oth_min_mode", (NUM_CMDS,)), ("oth_top_mode", (NUM_CMDS,)),
+                          ("oth_top_is_min", ())))
 
     @classmethod
     def of(cls, acc) -> "PlanLayout":
@@ -186,16 +160,15 @@ def summarise(acc, num_plan: int = 20) -> dict:
 PRECISIONS = ("f16x3", "bf16x6", "f32")
 
 
-class BevEvaluator:
+class BevEvaluator(EvaluatorBase):
     """Runs loader batches (train_bev's tuple) through the teacher and accumulates their metrics, one launch per batch.
 
         ev = BevEvaluator(lav)               # a lav_amd.train.LAV of stage "bev", or a BEVPlanner
         ev.run(loader, max_frames=None)      # -> frames evaluated
         ev.counters()                        # the accumulator, read once
 
-    others: "ahead" scores the vehicles that pass filter_cars (what the teacher was trained on), "all" every vehicle.  device "cpu"
-    keeps the accumulator on the host and calls eval_plans_numpy on copies of what the kernel would have been handed (the model still
-    runs on the GPU: there is no CPU inference path); that is how the tests capture what the kernel saw.
+    others: "ahead" scores the vehicles that pass filter_cars (what the teacher was trained on), "all" every vehicle.  device "cpu":
+    eval_plans_numpy on the host (EvaluatorBase).
 
     run() regroups the loader's frames into runs of `frames_per_forward`, whatever the loader's batch was: the convolution engines and
     lav_gru_plan choose their schedules (split-K, which plan kernel) by batch size, which moves the teacher's outputs in their last
@@ -203,23 +176,16 @@ class BevEvaluator:
     setting if a route's counters are to be the route's.  upload() + batch() run whatever batch they are given."""
 
     def __init__(self, bev_planner, precision=None, device=None, others="ahead", frames_per_forward=8):
-        from .evaluate_camera import _precision_code
         model = getattr(bev_planner, "bev_planner", bev_planner)
         if others not in OTHERS:
             raise ValueError(f"others={others!r} (ahead or all)")
-        self.model = model.eval()
-        self.model_device = next(model.parameters()).device
-        self.device = torch.device(device) if device is not None else self.model_device
-        self.code = _precision_code(precision)
-        self.others = others
         if int(frames_per_forward) < 1:
             raise ValueError(f"frames_per_forward={frames_per_forward}")
+        super().__init__(model, PlanLayout(int(model.num_plan_iter)), precision, device)
+        self.others = others
         self.group = int(frames_per_forward)
         self.num_plan = int(model.num_plan)
-        self.layout = PlanLayout(int(model.num_plan_iter))
-        self.acc = torch.zeros(len(self.layout), dtype=torch.int64, device=self.device)
         self.frames = 0
-        self.in_force = set()
         self._batch = None
 
     def upload(self, batch, limit=None):
@@ -244,14 +210,10 @@ class BevEvaluator:
     @torch.no_grad()
     def batch(self):
         """The uploaded batch: the teacher's forward, then the metrics launch."""
-        from .. import ops
         b, out = self._batch, self.infer()
         args = (out.ego_plan.contiguous(), out.ego_cast.contiguous(), out.ego_cmds.contiguous(), b["ego_locs"], b["cmds"], b["bras"],
                 out.other_cast.contiguous(), out.other_cmds.contiguous(), out.other_locs.contiguous())
-        if self.device.type == "cpu":
-            eval_plans_numpy(self.acc.numpy(), *args)
-        else:
-            ops.eval_plans(self.acc, *args)
+        self._add("eval_plans", eval_plans_numpy, None, *args)
         self.frames += int(b["cmds"].shape[0])
 
     def _groups(self, batches, budget):
@@ -276,13 +238,6 @@ class BevEvaluator:
             self.batch()
         return self.frames
 
-    def precision(self) -> str:
-        """The arithmetic of the convolutions that was in force over the batches so far."""
-        return "+".join(sorted(self.in_force)) or "none"
-
-    def counters(self) -> np.ndarray:
-        return self.acc.cpu().numpy()
-
 
 # ------------------------------------------------------------------------------------------------------------ command line
 def held_out_bev_frames(config_path, data_dir=None, seed=2021):
@@ -293,96 +248,33 @@ def held_out_bev_frames(config_path, data_dir=None, seed=2021):
     return SeededFrames(ds, seed)
 
 
-def _synthetic_batches(frames, seed, batch_size, num_plan):
+def _build(args, cfg, device):
+    from .lav import LAV
+    return LAV(cfg, device, what="bev", checkpoints={"bev": torch.load(args.bev, map_location="cpu")} if args.bev else {})
+
+
+def _batches(args, cfg):
     from .synthetic import synthetic_bev_batch
-    done = 0
-    while done < frames:
-        b = min(batch_size, frames - done)
-        yield synthetic_bev_batch(b, seed=seed + 1009 * done, num_plan=num_plan)
-        done += b
-
-
-def _checkpoint(args):
-    """The teacher's file: --bev, else the config's `bev_model_dir`; None for --synthetic without the flag (seeded weights).  A named
-    file that does not exist is an error, never a silent fall back to seeded weights."""
-    if args.bev:
-        if not os.path.isfile(args.bev):
-            raise SystemExit(f"--bev {args.bev}: no such file (the checkpoint the config calls `bev_model_dir`)")
-        return args.bev
     if args.synthetic:
-        return None
-    import yaml
-    with open(args.config_path, "r") as f:
-        rel = (yaml.safe_load(f) or {}).get("bev_model_dir")
-    if not rel:
-        raise SystemExit(f"{args.config_path} has no `bev_model_dir` and --bev was not given")
-    cands = [rel, os.path.join(os.path.dirname(os.path.abspath(args.config_path)), rel)]
-    hit = next((c for c in cands if os.path.isfile(c)), None)
-    if hit is None:
-        raise SystemExit(f"checkpoint `bev_model_dir: {rel}` of {args.config_path} not found (tried {cands}); pass --bev PATH, or --synthetic "
-                         "for seeded random weights on synthetic batches")
-    return hit
+        return synthetic_batches(synthetic_bev_batch, args.frames, args.batch_size, args.seed, num_plan=cfg.num_plan)
+    return held_out_bev_frames(args.config_path, args.data_dir, args.seed)
+
+
+TOOL = dict(
+    name="eval_bev_v2", about="held-out metrics of a privileged BEV teacher checkpoint (bev_*.th) on recorded routes", unit="frames",
+    checkpoints=dict(bev="bev_model_dir"), precisions=PRECISIONS, batch_size=8, frames=8, synthetic="synthetic_bev_batch samples",
+    help=dict(batch_size="loader batch; the teacher's forward and the metrics launch take 8 frames at a time whatever it is, so that it cannot "
+                         "move the counters"),
+    flags=[("--others", dict(default="ahead", choices=OTHERS,
+                             help="which vehicles' forecasts are scored: those ahead of the ego (what the teacher was trained on) or all"))],
+    build=_build, batches=_batches, make_evaluator=lambda lav, name, args: BevEvaluator(lav, precision=name, others=args.others),
+    line=lambda ev, acc, args, cfg: dict(others=args.others, summary=summarise(acc, cfg.num_plan)),
+    keys=("what", "precision", "asked", "others", "data", "batch_size", "frames_per_s", "summary", "counters"))
 
 
 def main(argv=None):
-    """eval_bev_v2.py: one JSON line per precision - the summary, the raw counters, the frames per second of the evaluation (the whole
-    run's, engine build and loader start-up included) and the arithmetic that was in force.  Single process, no jitter, the loader in
-    order and to its last sample."""
-    from .lav import LAV
-    from .run import load_config
-    ap = argparse.ArgumentParser(description="held-out metrics of a privileged BEV teacher checkpoint (bev_*.th) on recorded routes")
-    ap.add_argument("--config-path", default=None, help="the reference's config_v2.yaml; required unless --synthetic")
-    ap.add_argument("--data-dir", default=None, help="held-out routes; overrides the config's data_dir")
-    ap.add_argument("--bev", default=None, help="bev_*.th (default: the config's bev_model_dir)")
-    ap.add_argument("--precision", default=None, choices=PRECISIONS + ("all",),
-                    help="arithmetic of the convolutions (default: the frame's); all: the same frames three times, three summaries")
-    ap.add_argument("--others", default="ahead", choices=OTHERS,
-                    help="which vehicles' forecasts are scored: those ahead of the ego (what the teacher was trained on) or all")
-    ap.add_argument("--batch-size", type=int, default=8, help="loader batch; the teacher's forward and the metrics launch take 8 frames at a time "
-                    "whatever it is, so that it cannot move the counters")
-    ap.add_argument("--max-frames", type=int, default=None)
-    ap.add_argument("--num-workers", type=int, default=4)
-    ap.add_argument("--seed", type=int, default=2021)
-    ap.add_argument("--synthetic", action="store_true", help="synthetic_bev_batch samples and seeded random weights (smoke runs)")
-    ap.add_argument("--frames", type=int, default=8, help="--synthetic: how many frames")
-    ap.add_argument("--out", default=None, metavar="FILE", help="also write the JSON there")
-    args = ap.parse_args(argv)
-    if not args.synthetic and not args.config_path:
-        raise SystemExit("recorded routes are read from --data-dir or the data_dir of --config-path (or pass --synthetic)")
-    if args.batch_size < 1:
-        raise SystemExit(f"--batch-size {args.batch_size}")
-    path = _checkpoint(args)
-    if not torch.cuda.is_available():
-        raise SystemExit("eval_bev_v2: no GPU visible; the models have no CPU inference path")
-    device = torch.device("cuda", torch.cuda.current_device())
-    cfg = load_config(None if args.synthetic and not args.config_path else args.config_path, seed=args.seed)
-    torch.manual_seed(cfg.seed)
-    lav = LAV(cfg, device, what="bev", checkpoints={"bev": torch.load(path, map_location="cpu")} if path else {})
-    if args.synthetic:
-        data = f"{args.frames} synthetic frames"
-        batches = lambda: _synthetic_batches(args.frames, args.seed, args.batch_size, cfg.num_plan)
-    else:
-        frames = held_out_bev_frames(args.config_path, args.data_dir, args.seed)
-        if len(frames) == 0:
-            raise SystemExit(f"no recorded frames under {args.data_dir or 'the data_dir of ' + args.config_path}")
-        data = f"{len(frames)} recorded frames"
-        batches = lambda: torch.utils.data.DataLoader(frames, batch_size=args.batch_size, shuffle=False, drop_last=False, num_workers=args.num_workers)
-    lines = []
-    for name in (PRECISIONS if args.precision == "all" else (args.precision,)):
-        ev = BevEvaluator(lav, precision=name, others=args.others)
-        t0 = time.perf_counter()
-        n = ev.run(batches(), args.max_frames)
-        acc = ev.counters()                      # (the one copy; it also waits for the last launch)
-        dt = time.perf_counter() - t0
-        line = dict(what="eval_bev_v2", precision=ev.precision(), asked=name, others=args.others, data=data, batch_size=args.batch_size,
-                    frames_per_s=round(n / max(dt, 1e-9), 2), summary=summarise(acc, cfg.num_plan), counters=ev.layout.named(acc))
-        lines.append(line)
-        print(json.dumps(line), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
-    return lines
+    """eval_bev_v2.py: one JSON line per precision, with the arithmetic that was in force (eval_common.run_cli)."""
+    return run_cli(TOOL, argv)
 
 
 if __name__ == "__main__":

@@ -34,16 +34,12 @@ LAV_CONV_PRECISION=f32.
 """
 from __future__ import annotations
 
-import argparse
-import json
 import os
-import sys
-import time
 
 import numpy as np
 import torch
 
-from .evaluate import _np, _ratio, average_precision
+from .eval_common import AccLayout, EvaluatorBase, PRECISION_NAMES, _np, _ratio, average_precision, run_cli, synthetic_batches
 
 SEG_WORDS = 68
 MAX_CLASSES = 8
@@ -73,17 +69,13 @@ def fields(section, kind) -> dict:
         spec = _score_fields(nbins)
     else:
         raise ValueError(f"section kind {kind!r}")
-    out, at = {}, 0
-    for name, shape in spec:
-        size = int(np.prod(shape, dtype=np.int64))
-        out[name] = section[at:at + size].reshape(shape)
-        at += size
-    return out
+    return AccLayout(((kind, kind, spec),), sectioned=True).fields(section, kind)
 
 
-class CameraLayout:
-    """The sections of one int64 accumulator, in words: one 68-word section per name in `maps` (lav_eval_seg's) and, when `nbins` is
-    given, one of 6 + 2 nbins words called "scores" (lav_eval_scores's).  csrc/eval_camera.hip and include/lav_amd.h have the words."""
+class CameraLayout(AccLayout):
+    """The sections of one int64 accumulator, in words: one 68-word section per name in `maps` (lav_eval_seg's, kind "seg") and, when
+    `nbins` is given, one of 6 + 2 nbins words called "scores" (lav_eval_scores's, kind SCORES).  csrc/eval_camera.hip and
+    include/lav_amd.h have the words."""
 
     def __init__(self, maps, nbins=NBINS):
         if nbins is not None and not 1 <= int(nbins) <= 1024:
@@ -92,45 +84,8 @@ class CameraLayout:
         self.nbins = None if nbins is None else int(nbins)
         if SCORES in self.maps or len(set(self.maps)) != len(self.maps):
             raise ValueError(f"section names {self.maps}")
-        self.sections, at = {}, 0
-        for name in self.maps:
-            self.sections[name] = slice(at, at + SEG_WORDS)
-            at += SEG_WORDS
-        if self.nbins is not None:
-            self.sections[SCORES] = slice(at, at + SCORE_HEAD + 2 * self.nbins)
-            at += SCORE_HEAD + 2 * self.nbins
-        self.words = at
-
-    def __len__(self):
-        return self.words
-
-    def zeros(self) -> np.ndarray:
-        return np.zeros(self.words, np.int64)
-
-    def view(self, acc, name):
-        """The named section of `acc` (array or tensor): a view, so that adding to it adds to `acc`."""
-        return acc[self.sections[name]]
-
-    def kind(self, name) -> str:
-        """What `fields` is to make of the named section: SCORES for the score section, "seg" for a map's."""
-        return SCORES if name == SCORES else "seg"
-
-    def fields(self, acc, name) -> dict:
-        """The named, shaped views of the named section of `acc` (array)."""
-        return fields(self.view(acc, name), self.kind(name))
-
-    def named(self, acc) -> dict:
-        """The raw counters as nested lists per section (the JSON output)."""
-        acc = np.asarray(acc)
-        return {name: {k: v.tolist() for k, v in self.fields(acc, name).items()} for name in self.sections}
-
-    def unnamed(self, counters: dict) -> np.ndarray:
-        """The accumulator `named` was made from."""
-        acc = self.zeros()
-        for name in self.sections:
-            for k, v in self.fields(acc, name).items():
-                v[...] = np.asarray(counters[name][k], np.int64)
-        return acc
+        scores = () if self.nbins is None else ((SCORES, SCORES, _score_fields(self.nbins)),)
+        super().__init__(tuple((name, "seg", SEG_FIELDS) for name in self.maps) + scores, sectioned=True)
 
 
 SEG = CameraLayout(("seg",), nbins=None)
@@ -237,15 +192,6 @@ def _env_f32():
     return os.environ.get("LAV_CONV_PRECISION", "") in ("f32", "fp32")
 
 
-def _precision_code(name):
-    from .. import _lib, ops
-    if name is None:
-        return ops.frame_precision()
-    if isinstance(name, int):
-        return name
-    return {"f16x3": _lib.CONV_F16X3, "bf16x6": _lib.CONV_BF16X6, "f32": _lib.CONV_F32}[name]
-
-
 def trunk_arithmetic(resnet, code: int) -> str:
     """What the brake net's ResNet-18 ran at under ops.precision(code), read off the engine that call built
     (ResNet._engine: one engine per precision): the `precision` every packed layer's descriptor carries - 0 being the library's
@@ -257,7 +203,7 @@ def trunk_arithmetic(resnet, code: int) -> str:
         raise RuntimeError(f"the trunk has no engine for precision code {code}: it did not run under it")
     layers = [e["stem"]] + [l for b in e["blocks"] for l in (b["c1"], b["c2"], b["down"]) if l is not None]
     default = "f32" if _env_f32() else "bf16x6"
-    names = {{3: "f16x3", 2: "bf16x6", 1: "f32"}.get(int(l.desc.precision), default) for l in layers}
+    names = {PRECISION_NAMES.get(int(l.desc.precision), default) for l in layers}
     if names == {"f16x3"} and not e["f16"]:
         names = {"f16x3 without its scale hand-off"}
     return "/".join(sorted(names))
@@ -282,36 +228,7 @@ def erfnet_arithmetic(erfnet, shape) -> str:
 
 
 # ------------------------------------------------------------------------------------------------------------ the evaluators
-class _Evaluator:
-    """What the two evaluators share: where the accumulator lives.  device "cpu" keeps it on the host and calls the NumPy
-    specifications on copies of the tensors the kernels would have read (the models still run on the GPU: there is no CPU inference
-    path); that is how the tests capture what the kernels saw."""
-
-    def __init__(self, model, layout, precision, device):
-        self.model = model.eval()
-        self.model_device = next(model.parameters()).device
-        self.device = torch.device(device) if device is not None else self.model_device
-        self.code = _precision_code(precision)
-        self.layout = layout
-        self.acc = torch.zeros(len(layout), dtype=torch.int64, device=self.device)
-        self.in_force = set()
-
-    def _seg(self, name, logits, labels, scale):
-        from .. import ops
-        if self.device.type == "cpu":
-            eval_seg_numpy(self.layout.view(self.acc.numpy(), name), logits, labels, scale)
-        else:
-            ops.eval_seg(self.layout.view(self.acc, name), logits, labels, scale)
-
-    def precision(self) -> str:
-        """The arithmetic that was in force over the calls so far."""
-        return "+".join(sorted(self.in_force)) or "none"
-
-    def counters(self) -> np.ndarray:
-        return self.acc.cpu().numpy()
-
-
-class SegEvaluator(_Evaluator):
+class SegEvaluator(EvaluatorBase):
     """Runs the 'seg' loader's batches (rgb (B, H, W, 3) uint8 RGB, sem (B, H, W) labels) through an RGBSegmentationModel and adds
     the confusion matrix of its logits.
 
@@ -340,19 +257,16 @@ class SegEvaluator(_Evaluator):
             with ops.precision(self.code):
                 logits = self.model(part)
             self.in_force.add(erfnet_arithmetic(self.model.erfnet, part.shape))
-            self._seg("seg", logits, labels[j:j + self.images_per_call], 1)
+            self._add("eval_seg", eval_seg_numpy, "seg", logits, labels[j:j + self.images_per_call], 1)
         self.images += x.shape[0]
 
     def run(self, batches, max_images=None) -> int:
-        for rgb, sem in batches:
-            left = None if max_images is None else max_images - self.images
-            if left is not None and left <= 0:
-                break
+        for (rgb, sem), left in self._budget(batches, max_images, lambda: self.images):
             self.batch(rgb, sem, left)
         return self.images
 
 
-class BrakeEvaluator(_Evaluator):
+class BrakeEvaluator(EvaluatorBase):
     """Runs the 'bra' loader's batches (rgb, tel_rgb uint8 HWC, sem, tel_sem uint8 labels, bra flags) through an
     RGBBrakePredictionModel, frame by frame at batch 1 as the frame pipeline does: x1 = trunk(wide), x2 = trunk(tele),
     pred = classify(x1, x2), and the two segmentation heads at stride 4.  The heads' confusion matrices go to the sections "wide" and
@@ -382,139 +296,79 @@ class BrakeEvaluator(_Evaluator):
             if pred is None:
                 raise RuntimeError("BrakeEvaluator: the brake net has no fused classifier path here (eval mode, in HBM, batch 1)")
             self.in_force.add(trunk_arithmetic(m.conv_backbone, self.code))
-            self._seg("wide", logit1, sem[i:i + 1], SEG_SCALE)
-            self._seg("tele", logit2, tel_sem[i:i + 1], SEG_SCALE)
-            if self.device.type == "cpu":
-                eval_scores_numpy(self.layout.view(self.acc.numpy(), SCORES), pred, flags[i:i + 1], self.threshold, self.layout.nbins)
-            else:
-                ops.eval_scores(self.layout.view(self.acc, SCORES), pred.contiguous(), flags[i:i + 1], self.threshold, self.layout.nbins)
+            self._add("eval_seg", eval_seg_numpy, "wide", logit1, sem[i:i + 1], SEG_SCALE)
+            self._add("eval_seg", eval_seg_numpy, "tele", logit2, tel_sem[i:i + 1], SEG_SCALE)
+            self._add("eval_scores", eval_scores_numpy, SCORES, pred.contiguous(), flags[i:i + 1], self.threshold, self.layout.nbins)
         self.frames += wide.shape[0]
 
     def run(self, batches, max_frames=None) -> int:
-        for batch in batches:
-            left = None if max_frames is None else max_frames - self.frames
-            if left is not None and left <= 0:
-                break
+        for batch, left in self._budget(batches, max_frames, lambda: self.frames):
             self.batch(*batch, limit=left)
         return self.frames
 
 
 # ------------------------------------------------------------------------------------------------------------ command line
+def _build(what):
+    def build(args, cfg, device):
+        from .. import synth
+        from ..rgb import RGBBrakePredictionModel, RGBSegmentationModel
+        from .brake import BRA_LABELS
+        model = RGBSegmentationModel(cfg.seg_channels) if what == "seg" else RGBBrakePredictionModel(list(BRA_LABELS))
+        path = getattr(args, what)
+        model.load_state_dict(torch.load(path, map_location="cpu") if path else synth.seeded_state_dict(model, prefix=f"{what}."))
+        return model.to(device).eval()
+    return build
+
+
+def _classes(what, cfg):
+    from .brake import BRA_LABELS
+    return len(cfg.seg_channels if what == "seg" else BRA_LABELS) + 1
+
+
+def _batches(what):
+    def batches(args, cfg):
+        from . import synthetic
+        from ..data.datasets import LOADERS
+        if args.synthetic:
+            return synthetic_batches(getattr(synthetic, f"synthetic_{what}_batch"), args.frames, args.batch_size, args.seed, num_classes=_classes(what, cfg))
+        return LOADERS[what](args.config_path, seed=args.seed, overrides=dict(data_dir=args.data_dir) if args.data_dir else None)
+    return batches
+
+
+def _seg_line(ev, acc, args, cfg):
+    return dict(summary=summarise_seg(SEG.view(acc, "seg"), _classes("seg", cfg)))
+
+
+def _bra_line(ev, acc, args, cfg):
+    k = _classes("bra", cfg)
+    return dict(summary=dict(threshold=ev.threshold, brake=summarise_scores(BRA.view(acc, SCORES)), wide=summarise_seg(BRA.view(acc, "wide"), k),
+                             tele=summarise_seg(BRA.view(acc, "tele"), k)))
+
+
+def _tool(what, name, unit, **own):
+    """What eval_seg and eval_bra_v2 have in common of eval_common.run_cli's description.  {unit}_per_s is the whole run's rate, set-up
+    included: a precision's first call builds and packs its engines, the first line also starts the loader's workers.  On a short run it
+    measures that set-up, and it is not comparable between the lines of --precision all; the forwards and the metrics launches alone
+    are timed by tools/eval_camera_probe.py."""
+    return dict(name=name, unit=unit, checkpoints={what: f"{what}_model_dir"}, frames=6, synthetic="synthetic images", dedupe=True,
+                epilog=f"{unit}_per_s in the output is the whole run's rate, engine build, weight packing and loader start-up included: it says how "
+                       "long an evaluation takes, not how fast an arithmetic is",
+                build=_build(what), batches=_batches(what), keys=("what", "precision", "asked", "data", f"{unit}_per_s", "summary", "counters"), **own)
+
+
+_PRECISION_HELP = ("arithmetic of the convolutions, of what ops.precision switches in this net (default: the frame's); all: the same {unit} "
+                   "once per choice.")
 _WHAT = dict(
-    seg=dict(key="seg_model_dir", unit="images", precisions=SEG_PRECISIONS, batch=24,
-             about="held-out metrics of a camera segmenter checkpoint (seg_*.th) on recorded routes"),
-    bra=dict(key="bra_model_dir", unit="frames", precisions=BRA_PRECISIONS, batch=8,
-             about="held-out metrics of a brake-net checkpoint (bra_*.th) on recorded routes"))
-
-
-def _checkpoint(what, args):
-    """The checkpoint file: the flag's, else the config's `seg_model_dir` / `bra_model_dir`; None for --synthetic without the flag
-    (seeded weights).  A named file that does not exist is an error, never a silent fall back to seeded weights."""
-    key, path = _WHAT[what]["key"], getattr(args, what)
-    if path:
-        if not os.path.isfile(path):
-            raise SystemExit(f"--{what} {path}: no such file (the checkpoint the config calls `{key}`)")
-        return path
-    if args.synthetic:
-        return None
-    import yaml
-    with open(args.config_path, "r") as f:
-        rel = (yaml.safe_load(f) or {}).get(key)
-    if not rel:
-        raise SystemExit(f"{args.config_path} has no `{key}` and --{what} was not given")
-    cands = [rel, os.path.join(os.path.dirname(os.path.abspath(args.config_path)), rel)]
-    hit = next((c for c in cands if os.path.isfile(c)), None)
-    if hit is None:
-        raise SystemExit(f"checkpoint `{key}: {rel}` of {args.config_path} not found (tried {cands}); pass --{what} PATH, or --synthetic "
-                         "for seeded random weights on synthetic images")
-    return hit
-
-
-def _synthetic_batches(what, frames, seed, batch_size, num_classes):
-    from .synthetic import synthetic_bra_batch, synthetic_seg_batch
-    done = 0
-    while done < frames:
-        b = min(batch_size, frames - done)
-        yield (synthetic_seg_batch if what == "seg" else synthetic_bra_batch)(b, seed=seed + 1009 * done, num_classes=num_classes)
-        done += b
+    seg=_tool("seg", "eval_seg", "images", precisions=SEG_PRECISIONS, batch_size=24,
+              about="held-out metrics of a camera segmenter checkpoint (seg_*.th) on recorded routes",
+              help=dict(precision=_PRECISION_HELP.format(unit="images") + " Exact fp32: the same command under LAV_CONV_PRECISION=f32",
+                        batch_size="loader batch; inference is per call of three images"),
+              make_evaluator=lambda model, name, args: SegEvaluator(model, precision=name), line=_seg_line),
+    bra=_tool("bra", "eval_bra_v2", "frames", precisions=BRA_PRECISIONS, batch_size=8,
+              about="held-out metrics of a brake-net checkpoint (bra_*.th) on recorded routes", help=dict(precision=_PRECISION_HELP.format(unit="frames")),
+              make_evaluator=lambda model, name, args: BrakeEvaluator(model, precision=name), line=_bra_line))
 
 
 def main(what, argv=None):
-    """eval_seg.py ("seg") / eval_bra_v2.py ("bra"): one JSON line per precision - the summary, the raw counters and the images or
-    frames per second of the evaluation.  Single process, no augmentation, the loader in order and to its last sample.  The rate is
-    the whole run's, set-up included: a precision's first call builds and packs its engines, the first line also starts the loader's
-    workers.  On a short run it measures that set-up, and it is not comparable between the lines of --precision all; the forwards
-    and the metrics launches alone are timed by tools/eval_camera_probe.py."""
-    from .. import synth
-    from ..rgb import RGBBrakePredictionModel, RGBSegmentationModel
-    from .brake import BRA_LABELS
-    from .run import load_config
-    w = _WHAT[what]
-    unit = w["unit"]
-    ap = argparse.ArgumentParser(description=w["about"], epilog=f"{unit}_per_s in the output is the whole run's rate, engine build, weight packing and "
-                                 "loader start-up included: it says how long an evaluation takes, not how fast an arithmetic is")
-    ap.add_argument("--config-path", default=None, help="the reference's config_v2.yaml; required unless --synthetic")
-    ap.add_argument("--data-dir", default=None, help="held-out routes; overrides the config's data_dir")
-    ap.add_argument(f"--{what}", default=None, help=f"{what}_*.th (default: the config's {w['key']})")
-    ap.add_argument("--precision", default=None, choices=w["precisions"] + ("all",),
-                    help="arithmetic of the convolutions, of what ops.precision switches in this net (default: the frame's); all: the same "
-                         f"{unit} once per choice." + (" Exact fp32: the same command under LAV_CONV_PRECISION=f32" if what == "seg" else ""))
-    ap.add_argument(f"--max-{unit}", type=int, default=None, dest="max_units")
-    ap.add_argument("--batch-size", type=int, default=w["batch"], help="loader batch; inference is per "
-                    + ("call of three images" if what == "seg" else "frame"))
-    ap.add_argument("--num-workers", type=int, default=4)
-    ap.add_argument("--seed", type=int, default=2021)
-    ap.add_argument("--synthetic", action="store_true", help="synthetic images and seeded random weights (smoke runs)")
-    ap.add_argument("--frames", type=int, default=6, help=f"--synthetic: how many {unit}")
-    ap.add_argument("--out", default=None, metavar="FILE", help="also write the JSON there")
-    args = ap.parse_args(argv)
-    tool = "eval_seg" if what == "seg" else "eval_bra_v2"
-    if not args.synthetic and not args.config_path:
-        raise SystemExit("recorded routes are read from --data-dir or the data_dir of --config-path (or pass --synthetic)")
-    path = _checkpoint(what, args)
-    if not torch.cuda.is_available():
-        raise SystemExit(f"{tool}: no GPU visible; the models have no CPU inference path")
-    device = torch.device("cuda", torch.cuda.current_device())
-    cfg = load_config(args.config_path, seed=args.seed)
-    torch.manual_seed(cfg.seed)
-    if what == "seg":
-        model, k = RGBSegmentationModel(cfg.seg_channels), len(cfg.seg_channels) + 1
-    else:
-        model, k = RGBBrakePredictionModel(list(BRA_LABELS)), len(BRA_LABELS) + 1
-    model.load_state_dict(torch.load(path, map_location="cpu") if path else synth.seeded_state_dict(model, prefix=f"{what}."))
-    model.to(device).eval()
-    if args.synthetic:
-        data = f"{args.frames} synthetic {unit}"
-        batches = lambda: _synthetic_batches(what, args.frames, args.seed, args.batch_size, k)
-    else:
-        from ..data.datasets import LOADERS
-        ds = LOADERS[what](args.config_path, seed=args.seed, overrides=dict(data_dir=args.data_dir) if args.data_dir else None)
-        if len(ds) == 0:
-            raise SystemExit(f"no recorded {unit} under {args.data_dir or 'the data_dir of ' + args.config_path}")
-        data = f"{len(ds)} recorded {unit}"
-        batches = lambda: torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=False, drop_last=False, num_workers=args.num_workers)
-    lines = []
-    for name in (w["precisions"] if args.precision == "all" else (args.precision,)):
-        ev = SegEvaluator(model, precision=name) if what == "seg" else BrakeEvaluator(model, precision=name)
-        t0 = time.perf_counter()
-        n = ev.run(batches(), args.max_units)
-        acc = ev.counters()                      # (the one copy; it also waits for the last launch)
-        dt = time.perf_counter() - t0
-        ran = ev.precision()
-        if any(line["precision"] == ran for line in lines):      # (e.g. a shape the fp16 runs do not take, LAV_CONV_PRECISION=f32)
-            print(f"{tool}: --precision {name} ran at {ran}, which is already printed; no second line", file=sys.stderr)
-            continue
-        line = {"what": tool, "precision": ran, "asked": name, "data": data, f"{unit}_per_s": round(n / max(dt, 1e-9), 2)}
-        if what == "seg":
-            line["summary"] = summarise_seg(SEG.view(acc, "seg"), k)
-        else:
-            line["summary"] = dict(threshold=ev.threshold, brake=summarise_scores(BRA.view(acc, SCORES)),
-                                   wide=summarise_seg(BRA.view(acc, "wide"), k), tele=summarise_seg(BRA.view(acc, "tele"), k))
-        line["counters"] = ev.layout.named(acc)
-        lines.append(line)
-        print(json.dumps(line), flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
-    return lines
+    """eval_seg.py ("seg") / eval_bra_v2.py ("bra"): one JSON line per arithmetic that was in force (eval_common.run_cli)."""
+    return run_cli(_WHAT[what], argv)

@@ -133,26 +133,16 @@ def resolve_checkpoints(what, args):
     paths = dict(lidar=args.lidar, bev=args.bev, uniplanner=args.uniplanner)
     if args.synthetic or not args.config_path or what != "lidar":
         return paths
-    import yaml
-    with open(args.config_path, "r") as f:
-        raw = yaml.safe_load(f) or {}
+    from .eval_common import config_checkpoint
     wanted = dict(bev="bev_model_dir")
     if not args.perceive_only:
         wanted["lidar"] = "lidar_model_dir"
         if not args.motion_only:
             wanted["uniplanner"] = "uniplanner_dir"
     for name, key in wanted.items():
-        if paths[name]:
-            continue
-        rel = raw.get(key)
-        if not rel:
-            raise SystemExit(f"{args.config_path} has no `{key}` and --{name} was not given: train_full_v2 loads it (lav/lav_final_v2.py:42-72)")
-        cands = [rel, os.path.join(os.path.dirname(os.path.abspath(args.config_path)), rel)]
-        hit = next((c for c in cands if os.path.isfile(c)), None)
-        if hit is None:
-            raise SystemExit(f"checkpoint `{key}: {rel}` of {args.config_path} not found (tried {cands}); pass --{name} PATH, or --synthetic "
-                             "to train seeded random weights on synthetic batches")
-        paths[name] = hit
+        if not paths[name]:
+            paths[name] = config_checkpoint(args.config_path, key, name, None, False, "to train seeded random weights on synthetic batches",
+                                            why=": train_full_v2 loads it (lav/lav_final_v2.py:42-72)")
     return paths
 
 
