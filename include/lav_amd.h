@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 39
+#define LAV_ABI_VERSION 40
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -681,6 +681,19 @@ int lav_conv3x3_run_f16(int channels, int h, int w, int nlayers, const float *x,
                         const float *const *shift, float *out, const float *amax_in, int amax_in_count, float *amax_out, void *workspace,
                         size_t workspace_bytes, void *stream);
 int lav_conv3x3_run_f16_status(const void *workspace, int *h_timeouts_launches2, void *stream);
+/*
+ * lav_conv3x3_tile_f16 (ABI 40): a run of nlayers (<= 3) of the same layers at 64 channels as ONE launch without any hand-off between
+ * workgroups - stage s1 of the BEV backbone behind its stride-2 layer.  A workgroup owns an 8 x 16 output tile for all layers: it stages
+ * the input tile with a halo of nlayers pixels once, keeps the intermediate maps in LDS and recomputes their halo.  Arithmetic, weights
+ * (w_f16), scale / shift and amax_in as lav_conv3x3_run_f16; inside the run a workgroup takes a layer's activation scale from the largest
+ * finite |value| of the region it just computed.  amax_out (optional): one float per workgroup (lav_conv3x3_tile_f16_amax_count) - the
+ * maxima of the result, as lav_conv2d_amax leaves them.  No workspace, no waits: nothing to time out.  lav_conv3x3_tile_f16_lds_bytes
+ * returns 0 where the geometry is not served (other channel counts, more layers): run the layers one launch each.  Any h, w >= 1.
+ */
+size_t lav_conv3x3_tile_f16_lds_bytes(int channels, int h, int w, int nlayers);
+int lav_conv3x3_tile_f16_amax_count(int channels, int h, int w, int nlayers);
+int lav_conv3x3_tile_f16(int channels, int h, int w, int nlayers, const float *x, const void *const *w_f16, const float *const *scale,
+                         const float *const *shift, float *out, const float *amax_in, int amax_in_count, float *amax_out, void *stream);
 int lav_conv1d_pair(int batch, int channels, int h, int w, int d_a, int d_b, const float *x, const float *wa_packed,
                     const float *bias_a, const float *wb_packed, const float *bias_b, const float *scale, const float *shift,
                     const float *residual, int relu_post, float *y, void *stream);

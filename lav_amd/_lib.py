@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LAV_AMD_LIB") or os.path.join(HERE, "liblav_amd.so")   # LAV_AMD_LIB: A/B a second build
 
-ABI_VERSION = 39
+ABI_VERSION = 40
 MAX_CAM = 4
 MAX_CAM_F64 = 8
 
@@ -116,6 +116,9 @@ SIGNATURES = {
     "lav_conv_f16_weights_offset": (C.c_long, [C.POINTER(Conv)]),
     "lav_conv3x3_run_f16": (_I, [_I, _I, _I, _I, _P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P, _I, _P, _P, _Z, _P]),
     "lav_conv3x3_run_f16_status": (_I, [_P, C.POINTER(_I), _P]),
+    "lav_conv3x3_tile_f16_lds_bytes": (_Z, [_I, _I, _I, _I]),
+    "lav_conv3x3_tile_f16_amax_count": (_I, [_I, _I, _I, _I]),
+    "lav_conv3x3_tile_f16": (_I, [_I, _I, _I, _I, _P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P, _I, _P, _P]),
     "lav_conv1d_pair": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
     "lav_gru_seq_forward": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "lav_gru_seq_backward_workspace_bytes": (_Z, [_I, _I]),

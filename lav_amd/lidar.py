@@ -14,7 +14,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import ops
-from .ops import Amax, ConvLayer, ConvRun, GroupedDeconv, PointwiseUpconv
+from .ops import Amax, ConvLayer, ConvRun, ConvTileRun, GroupedDeconv, PointwiseUpconv
 from .point_pillar import PointPillarNet
 
 _NORM = dict(eps=1e-3, momentum=0.01)
@@ -147,6 +147,12 @@ class ConvBackbone(_Engine):
         # sits here, so the eager and the graphed pipeline run the same kernels)
         want = ops.bev_run_stages() if prec == _lib.CONV_F16X3 else ()
         eng[key]["runs"] = [ConvRun(eng[key][s][1:]) if s in want and len(eng[key][s]) > 2 else None for s in ("s1", "s2", "s3")]
+        # a 64-channel stage of at most 3 such layers that is not a persistent run (s1): one launch on halo tiles (ops.ConvTileRun)
+        if prec == _lib.CONV_F16X3 and ops.bev_tile_enabled():
+            for i, s in enumerate(("s1", "s2", "s3")):
+                st = eng[key][s]
+                if eng[key]["runs"][i] is None and 2 < len(st) <= 4 and st[1].cin == 64:
+                    eng[key]["runs"][i] = ConvTileRun(st[1:])
         eng["tensor_ids"] = self._tensor_ids()   # recorded where the engine is built, not at its first use
         object.__setattr__(self, "_eng", eng)
         return eng[key]

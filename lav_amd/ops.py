@@ -1365,6 +1365,47 @@ class ConvRun:
         return out
 
 
+def bev_tile_enabled() -> bool:
+    """LAV_BEV_TILE: a 64-channel stage that LAV_BEV_RUN leaves on its per-layer path runs its same-shape 3x3 layers as one launch
+    on halo tiles (ConvTileRun); default: what the measurement kept (profiles/bev_tile_ab.txt)."""
+    return _os.environ.get("LAV_BEV_TILE", BEV_TILE_DEFAULT).strip().lower() not in ("0", "", "off", "none")
+
+
+BEV_TILE_DEFAULT = "1"
+
+
+class ConvTileRun(ConvRun):
+    """ConvRun's layers (at most 3, at 64 channels) as ONE launch without hand-off between workgroups (lav_conv3x3_tile_f16): every
+    workgroup owns an output tile for all layers, stages the input tile with its halo once and keeps the intermediate maps in LDS.
+    The same layer checks, the same calling convention; no workspace and nothing that can time out."""
+
+    def takes(self, B: int, h: int, w: int) -> bool:
+        return B == 1 and _lib.load().lav_conv3x3_tile_f16_lds_bytes(self.ch, h, w, self._n) > 0
+
+    def __call__(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, amax_in: Optional["Amax"] = None,
+                 amax_out: Optional["Amax"] = None) -> torch.Tensor:
+        lib = _lib.load()
+        x = _f32c(x, "x")
+        B, ch, h, w = x.shape
+        if ch != self.ch or not self.takes(B, h, w):
+            raise RuntimeError(f"ConvTileRun: input {tuple(x.shape)} is not served (lav_conv3x3_tile_f16_lds_bytes)")
+        if out is None:
+            out = torch.empty_like(x)
+        n = self._n
+        if amax_in is not None and amax_in.count > 0:
+            a_in, n_in = amax_in.buf, amax_in.count
+        else:   # nobody left the input's maxima: measure it (one launch more)
+            a_in = _workspace(("conv_run_amax", id(self)), 512 * 4, x.device).view(torch.float32)
+            n_in = 512
+            check(lib.lav_absmax_parts(_ptr(x), x.numel(), _ptr(a_in), _stream()), "lav_absmax_parts")
+        a_out = amax_out.take(lib.lav_conv3x3_tile_f16_amax_count(ch, h, w, n)) if amax_out is not None else None
+        pa = lambda ts: (C.c_void_p * n)(*[t if isinstance(t, int) else t.data_ptr() for t in ts])
+        check(lib.lav_conv3x3_tile_f16(ch, h, w, n, _ptr(x), pa([l.w.data_ptr() + 4 * self._woff for l in self.layers]),
+                                       pa([l.scale for l in self.layers]), pa([l.shift for l in self.layers]), _ptr(out), _ptr(a_in), n_in,
+                                       _ptr(a_out), _stream()), "lav_conv3x3_tile_f16")
+        return out
+
+
 def bev_run_status(device, stream=None):
     """(workgroups that gave up, launches) of the lav_conv3x3_run_f16 launches on `stream` (default: the current one), summed over
     the runs' workspaces.  Synchronises that stream."""
