@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 40
+#define LAV_ABI_VERSION 41
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -994,6 +994,33 @@ size_t lav_eval_plans_words(int iters);
 int lav_eval_plans(const float *ego_plan, const float *ego_cast, const float *ego_cmds, const float *ego_locs, const int *cmds,
                    const unsigned char *bras, int batch, int iters, int num_plan, const float *other_cast, const float *other_cmds,
                    const float *other_locs, int num_others, long long *acc, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Baseline JPEG scans of RGB frames in HBM (ABI 41; the agent's MJPEG recording).  Specification: lav_amd.agent.mjpeg.scan_numpy,
+ * byte for byte; the stream format (4:2:0, full-range BT.601 in fixed point, an integer matrix DCT, the Annex K tables, restart
+ * intervals) is stated in that module.  All integer arithmetic.
+ *
+ * frames          DEVICE [n][h][row_stride bytes]: rows of w RGB pixels, uint8, row_stride >= 3 w.  1 <= n <= 4096, 1 <= h, w <= 16384.
+ * quality_tables  DEVICE [800] int32, lav_amd.agent.mjpeg.device_tables(quality): [0, 128) the luma and chroma quantisers in natural
+ *                 order, [128, 192) the DCT matrix, [192, 256) the zigzag order, [256, 288) code | length << 16 of the luma and chroma DC
+ *                 categories, [288, 800) the same of the luma and chroma AC symbols.  Indices read from it are masked or clamped: a wrong
+ *                 table gives a wrong stream, never an access outside the workspace or LDS.
+ * restart_mcus    MCUs (16 x 16 pixels) per restart interval, 1 .. 10: one wave codes an interval, one lane a block.
+ * scans_out       DEVICE [n][scan_stride bytes], scan_stride >= lav_jpeg_scan_capacity(h, w, restart_mcus): per frame the
+ *                 entropy-coded data of every interval, stuffed, with RST(k mod 8) behind all but the last - what stands between SOS
+ *                 and EOI.  Bytes past the frame's length are left as they were.
+ * lengths_out     DEVICE [n] int32: the bytes of each frame's scan.
+ * workspace       DEVICE, 256-byte aligned, lav_jpeg_workspace_bytes(n, h, w, restart_mcus) bytes; needs no initialisation.
+ * lav_jpeg_scan_capacity: the most bytes a frame's scan can take (every block 1660 bits, every byte stuffed, the markers); equals
+ * lav_amd.agent.mjpeg.scan_capacity.  Both size functions return 0 for arguments lav_jpeg_encode would refuse.
+ * Three launches on `stream` for the whole batch (coefficients per MCU, entropy coding per interval, compaction per interval); no
+ * host synchronisation, no dependency between workgroups of one launch.
+ */
+long long lav_jpeg_scan_capacity(int h, int w, int restart_mcus);
+size_t lav_jpeg_workspace_bytes(int n, int h, int w, int restart_mcus);
+int lav_jpeg_encode(const unsigned char *frames, int n, int h, int w, int row_stride, const int *quality_tables, int restart_mcus,
+                    unsigned char *scans_out, long long scan_stride, int *lengths_out, void *workspace, size_t workspace_bytes,
+                    void *stream);
 
 #ifdef __cplusplus
 }

@@ -311,33 +311,63 @@ def debug_view_numpy(rgb, tel_rgb, lidar, pred_bra, pred_bev, pred_loc, cast_loc
 
 # ---------------------------------------------------------------------------------------------- recorder
 class ViewRecorder:
-    """The frames of a drive: a pinned host ring of `capacity` frames that device frames are copied into without blocking;
-    flush() waits for the last copy, writes view_{first frame:06d}.npy of shape (n, H / 2, W / 2, 3) under `directory` and clears
-    the ring.  With capacity 0 (the view is off) it holds nothing and creates nothing."""
+    """The frames of a drive.  With capacity 0 (the view is off) it holds nothing and creates nothing.
 
-    def __init__(self, directory: str = "debug_view", capacity: int = 0):
-        self.directory, self.capacity = directory, int(capacity)
+    format "npy": a pinned host ring of `capacity` frames that device frames are copied into without blocking; flush() waits for the
+    last copy, writes view_{first frame:06d}.npy of shape (n, H / 2, W / 2, 3) under `directory` and clears the ring.
+
+    format "mjpeg": append() encodes the device frame on the current stream (ops.jpeg_encode, csrc/jpeg.hip) into one of STAGES
+    worst-case slots in HBM and copies its length to the host; a later append() that finds that copy landed (the event is queried,
+    never waited for) copies exactly that many bytes into the slot's pinned twin, and one after that moves them into ordinary host
+    memory and frees the slot - so in steady state a frame is on the host two ticks after it was rendered, run_step waits for nothing
+    and only the compressed bytes cross the bus.  Only when every slot is still in flight (the device more than STAGES - 1 frames behind)
+    does append() wait, for the oldest: nothing is ever dropped or cut.  Pinned memory: STAGES x (scan capacity + 4) bytes, 7.2 MB at
+    the agent's 160 x 1146 frame, whatever `capacity` is.  flush() and frames_jpeg() synchronise; flush() writes
+    view_{first frame:06d}.avi (lav_amd.agent.mjpeg.AviWriter at `fps`), every frame jpeg_header + scan + EOI.  CPU tensors are
+    encoded by the specification jpeg_encode_numpy: the same bytes.  frames() is the "npy" ring's and not available here."""
+
+    STAGES = 4
+    FORMATS = ("npy", "mjpeg")
+
+    def __init__(self, directory: str = "debug_view", capacity: int = 0, format: str = "npy", quality: int = 90, fps: float = 20.0):
+        if format not in self.FORMATS:
+            raise ValueError(f"ViewRecorder: format {format!r} is not one of {self.FORMATS}")
+        self.directory, self.capacity, self.format, self.quality, self.fps = directory, int(capacity), format, quality, float(fps)
+        if format == "mjpeg":
+            from . import mjpeg
+            mjpeg._check(quality, mjpeg.DEFAULT_RESTART_MCUS)
+            if not self.fps > 0:
+                raise ValueError(f"ViewRecorder: {fps} frames per second")
         self.ring = self.event = None
         self.count = 0
         self.first_frame = 0
         self.written = []
+        self.jpegs = []                # mjpeg: the scans that have reached ordinary host memory, in order
+        self.shape = None              # mjpeg: (h, w) of the frames held
+        self.stage = None              # mjpeg: the device slots and their pinned twins
+        self.inflight = []             # mjpeg: [slot, state, event, length] in frame order; state 0: length on its way, 1: bytes on their way
 
     def __len__(self):
         return self.count
 
     def clear(self):
+        if self.inflight:
+            self._advance(wait=True)           # (frames still on their way must not turn up among the next ones)
         self.count = 0
+        self.jpegs = []
 
     def full(self) -> bool:
         return self.capacity > 0 and self.count >= self.capacity
 
     def append(self, frame, frame_no: int):
-        """Copy the device frame into the next slot (non-blocking, on the current stream)."""
+        """Copy (npy) or encode (mjpeg) the device frame into the next slot (non-blocking, on the current stream)."""
         import torch
         if self.capacity < 1:
             raise RuntimeError("ViewRecorder: recording is off (capacity 0)")
         if self.full():
             self.flush()
+        if self.format == "mjpeg":
+            return self._append_jpeg(frame, frame_no)
         if self.ring is None or tuple(self.ring.shape[1:]) != tuple(frame.shape):
             if self.count:
                 self.flush()
@@ -349,8 +379,82 @@ class ViewRecorder:
         self.event.record()
         self.count += 1
 
+    # ------------------------------------------------------------------------------------------ mjpeg
+    def _append_jpeg(self, frame, frame_no: int):
+        import torch
+
+        from . import mjpeg
+        if frame.dim() != 3 or frame.shape[2] != 3 or frame.dtype != torch.uint8:
+            raise ValueError(f"ViewRecorder: frame must be (h, w, 3) uint8, got {frame.dtype} {tuple(frame.shape)}")
+        hw = (int(frame.shape[0]), int(frame.shape[1]))
+        if self.shape != hw:
+            if self.count:
+                self.flush()
+            self.shape, self.stage = hw, None
+        if self.count == 0:
+            self.first_frame = int(frame_no)
+        self.count += 1
+        if not frame.is_cuda:
+            self._advance(wait=True)           # (device frames before this one keep their place)
+            self.jpegs.append(mjpeg.scan_numpy(frame.numpy(), self.quality))
+            return
+        from .. import ops
+        if self.stage is None or self.stage[0].device != frame.device:
+            self._advance(wait=True)
+            cap = mjpeg.scan_capacity(*hw)
+            self.stage = (torch.empty((self.STAGES, cap), dtype=torch.uint8, device=frame.device),
+                          torch.empty((self.STAGES,), dtype=torch.int32, device=frame.device),
+                          torch.empty((self.STAGES, cap), dtype=torch.uint8).pin_memory(), torch.empty((self.STAGES,), dtype=torch.int32).pin_memory())
+            self.free = list(range(self.STAGES))
+        self._advance(wait=False)
+        if not self.free:
+            self._advance(wait=True)           # every slot in flight: the device is STAGES frames behind
+        slot = self.free.pop(0)
+        dev_scans, dev_len, _, host_len = self.stage
+        ops.jpeg_encode(frame, quality=self.quality, out=dev_scans[slot:slot + 1], lengths=dev_len[slot:slot + 1])
+        host_len[slot:slot + 1].copy_(dev_len[slot:slot + 1], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.inflight.append([slot, 0, ev, 0])
+
+    def _advance(self, wait: bool):
+        """Move the frames in flight on as far as their copies have landed (the events are queried) - or, with wait, all the way."""
+        import torch
+        if not self.inflight:
+            return
+        dev_scans, _, host_scans, host_len = self.stage
+        for item in self.inflight:             # a length has landed: copy exactly that many bytes
+            slot, state, ev, _ = item
+            if state == 0 and (wait or ev.query()):
+                ev.synchronize()
+                n = int(host_len[slot])
+                if not 0 < n <= host_scans.shape[1]:
+                    raise RuntimeError(f"ViewRecorder: a scan of {n} bytes in a slot of {host_scans.shape[1]}")
+                host_scans[slot, :n].copy_(dev_scans[slot, :n], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                item[1:] = [1, ev, n]
+        while self.inflight and self.inflight[0][1] == 1 and (wait or self.inflight[0][2].query()):      # in frame order
+            slot, _, ev, n = self.inflight.pop(0)
+            ev.synchronize()
+            self.jpegs.append(host_scans[slot, :n].numpy().tobytes())
+            self.free.append(slot)
+
+    def frames_jpeg(self) -> list:
+        """The recorded frames as complete JPEG streams, once every copy has landed (mjpeg only)."""
+        from . import mjpeg
+        if self.format != "mjpeg":
+            raise RuntimeError("ViewRecorder: frames_jpeg() is the mjpeg format's; frames() holds the npy ring")
+        self._advance(wait=True)
+        if self.count == 0:
+            return []
+        head = mjpeg.jpeg_header(*self.shape, self.quality)
+        return [head + scan + mjpeg.EOI for scan in self.jpegs]
+
     def frames(self) -> np.ndarray:
         """The recorded frames (n, H / 2, W / 2, 3), once their copies have landed; a view of the ring, valid until the next append."""
+        if self.format != "npy":
+            raise RuntimeError("ViewRecorder: frames() is the npy format's; frames_jpeg() holds the mjpeg frames")
         if self.count == 0:
             return np.zeros((0, 0, 0, 3), np.uint8)
         self.event.synchronize()
@@ -359,10 +463,20 @@ class ViewRecorder:
     def flush(self):
         if self.count == 0:
             return None
-        frames = self.frames()
-        os.makedirs(self.directory, exist_ok=True)
-        path = os.path.join(self.directory, f"view_{self.first_frame:06d}.npy")
-        np.save(path, frames)
+        if self.format == "mjpeg":
+            from . import mjpeg
+            jpegs = self.frames_jpeg()
+            assert len(jpegs) == self.count
+            os.makedirs(self.directory, exist_ok=True)
+            path = os.path.join(self.directory, f"view_{self.first_frame:06d}.avi")
+            with mjpeg.AviWriter(path, *self.shape, fps=self.fps) as avi:
+                for j in jpegs:
+                    avi.add(j)
+        else:
+            frames = self.frames()
+            os.makedirs(self.directory, exist_ok=True)
+            path = os.path.join(self.directory, f"view_{self.first_frame:06d}.npy")
+            np.save(path, frames)
         self.written.append(path)
         self.clear()
         return path

@@ -8,7 +8,8 @@ route/command tracking, PID, the brake / collision / creep overrides) is restate
 The debug view of the reference (visualize, :459-518) is rendered on the device and recorded when `debug_view: true`
 (lav_amd/agent/debug_view.py, csrc/debug_view.hip; off by default: nothing is launched, allocated or written then).
 
-Differences, all deliberate: no wandb logging and no mp4 encoding (flush_data writes the recorded frames as .npy files); the
+Differences, all deliberate: no wandb logging and no mp4 encoding (flush_data writes the recorded frames as .npy files or, with
+`debug_view_format: mjpeg`, as MJPEG/AVI files encoded on the device: lav_amd/agent/mjpeg.py, csrc/jpeg.hip); the
 two camera networks are loaded from state_dicts (`seg_model_dir`, `bra_model_dir`) instead of TorchScript traces, because the HIP
 convolution engines are built from the modules' parameters; `synthetic_weights: true` in the config replaces missing
 checkpoint files by seeded random weights (tests, benchmarks - the released checkpoints are git-LFS objects).
@@ -43,8 +44,9 @@ DEFAULT_CONFIG = dict(
     speed_ratio=[0.8, 0.8, 0.8, 0.6, 0.8, 0.8], lidar_model_dir="weights/lidar_v2_7.th",
     uniplanner_dir="weights/uniplanner_v2_7.th", bra_model_dir="weights/bra_v2_9.th", seg_model_dir="weights/seg_1.th",
     synthetic_weights=False, hip_graphs=True, points_per_tick=32768, precapture=True, log_wandb=False,
-    # the debug view: render every debug_view_every-th tick, write debug_view_dir/view_{first frame}.npy every debug_view_flush frames
-    debug_view=False, debug_view_dir="debug_view", debug_view_every=1, debug_view_flush=600)
+    # the debug view: render every debug_view_every-th tick, write debug_view_dir/view_{first frame}.npy every debug_view_flush frames;
+    # debug_view_format "mjpeg": view_{first frame}.avi instead, JPEG-encoded on the device at debug_view_quality, played at 20 / debug_view_every fps
+    debug_view=False, debug_view_dir="debug_view", debug_view_every=1, debug_view_flush=600, debug_view_format="npy", debug_view_quality=90)
 
 
 def get_entry_point():
@@ -129,7 +131,8 @@ class LAVAgent(AutonomousAgent):
 
         self.ekf = EKF(1, 1.477531, 1.393600)      # cos0 = 1 rad (sic), lf, lr (lav_agent_fast.py:141)
         self.ekf_initialized = False
-        self.vizs = view.ViewRecorder(self.debug_view_dir, int(self.debug_view_flush) if self.debug_view else 0)
+        self.vizs = view.ViewRecorder(self.debug_view_dir, int(self.debug_view_flush) if self.debug_view else 0, format=self.debug_view_format,
+                                      quality=self.debug_view_quality, fps=20.0 / max(int(self.debug_view_every), 1))
         self._view_frame = None
         self.num_frames = 0
         self.num_frame_keep = (self.num_frame_stack + 1) * GAP
@@ -149,7 +152,7 @@ class LAVAgent(AutonomousAgent):
         raise FileNotFoundError(f"LAVAgent: checkpoint {path!r} not found (set synthetic_weights: true for seeded random weights)")
 
     def flush_data(self):
-        """Write the recorded frames (waits for the last frame's copy) and clear the ring; nothing to do with the view off."""
+        """Write the recorded frames (.npy or .avi; waits for the last frame's copy) and clear the ring; nothing to do with the view off."""
         return self.vizs.flush()
 
     def destroy(self):

@@ -356,6 +356,62 @@ def debug_view(rgb: torch.Tensor, tel_rgb: torch.Tensor, lidar: torch.Tensor, pr
     return out
 
 
+_jpeg_tables: dict = {}
+
+
+def jpeg_encode(frames: torch.Tensor, quality: int = 90, restart_mcus: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                lengths: Optional[torch.Tensor] = None):
+    """Baseline JPEG scans of RGB frames on the device (lav_jpeg_encode; three launches on the current stream for the whole batch, no
+    synchronisation): frames (n, h, w, 3) or (h, w, 3) uint8 in HBM, quality 1 .. 100, restart_mcus 1 .. 10 MCUs per restart interval
+    (default lav_amd.agent.mjpeg.DEFAULT_RESTART_MCUS).  Returns (scans (n, capacity) uint8, lengths (n,) int32) in HBM - `out` and
+    `lengths` when given; out may have more columns than capacity = lav_amd.agent.mjpeg.scan_capacity(h, w, restart_mcus).
+    scans[i, :lengths[i]] is what stands between jpeg_header(h, w, quality, restart_mcus) and EOI; the bytes behind it are not
+    written.  Byte-identical to lav_amd.agent.mjpeg.scan_numpy.  The workspace and the device tables are kept per (n, h, w, quality,
+    restart_mcus, stream).  Wrong device, dtype, shape, quality, interval or a short `out` raise ValueError before anything is launched."""
+    from .agent import mjpeg as J
+    if restart_mcus is None:
+        restart_mcus = J.DEFAULT_RESTART_MCUS
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        raise ValueError("jpeg_encode: frames must be a tensor in HBM (cuda/hip device); lav_amd.ops has no CPU path "
+                         "(lav_amd.agent.mjpeg.jpeg_encode_numpy is the CPU specification)")
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
+        raise ValueError(f"jpeg_encode: frames must be (n, h, w, 3) or (h, w, 3) uint8, got {frames.dtype} {tuple(frames.shape)}")
+    if isinstance(quality, bool) or isinstance(restart_mcus, bool):
+        raise ValueError("jpeg_encode: quality and restart_mcus are integers")
+    J._check(quality, restart_mcus)
+    batch = frames if frames.dim() == 4 else frames[None]
+    n, h, w = (int(v) for v in batch.shape[:3])
+    if n < 1 or n > 4096:
+        raise ValueError(f"jpeg_encode: {n} frames (1 .. 4096)")
+    capacity = J.scan_capacity(h, w, restart_mcus)           # (refuses sides outside 1 .. 16384)
+    if capacity > 0x7FFFFFFF:
+        raise ValueError(f"jpeg_encode: a scan of up to {capacity} bytes has no int32 length")
+    dev = frames.device
+    if out is None:
+        out = torch.empty((n, capacity), dtype=torch.uint8, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == n
+              and out.shape[1] >= capacity and out.stride(1) == 1 and out.stride(0) >= capacity):
+        raise ValueError(f"jpeg_encode: out must be uint8 ({n}, >= {capacity}) with contiguous rows in HBM, on the frames' device")
+    if lengths is None:
+        lengths = torch.empty((n,), dtype=torch.int32, device=dev)
+    elif not (isinstance(lengths, torch.Tensor) and lengths.is_cuda and lengths.device == dev and lengths.dtype == torch.int32 and tuple(lengths.shape) == (n,)
+              and lengths.is_contiguous()):
+        raise ValueError(f"jpeg_encode: lengths must be a contiguous int32 tensor of shape ({n},) in HBM, on the frames' device")
+    lib = _lib.load()
+    batch = batch.contiguous()
+    key = (dev, int(quality))
+    tables = _jpeg_tables.get(key)
+    if tables is None:
+        if len(_jpeg_tables) > 16:
+            _jpeg_tables.clear()
+        tables = _jpeg_tables[key] = torch.from_numpy(J.device_tables(int(quality))).to(dev)
+    nbytes = int(lib.lav_jpeg_workspace_bytes(n, h, w, int(restart_mcus)))
+    ws = _workspace(("jpeg_encode", n, h, w, int(quality), int(restart_mcus)), nbytes, dev)
+    check(lib.lav_jpeg_encode(_ptr(batch), n, h, w, 3 * w, _ptr(tables), int(restart_mcus), _ptr(out), int(out.stride(0)), _ptr(lengths), _ptr(ws), nbytes,
+                              _stream()), "lav_jpeg_encode")
+    return out, lengths
+
+
 _log_view_font: dict = {}
 
 
