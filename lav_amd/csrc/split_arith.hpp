@@ -1,7 +1,7 @@
 // The split-operand arithmetic ("bf16x6" / "f16x3"): fp32 dot products on the matrix cores.  Every convolution kernel of the hot
 // path (conv_split_kernel.hpp, conv_pair.hip, conv_run.hip, conv_wgrad.hip) and every host packer (conv_split.hpp, conv_pair.hip)
-// takes its pieces, scales and product order from here; tests/test_gpu_f16x3_contract.py, test_gpu_conv.py, test_gpu_conv_run.py
-// and tests/test_capi_host.py hold them to it.
+// takes its pieces, scales and product order from here; tests/test_gpu_f16x3_contract.py, test_gpu_conv.py, test_gpu_conv_run.py,
+// test_gpu_conv_exact.py (bit for bit against float64 on exactly representable data) and tests/test_capi_host.py hold them to it.
 //
 // bf16x6   v_mfma_f32_32x32x2_f32 runs at the fp32 VECTOR rate (157 TFLOP/s, 1/16 of the bf16 matrix rate).  Every fp32 value is the
 //          exact sum of three bf16 pieces, x = x0 + x1 + x2 (8 + 8 + 8 significant bits; x1 = bf16(x - x0), ...: x - bf16(x) and the

@@ -107,8 +107,10 @@ def test_split_k_epilogue_matches_unsplit():
     assert_close(y.numpy(), ref.numpy(), atol=2e-5, rtol=1e-5, what="split-K epilogue")
 
 
-@pytest.mark.parametrize("cin,k,cout,B,H,W", [(3, 7, 64, 1, 288, 768), (3, 7, 64, 2, 50, 70), (3, 3, 13, 3, 288, 256), (3, 3, 13, 2, 37, 45), (3, 7, 40, 1, 20, 24),
-                                              (3, 3, 16, 1, 16, 64)])
+SMALL_CIN_CASES = [(3, 7, 64, 1, 288, 768), (3, 7, 64, 2, 50, 70), (3, 3, 13, 3, 288, 256), (3, 3, 13, 2, 37, 45), (3, 7, 40, 1, 20, 24), (3, 3, 16, 1, 16, 64)]
+
+
+@pytest.mark.parametrize("cin,k,cout,B,H,W", SMALL_CIN_CASES)
 def test_small_cin_vector_kernel(cin, k, cout, B, H, W):
     """The camera stems (3 input channels, stride 2: brake net 7x7 -> 64, ERFNet 3x3 -> 13) on k_conv_smallcin (packed fp32 FMAs, round 5):
     an fp32 FMA chain per output - held to 2e-6 of sum |w||x| against float64 - ragged tiles, a folded-normalisation pad value, every
