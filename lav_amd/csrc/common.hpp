@@ -106,6 +106,51 @@ __device__ __forceinline__ float parts_absmax(const float *__restrict__ parts, i
 // launch errors are sticky until queried; call after every kernel launch
 #define LAV_LAUNCH_CHECK() LAV_HIP(hipGetLastError())
 
+// Launch of a kernel with dynamic LDS beyond the 64 KB default: the first launch of every kernel instantiation raises its
+// hipFuncAttributeMaxDynamicSharedMemorySize to `attr_bytes` (the attribute is per function; set once, it stays).
+template <auto Kernel, class... A>
+int launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, int attr_bytes, const A &...args) {
+    static bool attr = false;
+    if (!attr) {
+        LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, attr_bytes));
+        attr = true;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+    LAV_LAUNCH_CHECK();
+    return LAV_OK;
+}
+
+// For a kernel that also holds `static_bytes` of static LDS and wants the rest of the CU's 160 KB: asks for 160 KB minus the static
+// part, settles for 152 KB where the runtime refuses, and clamps the launch's dynamic LDS to the cap it was granted (*cap_out).
+template <auto Kernel, class... A>
+int launch_lds_capped(dim3 grid, dim3 block, size_t lds, hipStream_t st, size_t static_bytes, size_t *cap_out, const A &...args) {
+    static size_t cap = 0;
+    if (!cap) {
+        size_t c = (160 * 1024 - static_bytes) / 16 * 16;
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c) != hipSuccess) {
+            (void)hipGetLastError();
+            c = 152 * 1024;
+            LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c));
+        }
+        cap = c;
+    }
+    if (cap_out) *cap_out = cap;
+    hipLaunchKernelGGL(Kernel, grid, block, std::min(cap, lds), st, args...);
+    LAV_LAUNCH_CHECK();
+    return LAV_OK;
+}
+
+// CUs of the device that was current at the first call (256 where it cannot be asked): one workgroup per CU is what a persistent
+// launch may count on to be resident at once
+inline int cu_count() {
+    static const int cus = [] {
+        int dev = 0, v = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
+        return v > 0 ? v : 256;
+    }();
+    return cus;
+}
+
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // bump allocator over the caller's workspace

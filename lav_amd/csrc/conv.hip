@@ -920,61 +920,50 @@ extern "C" int lav_conv_tile_info(const lav_conv *c, int *info) {
 namespace {
 template <int MP, int MC>
 int launch(const ConvArgs &a, const Plan &p, int batch, size_t lds, hipStream_t st, float *amax_out = nullptr) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv<MP, MC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
     const int Q = p.QH * p.QW;
     dim3 grid(a.rowblock ? p.QH * a.xblocks : (Q + 128 * MP - 1) / (128 * MP), (a.cout + 32 * MC - 1) / (32 * MC), batch * p.nclasses * a.ksplit);
+    const size_t nwg = (size_t)grid.x * grid.y * grid.z;
+    static const bool want_trace = getenv("LAV_CONV_TRACE") != nullptr;   // debug: per-workgroup phase stamps of every 10th launch
+    static unsigned long long *d_trace = nullptr;
+    static int runs = 0;
+    const bool trace = want_trace && nwg <= 65536;
+    if (trace && !d_trace) LAV_HIP(hipMalloc(&d_trace, (size_t)65536 * 8 * sizeof(unsigned long long)));
     const int tok = timer_begin("conv2d", st);
-    static const bool want_trace = getenv("LAV_CONV_TRACE") != nullptr;
-    if (want_trace) {  // debug: per-workgroup phase stamps of every 10th launch
-        static unsigned long long *d_trace = nullptr;
-        static int runs = 0;
-        static bool attr2 = false;
-        const size_t nwg = (size_t)grid.x * grid.y * grid.z;
-        if (!d_trace) LAV_HIP(hipMalloc(&d_trace, (size_t)65536 * 8 * sizeof(unsigned long long)));
-        if (!attr2) {
-            LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv<MP, MC, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr2 = true;
-        }
-        if (nwg <= 65536) {
-            ConvArgs at = a;
-            at.trace = d_trace;
-            hipLaunchKernelGGL((k_conv<MP, MC, true>), grid, dim3(256), lds, st, at);
-            if (a.ksplit > 1) {
-                const long total = (long)batch * a.cout * p.OH * p.OW;
-                hipLaunchKernelGGL(k_conv_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a, batch, amax_out);
-            }
-            if (++runs % 10 == 0) {
-                std::vector<unsigned long long> h(nwg * 8);
-                if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(h.data(), d_trace, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-                    unsigned long long t0 = ~0ull, t1 = 0;
-                    for (size_t i = 0; i < nwg; ++i) { t0 = std::min(t0, h[i * 8]); t1 = std::max(t1, h[i * 8 + 4]); }
-                    double ph[4] = {0, 0, 0, 0}, last_start = 0;
-                    for (size_t i = 0; i < nwg; ++i) {
-                        for (int k = 0; k < 4; ++k) ph[k] += (double)(h[i * 8 + k + 1] - h[i * 8 + k]) / 100.0;
-                        last_start = std::max(last_start, (double)(h[i * 8] - t0) / 100.0);
-                    }
-                    fprintf(stderr, "[conv trace] %zu wgs (%ux%ux%u) lds %zu KB ksplit %d cps %d: span %.2f us, last start %.2f | mean us: setup+issue %.2f | first stage wait %.2f | main loop %.2f | epilogue %.2f\n",
-                            nwg, grid.x, grid.y, grid.z, lds / 1024, a.ksplit, a.cps, (double)(t1 - t0) / 100.0, last_start, ph[0] / nwg, ph[1] / nwg, ph[2] / nwg, ph[3] / nwg);
-                }
-            }
-            timer_end(tok, st);
-            LAV_LAUNCH_CHECK();
-            return LAV_OK;
-        }
+    int rc;
+    if (trace) {
+        ConvArgs at = a;
+        at.trace = d_trace;
+        rc = launch_lds<k_conv<MP, MC, true>>(grid, dim3(256), lds, st, 160 * 1024, at);
+    } else {
+        rc = launch_lds<k_conv<MP, MC>>(grid, dim3(256), lds, st, 160 * 1024, a);
     }
-    hipLaunchKernelGGL((k_conv<MP, MC>), grid, dim3(256), lds, st, a);
-    if (a.ksplit > 1) {
+    if (!rc && a.ksplit > 1) {
         const long total = (long)batch * a.cout * p.OH * p.OW;
         hipLaunchKernelGGL(k_conv_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a, batch, amax_out);
     }
+    if (!rc && trace && ++runs % 10 == 0) {
+        std::vector<unsigned long long> h(nwg * 8);
+        if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(h.data(), d_trace, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
+            unsigned long long t0 = ~0ull, t1 = 0;
+            for (size_t i = 0; i < nwg; ++i) { t0 = std::min(t0, h[i * 8]); t1 = std::max(t1, h[i * 8 + 4]); }
+            double ph[4] = {0, 0, 0, 0}, last_start = 0;
+            for (size_t i = 0; i < nwg; ++i) {
+                for (int k = 0; k < 4; ++k) ph[k] += (double)(h[i * 8 + k + 1] - h[i * 8 + k]) / 100.0;
+                last_start = std::max(last_start, (double)(h[i * 8] - t0) / 100.0);
+            }
+            fprintf(stderr, "[conv trace] %zu wgs (%ux%ux%u) lds %zu KB ksplit %d cps %d: span %.2f us, last start %.2f | mean us: setup+issue %.2f | first stage wait %.2f | main loop %.2f | epilogue %.2f\n",
+                    nwg, grid.x, grid.y, grid.z, lds / 1024, a.ksplit, a.cps, (double)(t1 - t0) / 100.0, last_start, ph[0] / nwg, ph[1] / nwg, ph[2] / nwg, ph[3] / nwg);
+        }
+    }
     timer_end(tok, st);
+    if (rc) return rc;
     LAV_LAUNCH_CHECK();
     return LAV_OK;
 }
+
+using DirectLaunch = int (*)(dim3, dim3, size_t, hipStream_t, int, const DirectArgs &);
+template <int D, int MC>
+constexpr DirectLaunch direct_launch = &launch_lds<k_conv_direct<D, MC>, DirectArgs>;
 }  // namespace
 
 extern "C" int lav_conv_out_hw(const lav_conv *c, int *oh, int *ow) {
@@ -1357,27 +1346,25 @@ extern "C" int lav_conv2d_amax(const lav_conv *c, const float *x, const float *w
         d.M = c->batch * p.QH * p.QW; d.cw = dp.cw; d.cks = dp.cw * dp.waves; d.ksplit = dp.ksplit;
         d.relu_pre = c->relu_pre; d.relu_post = c->relu_post; d.sigmoid = c->sigmoid; d.pad_value = c->pad_value;
         d.amax_out = io.out;
-        const int tok = timer_begin("conv2d", st);
         dim3 grid((d.M + 31) / 32, (c->cout + 32 * dp.mc - 1) / (32 * dp.mc), dp.ksplit * p.nclasses);
         const dim3 block(64 * dp.waves);
         const size_t lds_red = (size_t)dp.waves * dp.mc * 32 * 33 * 4;   // <= 66 KB
         int depth = dp.mc == 1 ? 9 : 6;   // ring registers: DEPTH * (4 * MC + 4)
         while (steps_gcd % depth) --depth;
-        switch (depth * 10 + dp.mc) {
-#define LAV_DIRECT_CASE(D, MC_) case D * 10 + MC_: { \
-            static bool attr = false; \
-            if (!attr) { LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_direct<D, MC_>), hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 32 * 33 * 4)); attr = true; } \
-            hipLaunchKernelGGL((k_conv_direct<D, MC_>), grid, block, lds_red, st, d); } break;
-            LAV_DIRECT_CASE(1, 1) LAV_DIRECT_CASE(2, 1) LAV_DIRECT_CASE(3, 1) LAV_DIRECT_CASE(4, 1) LAV_DIRECT_CASE(5, 1)
-            LAV_DIRECT_CASE(6, 1) LAV_DIRECT_CASE(7, 1) LAV_DIRECT_CASE(8, 1) LAV_DIRECT_CASE(9, 1)
-            LAV_DIRECT_CASE(1, 2) LAV_DIRECT_CASE(2, 2) LAV_DIRECT_CASE(3, 2) LAV_DIRECT_CASE(4, 2) LAV_DIRECT_CASE(5, 2) LAV_DIRECT_CASE(6, 2)
-#undef LAV_DIRECT_CASE
-        }
-        if (dp.ksplit > 1) {
+        // [MC - 1][DEPTH - 1]
+        static constexpr DirectLaunch table[2][9] = {
+            {direct_launch<1, 1>, direct_launch<2, 1>, direct_launch<3, 1>, direct_launch<4, 1>, direct_launch<5, 1>, direct_launch<6, 1>, direct_launch<7, 1>,
+             direct_launch<8, 1>, direct_launch<9, 1>},
+            {direct_launch<1, 2>, direct_launch<2, 2>, direct_launch<3, 2>, direct_launch<4, 2>, direct_launch<5, 2>, direct_launch<6, 2>}};
+        LAV_REQUIRE((dp.mc == 1 || dp.mc == 2) && table[dp.mc - 1][depth - 1], "lav_conv2d: direct kernel of ring depth %d, %d cout blocks not built", depth, dp.mc);
+        const int tok = timer_begin("conv2d", st);
+        rc = table[dp.mc - 1][depth - 1](grid, block, lds_red, st, 16 * 32 * 33 * 4, d);
+        if (!rc && dp.ksplit > 1) {
             const long total = (long)c->batch * c->cout * p.OH * p.OW;
             hipLaunchKernelGGL(k_conv_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a, c->batch, io.out);
         }
         timer_end(tok, st);
+        if (rc) return rc;
         LAV_LAUNCH_CHECK();
         return measure_y();
     }

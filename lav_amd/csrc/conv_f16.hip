@@ -60,13 +60,7 @@ __global__ __launch_bounds__(256) void k_absmax_parts(const float *__restrict__ 
 
 template <int MP, int MC, int WPX, int NT, int G, bool TP>
 int launch_one(const SplitArgs &s, dim3 grid, size_t lds, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_split_f16<MP, MC, WPX, NT, G, TP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr = true;
-    }
-    hipLaunchKernelGGL((k_conv_split_f16<MP, MC, WPX, NT, G, TP>), grid, dim3(512), lds, st, s);
-    return LAV_OK;
+    return launch_lds<k_conv_split_f16<MP, MC, WPX, NT, G, TP>>(grid, dim3(512), lds, st, 160 * 1024, s);
 }
 template <int MP, int MC, int WPX>
 int launch_shape(const SplitArgs &s, bool small, int G, dim3 grid, size_t lds, hipStream_t st) {

@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "persistent.hpp"
 #include "split_arith.hpp"
 
 namespace {
@@ -1223,6 +1224,57 @@ inline bool pair_use_split() {
     }();
     return v;
 }
+
+// One fragment section of the packed weights, from PyTorch's [cout][cin][3]: [tap][chunk][cout block][piece NP][lane = khalf*32 + cout%32]
+// [8 channels] of T, zero where cout is padding.  split(w, p): the NP pieces of one weight.
+template <int NP, class T, class Split>
+void pair_pack_section(int C, const float *h_weight, T *o, Split split) {
+    const int CP = (C + 31) / 32 * 32, nchunk = C / 16;
+    for (int t = 0; t < 3; ++t)
+        for (int ch = 0; ch < nchunk; ++ch)
+            for (int blk = 0; blk < CP / 32; ++blk)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int e = 0; e < 8; ++e) {
+                        const int co = blk * 32 + (lane & 31), ci = ch * 16 + 8 * (lane >> 5) + e;
+                        T piece[NP];
+                        split(co < C ? h_weight[((size_t)co * C + ci) * 3 + t] : 0.f, piece);
+                        const size_t frag = ((((size_t)t * nchunk + ch) * (CP / 32) + blk) * NP) * 512;
+                        for (int q = 0; q < NP; ++q) o[frag + q * 512 + lane * 8 + e] = piece[q];
+                    }
+}
+
+// The kernel families of this file as template arguments: their argument block and their instantiations by (K halves, weight ring depth)
+struct PairExact {
+    using Args = PairArgs;
+    template <int KS, int R> static constexpr auto kernel = &k_conv1d_pair<KS, R>;
+};
+struct PairSplit {
+    using Args = PairSplitArgs;
+    template <int KS, int R> static constexpr auto kernel = &k_conv1d_pair_split<KS, R>;
+};
+// ... and the persistent runs': the bytes of static LDS they hold, the trace's name and what its phases 1 - 3 are
+struct ChainBf16 {
+    using Args = PairChainArgs;
+    template <int KS, int R, bool TRACE> static constexpr auto kernel = &k_conv1d_pair_chain<KS, R, TRACE>;
+    static constexpr size_t STATIC_LDS = CHAIN_STATIC_LDS;
+    static constexpr const char *label[4] = {"pair chain", "counter wait", "neighbour rows", "halo+barrier"};
+};
+struct ChainF16 {
+    using Args = PairChainF16Args;
+    template <int KS, int R, bool TRACE> static constexpr auto kernel = &k_conv1d_pair_chain_f16<KS, R, TRACE>;
+    static constexpr size_t STATIC_LDS = 2064 + 64;   // s_abort, s_epi, s_wmax, s_bmax, s_m3
+    static constexpr const char *label[4] = {"pair chain f16", "hand-off wait", "neighbour + own rows", "barrier"};
+};
+
+// a single pair: one workgroup of 256 * KS threads per row
+template <class F>
+int pair_launch(int ks, int ring, int rows, size_t lds, hipStream_t st, const typename F::Args &a) {
+    using A = typename F::Args;
+    static constexpr int (*table[2][3])(dim3, dim3, size_t, hipStream_t, int, const A &) = {   // [KS - 1][R = 1, 2, 4]
+        {&launch_lds<F::template kernel<1, 1>, A>, &launch_lds<F::template kernel<1, 2>, A>, &launch_lds<F::template kernel<1, 4>, A>},
+        {&launch_lds<F::template kernel<2, 1>, A>, &launch_lds<F::template kernel<2, 2>, A>, &launch_lds<F::template kernel<2, 4>, A>}};
+    return table[ks - 1][ring >> 1](dim3(rows), dim3(256 * ks), lav::lds_claim(lds), st, 160 * 1024, a);
+}
 }  // namespace
 
 extern "C" size_t lav_conv1d_pair_packed_weight_floats(int channels) {
@@ -1244,47 +1296,29 @@ extern "C" int lav_conv1d_pair_pack_weights(int channels, const float *h_weight,
                         const int k = ch * 16 + 2 * cp + half;
                         h_packed[((((size_t)t * nchunk + ch) * 2 + half) * CP + co) * 8 + cp] = co < C ? h_weight[((size_t)co * C + k) * 3 + t] : 0.f;
                     }
-    // split packing: [tap][chunk][cout block][piece][lane = khalf*32 + cout%32][8 channels] bf16
-    unsigned short *o = reinterpret_cast<unsigned short *>(h_packed + pair_f32_floats(C));
-    for (int t = 0; t < 3; ++t)
-        for (int ch = 0; ch < nchunk; ++ch)
-            for (int blk = 0; blk < CP / 32; ++blk)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < 8; ++e) {
-                        const int co = blk * 32 + (lane & 31), ci = ch * 16 + 8 * (lane >> 5) + e;
-                        const float w = co < C ? h_weight[((size_t)co * C + ci) * 3 + t] : 0.f;
-                        float r1, r2, r3;
-                        const unsigned short p0 = bf16_round(w, r1), p1 = bf16_round(r1, r2), p2 = bf16_round(r2, r3);
-                        const size_t frag = ((((size_t)t * nchunk + ch) * (CP / 32) + blk) * 3) * 512;
-                        o[frag + lane * 8 + e] = p0; o[frag + 512 + lane * 8 + e] = p1; o[frag + 1024 + lane * 8 + e] = p2;
-                    }
-    // fp16 packing (lav_conv1d_pair_chain_f16): [tap][chunk][cout block][piece 2][lane][8 channels] fp16 of w / s, s = the power of two that
-    // puts the largest |w| into [16384, 32768); behind it {s, max over cout of sum |w[cout]|, 0, 0}
-    {
-        const size_t nw = (size_t)C * C * 3;
-        float m = 0.f, l1 = 0.f;
-        for (size_t i = 0; i < nw; ++i) { const float v = fabsf(h_weight[i]); if (v <= 3.4028235e38f && v > m) m = v; }
-        for (int co = 0; co < C; ++co) {
-            double acc = 0.0;
-            for (int k = 0; k < C * 3; ++k) { const float v = fabsf(h_weight[(size_t)co * C * 3 + k]); if (v <= 3.4028235e38f) acc += v; }
-            l1 = std::max(l1, (float)(acc * (1.0 + 1e-6)));
-        }
-        const float sw = f16_scale_of(m), inv = 1.f / sw;
-        _Float16 *h = reinterpret_cast<_Float16 *>(h_packed + pair_f32_floats(C) + pair_split_bytes(C) / 4);
-        for (int t = 0; t < 3; ++t)
-            for (int ch = 0; ch < nchunk; ++ch)
-                for (int blk = 0; blk < CP / 32; ++blk)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            const int co = blk * 32 + (lane & 31), ci = ch * 16 + 8 * (lane >> 5) + e;
-                            const float w = co < C ? h_weight[((size_t)co * C + ci) * 3 + t] * inv : 0.f;
-                            const _Float16 h0 = (_Float16)w, h1 = (_Float16)(w - (float)h0);
-                            const size_t frag = ((((size_t)t * nchunk + ch) * (CP / 32) + blk) * 2) * 512;
-                            h[frag + lane * 8 + e] = h0; h[frag + 512 + lane * 8 + e] = h1;
-                        }
-        float *tail = h_packed + pair_f32_floats(C) + pair_split_bytes(C) / 4 + pair_f16_bytes(C) / 4;
-        tail[0] = sw; tail[1] = l1; tail[2] = 0.f; tail[3] = 0.f;
+    // split packing: three bf16 pieces per weight
+    pair_pack_section<3>(C, h_weight, reinterpret_cast<unsigned short *>(h_packed + pair_f32_floats(C)), [](float w, unsigned short *p) {
+        float r1, r2, r3;
+        p[0] = bf16_round(w, r1); p[1] = bf16_round(r1, r2); p[2] = bf16_round(r2, r3);
+    });
+    // fp16 packing (lav_conv1d_pair_chain_f16): two fp16 pieces of w / s, s = the power of two that puts the largest |w| into
+    // [16384, 32768); behind it {s, max over cout of sum |w[cout]|, 0, 0}
+    const size_t nw = (size_t)C * C * 3;
+    float m = 0.f, l1 = 0.f;
+    for (size_t i = 0; i < nw; ++i) { const float v = fabsf(h_weight[i]); if (v <= 3.4028235e38f && v > m) m = v; }
+    for (int co = 0; co < C; ++co) {
+        double acc = 0.0;
+        for (int k = 0; k < C * 3; ++k) { const float v = fabsf(h_weight[(size_t)co * C * 3 + k]); if (v <= 3.4028235e38f) acc += v; }
+        l1 = std::max(l1, (float)(acc * (1.0 + 1e-6)));
     }
+    const float sw = f16_scale_of(m), inv = 1.f / sw;
+    float *sec16 = h_packed + pair_f32_floats(C) + pair_split_bytes(C) / 4;
+    pair_pack_section<2>(C, h_weight, reinterpret_cast<_Float16 *>(sec16), [inv](float w, _Float16 *p) {
+        w *= inv;
+        p[0] = (_Float16)w; p[1] = (_Float16)(w - (float)p[0]);
+    });
+    float *tail = sec16 + pair_f16_bytes(C) / 4;
+    tail[0] = sw; tail[1] = l1; tail[2] = 0.f; tail[3] = 0.f;
     return LAV_OK;
 }
 
@@ -1321,15 +1355,9 @@ extern "C" int lav_conv1d_pair(int batch, int channels, int h, int w, int d_a, i
         const int nch2 = channels / 16 / ks2;
         const int ring2 = nch2 % 4 == 0 ? 4 : nch2 % 2 == 0 ? 2 : 1;
         const int tok2 = timer_begin("conv1d_pair", sst);
-#define LAV_PAIRS_CASE(KS_, R_) if (ks2 == KS_ && ring2 == R_) { \
-        static bool attr = false; \
-        if (!attr) { LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv1d_pair_split<KS_, R_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr = true; } \
-        hipLaunchKernelGGL((k_conv1d_pair_split<KS_, R_>), dim3(batch * h), dim3(256 * KS_), lav::lds_claim(lds), sst, sa); }
-        LAV_PAIRS_CASE(1, 1) LAV_PAIRS_CASE(1, 2) LAV_PAIRS_CASE(1, 4) LAV_PAIRS_CASE(2, 1) LAV_PAIRS_CASE(2, 2) LAV_PAIRS_CASE(2, 4)
-#undef LAV_PAIRS_CASE
+        const int rc = pair_launch<PairSplit>(ks2, ring2, batch * h, lds, sst, sa);
         timer_end(tok2, sst);
-        LAV_LAUNCH_CHECK();
-        return LAV_OK;
+        return rc;
     }
     PairArgs a;
     a.x = x; a.wA = wa_packed; a.bA = bias_a; a.wB = wb_packed; a.bB = bias_b; a.scale = scale; a.shift = shift; a.res = residual;
@@ -1352,13 +1380,8 @@ extern "C" int lav_conv1d_pair(int batch, int channels, int h, int w, int d_a, i
     const int ks = (channels >= 64 && (channels / 16) % 2 == 0 && !no_split && (size_t)channels * 3 * w * sizeof(float) >= 16 * 1024) ? 2 : 1;
     const int nch = channels / 16 / ks;              // chunks per wave
     const int ring = nch % 4 == 0 ? 4 : nch % 2 == 0 ? 2 : 1;
-#define LAV_PAIR_CASE(KS_, R_) if (ks == KS_ && ring == R_) { \
-        static bool attr = false; \
-        if (!attr) { LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv1d_pair<KS_, R_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr = true; } \
-        hipLaunchKernelGGL((k_conv1d_pair<KS_, R_>), dim3(batch * h), dim3(256 * KS_), lav::lds_claim(lds), st, a); }
-    LAV_PAIR_CASE(1, 1) LAV_PAIR_CASE(1, 2) LAV_PAIR_CASE(1, 4) LAV_PAIR_CASE(2, 1) LAV_PAIR_CASE(2, 2) LAV_PAIR_CASE(2, 4)
-#undef LAV_PAIR_CASE
-    if (a.trace && ++runs % 10 == 0) {   // debug: per-workgroup phase times of every 10th launch
+    const int rc = pair_launch<PairExact>(ks, ring, batch * h, lds, st, a);
+    if (!rc && a.trace && ++runs % 10 == 0) {   // debug: per-workgroup phase times of every 10th launch
         const size_t nwg = (size_t)batch * h;
         std::vector<unsigned long long> hst(nwg * 8);
         if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(hst.data(), d_trace, hst.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
@@ -1376,8 +1399,7 @@ extern "C" int lav_conv1d_pair(int batch, int channels, int h, int w, int d_a, i
         }
     }
     timer_end(tok, st);
-    LAV_LAUNCH_CHECK();
-    return LAV_OK;
+    return rc;
 }
 
 namespace {
@@ -1391,6 +1413,41 @@ __global__ __launch_bounds__(256) void k_zero_ints(int *p, int n, int *q, int nq
 // lav_conv1d_pair_chain_region: where this thread's next runs keep their counters, and what they clean first
 thread_local int g_chain_row_offset = 0, g_chain_clean_rows = -1;
 inline size_t chain_cap_rows(size_t workspace_bytes) { return workspace_bytes > 256 ? (workspace_bytes - 256) / 132 / 64 * 64 : 0; }
+
+constexpr int CHAIN_TRACE_ROWS = 512;   // workgroups the trace buffer holds
+
+// One run of family F: a workgroup of 256 * KS threads per row.  `want` bytes of dynamic LDS: what the run needs, or its claim of the
+// CU (lds_claim); the kernel also holds F::STATIC_LDS bytes of static LDS, so the dynamic part may reach 160 KB minus that.
+// trace (LAV_PAIR_CHAIN_TRACE, built for KS = R = 2 only): the exact size `need`, and a.trace is set.
+template <class F>
+int chain_launch(int ks, int ring, bool trace, int rows, size_t need, size_t want, hipStream_t st, const typename F::Args &a) {
+    using A = typename F::Args;
+    const dim3 grid(rows), block(256 * ks);
+    if (trace) return launch_lds<F::template kernel<2, 2, true>>(grid, block, need, st, 152 * 1024, a);
+    static constexpr int (*table[2][2])(dim3, dim3, size_t, hipStream_t, size_t, size_t *, const A &) = {   // [KS - 1][R - 1]
+        {&launch_lds_capped<F::template kernel<1, 1, false>, A>, &launch_lds_capped<F::template kernel<1, 2, false>, A>},
+        {&launch_lds_capped<F::template kernel<2, 1, false>, A>, &launch_lds_capped<F::template kernel<2, 2, false>, A>}};
+    size_t cap = 0;
+    const int rc = table[ks - 1][ring - 1](grid, block, want, st, F::STATIC_LDS, &cap, a);
+    static bool said[2][2] = {};
+    if (!said[ks - 1][ring - 1] && getenv("LAV_PAIR_CHAIN_DEBUG"))
+        fprintf(stderr, "[%s] dynamic LDS cap %zu bytes, this launch %zu\n", F::label[0], cap, std::min(cap, want));
+    said[ks - 1][ring - 1] = true;
+    return rc;
+}
+
+// debug: mean cycles per pair and workgroup of every 10th traced run, by phase (the kernels' TRACE comments); label: the family's
+void chain_trace_report(const long long *d_trace, const char *const (&label)[4], int channels, int w, int rows, int npairs, hipStream_t st) {
+    static int runs = 0;
+    if (++runs % 10) return;
+    std::vector<long long> hst((size_t)rows * 8);
+    if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(hst.data(), d_trace, hst.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
+    double m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < rows; ++i) for (int k = 0; k < 8; ++k) m[k] += (double)hst[(size_t)i * 8 + k];
+    const double f = 1.0 / rows / npairs;
+    fprintf(stderr, "[%s trace] C %d W %d, %d rows, %d pairs: cycles per pair and workgroup: all %.0f | %s %.0f | %s %.0f | %s %.0f | phase A %.0f | combine+mid %.0f | phase B %.0f | epilogue+publish %.0f\n",
+            label[0], channels, w, rows, npairs, m[0] * f, label[1], m[1] * f, label[2], m[2] * f, label[3], m[3] * f, m[4] * f, m[5] * f, m[6] * f, m[7] * f);
+}
 }  // namespace
 
 extern "C" size_t lav_conv1d_pair_chain_workspace_bytes(int batch, int h) {
@@ -1422,27 +1479,28 @@ static int pair_chain_launch(bool f16, int batch, int channels, int h, int w, in
     LAV_REQUIRE(d_a && d_b && residual && relu_post && x && wa_packed && bias_a && wb_packed && bias_b && scale && shift && out, "lav_conv1d_pair_chain: null argument");
     LAV_REQUIRE(workspace && workspace_bytes >= lav_conv1d_pair_chain_workspace_bytes(batch, h), "lav_conv1d_pair_chain: workspace too small");
     // every row's workgroup must be resident at once (they wait for each other): one workgroup per CU at these LDS sizes
-    static const int cus = [] {
-        int dev = 0, v = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-        return v > 0 ? v : 256;
-    }();
+    const int cus = cu_count(), rows = batch * h;
     {   // a CU takes two of the run's workgroups when they are 256 threads with at most 76 KB of LDS each (16-channel stages)
         int dbm = 1;
         for (int i = 0; i < npairs; ++i) dbm = std::max(dbm, d_b[i]);
         const bool two = lav_conv1d_pair_chain_lds_bytes(channels, w, dbm) <= 76 * 1024 && !(channels >= 64 && (channels / 16) % 2 == 0);
-        LAV_REQUIRE(batch * h <= cus * (two ? 2 : 1), "lav_conv1d_pair_chain: %d rows exceed the %d workgroups the chip holds at once (run the pairs one launch each)",
-                    batch * h, cus * (two ? 2 : 1));
+        LAV_REQUIRE(rows <= cus * (two ? 2 : 1), "lav_conv1d_pair_chain: %d rows exceed the %d workgroups the chip holds at once (run the pairs one launch each)",
+                    rows, cus * (two ? 2 : 1));
     }
-    PairChainArgs a;
+    // the fp16 run's argument block holds the bf16 run's; the weights are the section of the precision that runs
+    PairChainF16Args fa;
+    PairChainArgs &a = fa.c;
+    const size_t sec = pair_f32_floats(channels) + (f16 ? pair_split_bytes(channels) / 4 : 0);   // floats in front of that section
     int dbmax = 1;
     for (int i = 0; i < CHAIN_MAX; ++i) {
-        const int j = i < npairs ? i : npairs - 1;
+        const int j = layer_of(i, npairs);
         LAV_REQUIRE(d_a[j] >= 1 && d_b[j] >= 1 && d_b[j] <= 16 && d_a[j] < 256, "lav_conv1d_pair_chain: bad dilation");
         LAV_REQUIRE(wa_packed[j] && bias_a[j] && wb_packed[j] && bias_b[j] && scale[j] && shift[j] && out[j], "lav_conv1d_pair_chain: null argument of pair %d", j);
         a.out[i] = out[j];
-        a.wA[i] = reinterpret_cast<const unsigned char *>(wa_packed[j] + pair_f32_floats(channels));
-        a.wB[i] = reinterpret_cast<const unsigned char *>(wb_packed[j] + pair_f32_floats(channels));
+        a.wA[i] = reinterpret_cast<const unsigned char *>(wa_packed[j] + sec);
+        a.wB[i] = reinterpret_cast<const unsigned char *>(wb_packed[j] + sec);
+        fa.tA[i] = f16 ? wa_packed[j] + sec + pair_f16_bytes(channels) / 4 : nullptr;
+        fa.tB[i] = f16 ? wb_packed[j] + sec + pair_f16_bytes(channels) / 4 : nullptr;
         a.bA[i] = bias_a[j]; a.bB[i] = bias_b[j]; a.scale[i] = scale[j]; a.shift[i] = shift[j];
         a.dA[i] = (unsigned char)d_a[j]; a.dB[i] = (unsigned char)d_b[j]; a.res[i] = residual[j] ? 1 : 0; a.relu[i] = relu_post[j] ? 1 : 0;
         dbmax = std::max(dbmax, d_b[j]);
@@ -1450,127 +1508,45 @@ static int pair_chain_launch(bool f16, int batch, int channels, int h, int w, in
     LAV_REQUIRE(!residual[0], "lav_conv1d_pair_chain: the run starts at a block boundary (its first pair has no residual)");
     const size_t cap_rows = chain_cap_rows(workspace_bytes);
     const int row_off = g_chain_row_offset, clean_rows = g_chain_clean_rows;
-    LAV_REQUIRE((size_t)row_off + (size_t)batch * h <= cap_rows && (clean_rows < 0 || (size_t)clean_rows <= cap_rows),
-                "lav_conv1d_pair_chain: rows %d + %d exceed the workspace's %zu counters (lav_conv1d_pair_chain_region)", row_off, batch * h, cap_rows);
+    LAV_REQUIRE((size_t)row_off + (size_t)rows <= cap_rows && (clean_rows < 0 || (size_t)clean_rows <= cap_rows),
+                "lav_conv1d_pair_chain: rows %d + %d exceed the workspace's %zu counters (lav_conv1d_pair_chain_region)", row_off, rows, cap_rows);
     a.x0 = x; a.sticky = static_cast<int *>(workspace); a.flags = a.sticky + 64 + row_off;
     a.B = batch; a.C = channels; a.H = h; a.W = w; a.CP = (channels + 31) / 32 * 32; a.npairs = npairs;
-    const char *lim = getenv("LAV_CHAIN_SPIN_LIMIT");   // test knob: 0 makes every wait that is not satisfied at once a time-out
-    a.spin_limit = lim ? std::max(0ll, atoll(lim)) : (1ll << 21);
+    a.spin_limit = chain_spin_limit();
+    a.trace = nullptr;
+    // (the fp16 runs hand off through their count-and-maximum words - 16 pairs x capacity rows x 8 bytes behind the counters, cleaned as a whole)
+    int *words = reinterpret_cast<int *>(static_cast<char *>(workspace) + 256 + cap_rows * sizeof(int));
+    fa.rowmax = reinterpret_cast<unsigned long long *>(words) + row_off;
+    fa.rm_stride = (int)cap_rows;
+    fa.dbmax = dbmax;
     const size_t lds = lav_conv1d_pair_chain_lds_bytes(channels, w, dbmax);
     LAV_REQUIRE(lds <= 152 * 1024, "lav_conv1d_pair_chain: %zu bytes of LDS needed", lds);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int nflag = batch * h;
     // counters at zero: this run's own (default), the first `clean_rows` of the array (the first of several runs that share one
     // cleaning), or nothing (clean_rows = 0: a launch earlier on the stream cleaned this run's region)
-    {
-        // (the fp16 runs hand off through their count-and-maximum words - 16 pairs x capacity rows x 8 bytes behind the counters, cleaned as a whole)
-        int *words = reinterpret_cast<int *>(static_cast<char *>(workspace) + 256 + cap_rows * sizeof(int));
-        const int nwords = f16 ? (int)(CHAIN_MAX * cap_rows * 2) : 0;
-        if (clean_rows < 0) hipLaunchKernelGGL(k_zero_ints, dim3((nflag + nwords + 255) / 256), dim3(256), 0, st, a.flags, nflag, words, nwords, a.sticky + 2);
-        else if (clean_rows > 0) hipLaunchKernelGGL(k_zero_ints, dim3((clean_rows + nwords + 255) / 256), dim3(256), 0, st, a.sticky + 64, clean_rows, words, nwords, a.sticky + 2);
-    }
+    const int nwords = f16 ? (int)(CHAIN_MAX * cap_rows * 2) : 0;
+    if (clean_rows < 0) hipLaunchKernelGGL(k_zero_ints, dim3((rows + nwords + 255) / 256), dim3(256), 0, st, a.flags, rows, words, nwords, a.sticky + 2);
+    else if (clean_rows > 0) hipLaunchKernelGGL(k_zero_ints, dim3((clean_rows + nwords + 255) / 256), dim3(256), 0, st, a.sticky + 64, clean_rows, words, nwords, a.sticky + 2);
     const int ks2 = channels >= 64 && (channels / 16) % 2 == 0 ? 2 : 1;
     const int nch2 = channels / 16 / ks2;
     // weight ring of at most two chunks: the four-chunk ring of the single-pair kernel does not fit the registers next to the
     // block's input row and the next pair's prefetch (364 bytes of scratch per lane)
     const int ring2 = nch2 % 2 == 0 ? 2 : 1;
-    const int tok = timer_begin("conv1d_pair", st);
-    if (f16) {
-        PairChainF16Args fa;
-        fa.c = a;
-        fa.c.trace = nullptr;
-        const size_t sec = pair_f32_floats(channels) + pair_split_bytes(channels) / 4;   // floats in front of the fp16 section
-        for (int i = 0; i < CHAIN_MAX; ++i) {
-            const int j = i < npairs ? i : npairs - 1;
-            fa.c.wA[i] = reinterpret_cast<const unsigned char *>(wa_packed[j] + sec);
-            fa.c.wB[i] = reinterpret_cast<const unsigned char *>(wb_packed[j] + sec);
-            fa.tA[i] = wa_packed[j] + sec + pair_f16_bytes(channels) / 4;
-            fa.tB[i] = wb_packed[j] + sec + pair_f16_bytes(channels) / 4;
-        }
-        fa.rowmax = reinterpret_cast<unsigned long long *>(static_cast<char *>(workspace) + 256 + cap_rows * sizeof(int)) + row_off;
-        fa.rm_stride = (int)cap_rows;
-        fa.dbmax = dbmax;
-        const size_t lds16 = 16384 + (size_t)channels * w * 12 + (size_t)channels * (w + 2 * dbmax) * 4;
-        constexpr size_t F16_STATIC_LDS = 2064 + 64;   // s_abort, s_epi, s_wmax, s_bmax, s_m3
-#define LAV_CHAIN16_CASE(KS_, R_) if (ks2 == KS_ && ring2 == R_) { \
-        static size_t cap = 0; \
-        if (!cap) { \
-            cap = (160 * 1024 - F16_STATIC_LDS) / 16 * 16; \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv1d_pair_chain_f16<KS_, R_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap) != hipSuccess) { \
-                (void)hipGetLastError(); \
-                cap = 152 * 1024; \
-                LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv1d_pair_chain_f16<KS_, R_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap)); \
-            } \
-        } \
-        /* (the residency rule above was checked with the bf16 run's LDS size: this run claims what THAT one would, so the same rows per CU) */ \
-        hipLaunchKernelGGL((k_conv1d_pair_chain_f16<KS_, R_>), dim3(batch * h), dim3(256 * KS_), \
-                           std::min(cap, std::max(lds16, lav::lds_claim(lds, F16_STATIC_LDS, batch * h > cus))), st, fa); }
-        static const bool want_trace16 = getenv("LAV_PAIR_CHAIN_TRACE") != nullptr;
-        if (want_trace16 && ks2 == 2 && ring2 == 2 && batch * h <= 512) {
-            static long long *d_trace16 = nullptr;
-            if (!d_trace16) LAV_HIP(hipMalloc(&d_trace16, (size_t)512 * 8 * sizeof(long long)));
-            fa.c.trace = d_trace16;
-            static bool attr_t = false;
-            if (!attr_t) { LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv1d_pair_chain_f16<2, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024)); attr_t = true; }
-            hipLaunchKernelGGL((k_conv1d_pair_chain_f16<2, 2, true>), dim3(batch * h), dim3(512), std::max(lds16, lav::lds_claim(lds, F16_STATIC_LDS, batch * h > cus)), st, fa);
-            static int runs16 = 0;
-            if (++runs16 % 10 == 0) {
-                std::vector<long long> hst((size_t)batch * h * 8);
-                if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(hst.data(), d_trace16, hst.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-                    double m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                    for (int i = 0; i < batch * h; ++i) for (int k = 0; k < 8; ++k) m[k] += (double)hst[(size_t)i * 8 + k];
-                    const double f = 1.0 / (batch * h) / npairs;
-                    fprintf(stderr, "[pair chain f16 trace] C %d W %d, %d rows, %d pairs: cycles per pair and workgroup: all %.0f | hand-off wait %.0f | neighbour + own rows %.0f | barrier %.0f | phase A %.0f | combine+mid %.0f | phase B %.0f | epilogue+publish %.0f\n",
-                            channels, w, batch * h, npairs, m[0] * f, m[1] * f, m[2] * f, m[3] * f, m[4] * f, m[5] * f, m[6] * f, m[7] * f);
-                }
-            }
-        } else {
-        LAV_CHAIN16_CASE(1, 1) LAV_CHAIN16_CASE(1, 2) LAV_CHAIN16_CASE(2, 1) LAV_CHAIN16_CASE(2, 2)
-        }
-#undef LAV_CHAIN16_CASE
-        timer_end(tok, st);
-        LAV_LAUNCH_CHECK();
-        return LAV_OK;
-    }
-#define LAV_CHAIN_CASE(KS_, R_) if (ks2 == KS_ && ring2 == R_) { \
-        static size_t cap = 0;   /* (the kernel also holds CHAIN_STATIC_LDS bytes of static LDS: the dynamic part may claim 160 KB minus that) */ \
-        if (!cap) { \
-            cap = (160 * 1024 - CHAIN_STATIC_LDS) / 16 * 16; \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv1d_pair_chain<KS_, R_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap) != hipSuccess) { \
-                (void)hipGetLastError(); \
-                cap = 152 * 1024; \
-                LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv1d_pair_chain<KS_, R_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap)); \
-            } \
-            if (getenv("LAV_PAIR_CHAIN_DEBUG")) fprintf(stderr, "[pair chain] dynamic LDS cap %zu bytes, this launch %zu\n", cap, std::min(cap, lav::lds_claim(lds, CHAIN_STATIC_LDS, batch * h > cus))); \
-        } \
-        hipLaunchKernelGGL((k_conv1d_pair_chain<KS_, R_>), dim3(batch * h), dim3(256 * KS_), std::min(cap, lav::lds_claim(lds, CHAIN_STATIC_LDS, batch * h > cus)), st, a); }
     static const bool want_trace = getenv("LAV_PAIR_CHAIN_TRACE") != nullptr;
     static long long *d_trace = nullptr;
-    a.trace = nullptr;
-    if (want_trace && ks2 == 2 && ring2 == 2) {
-        if (!d_trace) LAV_HIP(hipMalloc(&d_trace, (size_t)512 * 8 * sizeof(long long)));
+    const bool trace = want_trace && ks2 == 2 && ring2 == 2 && rows <= CHAIN_TRACE_ROWS;
+    if (trace) {
+        if (!d_trace) LAV_HIP(hipMalloc(&d_trace, (size_t)CHAIN_TRACE_ROWS * 8 * sizeof(long long)));
         a.trace = d_trace;
-        static bool attr_t = false;
-        if (!attr_t) { LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv1d_pair_chain<2, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024)); attr_t = true; }
-        hipLaunchKernelGGL((k_conv1d_pair_chain<2, 2, true>), dim3(batch * h), dim3(512), lds, st, a);   // (trace build: exact size)
-        static int runs = 0;
-        if (++runs % 10 == 0 && batch * h <= 512) {
-            std::vector<long long> hst((size_t)batch * h * 8);
-            if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(hst.data(), d_trace, hst.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-                double m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (int i = 0; i < batch * h; ++i) for (int k = 0; k < 8; ++k) m[k] += (double)hst[(size_t)i * 8 + k];
-                const double f = 1.0 / (batch * h) / npairs;
-                fprintf(stderr, "[pair chain trace] C %d W %d, %d rows, %d pairs: cycles per pair and workgroup: all %.0f | counter wait %.0f | neighbour rows %.0f | halo+barrier %.0f | phase A %.0f | combine+mid %.0f | phase B %.0f | epilogue+publish %.0f\n",
-                        channels, w, batch * h, npairs, m[0] * f, m[1] * f, m[2] * f, m[3] * f, m[4] * f, m[5] * f, m[6] * f, m[7] * f);
-            }
-        }
-    } else {
-    LAV_CHAIN_CASE(1, 1) LAV_CHAIN_CASE(1, 2) LAV_CHAIN_CASE(2, 1) LAV_CHAIN_CASE(2, 2)
     }
-#undef LAV_CHAIN_CASE
+    const int tok = timer_begin("conv1d_pair", st);
+    // (the residency rule above was checked with the bf16 run's LDS size: the fp16 run, which needs less, claims what THAT one would, so
+    // the same rows per CU)
+    const size_t want = lav::lds_claim(lds, f16 ? ChainF16::STATIC_LDS : ChainBf16::STATIC_LDS, rows > cus);
+    const int rc = f16 ? chain_launch<ChainF16>(ks2, ring2, trace, rows, lds, want, st, fa) : chain_launch<ChainBf16>(ks2, ring2, trace, rows, lds, want, st, a);
+    if (!rc && trace) chain_trace_report(d_trace, f16 ? ChainF16::label : ChainBf16::label, channels, w, rows, npairs, st);
     timer_end(tok, st);
-    LAV_LAUNCH_CHECK();
-    return LAV_OK;
+    return rc;
 }
 
 extern "C" int lav_conv1d_pair_chain(int batch, int channels, int h, int w, int npairs, const int *d_a, const int *d_b, const int *residual,
@@ -1591,8 +1567,5 @@ extern "C" int lav_conv1d_pair_chain_f16(int batch, int channels, int h, int w, 
 
 extern "C" int lav_conv1d_pair_chain_status(const void *workspace, int *h_timeouts_launches2, void *stream) {
     LAV_REQUIRE(workspace && h_timeouts_launches2, "lav_conv1d_pair_chain_status: bad argument");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    LAV_HIP(hipMemcpyAsync(h_timeouts_launches2, workspace, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    LAV_HIP(hipStreamSynchronize(st));
-    return LAV_OK;
+    return read_status(workspace, 0, h_timeouts_launches2, static_cast<hipStream_t>(stream));
 }

@@ -26,6 +26,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "persistent.hpp"
 #include "split_arith.hpp"
 
 namespace {
@@ -314,6 +315,13 @@ bool run_config(int channels, int h, int w, RunConfig &c) {
     c.map_bytes = ((size_t)channels * h * w * sizeof(float) + 255) / 256 * 256;
     return true;
 }
+
+// the instantiations that are built: the cuts run_config makes of the geometries the BEV backbone has
+struct RunBuild { int NPB, NCBW, KS, NTK; int (*launch)(dim3, dim3, size_t, hipStream_t, int, const RunArgs &); };
+template <int NPB, int NCBW, int KS, int NTK>
+constexpr RunBuild run_build() { return {NPB, NCBW, KS, NTK, &launch_lds<k_conv3x3_run_f16<NPB, NCBW, KS, NTK>, RunArgs>}; }
+constexpr RunBuild RUN_BUILDS[] = {run_build<5, 2, 4, 4>(), run_build<3, 2, 4, 4>(), run_build<3, 2, 4, 2>(), run_build<2, 2, 4, 4>(),
+                                   run_build<2, 2, 4, 2>(), run_build<2, 1, 8, 4>(), run_build<2, 1, 8, 2>(), run_build<3, 1, 8, 4>()};
 }  // namespace
 
 extern "C" size_t lav_conv3x3_run_f16_workspace_bytes(int channels, int h, int w, int nlayers) {
@@ -346,11 +354,15 @@ extern "C" int lav_conv3x3_run_f16(int channels, int h, int w, int nlayers, cons
     LAV_REQUIRE(run_config(channels, h, w, c), "lav_conv3x3_run_f16: %d channels on %d x %d is not served (lav_conv3x3_run_f16_workspace_bytes returns 0)", channels, h, w);
     LAV_REQUIRE(x && w_f16 && scale && shift && out && amax_in && amax_in_count >= 1, "lav_conv3x3_run_f16: null argument (the first layer's scale comes from amax_in)");
     LAV_REQUIRE(workspace && workspace_bytes >= RUN_MAPS_OFF + 2 * c.map_bytes, "lav_conv3x3_run_f16: workspace too small");
+    const RunBuild *build = nullptr;
+    for (const RunBuild &b : RUN_BUILDS)
+        if (c.NPB == b.NPB && c.NCBW == b.NCBW && c.KS == b.KS && c.NTK == b.NTK) build = &b;
+    LAV_REQUIRE(build, "lav_conv3x3_run_f16: tile %d x %d / %d / %d not built", c.NPB, c.NCBW, c.KS, c.NTK);
     RunArgs a;
     char *ws = static_cast<char *>(workspace);
     const size_t wbytes = lav_conv3x3_run_f16_weight_bytes(channels);
     for (int i = 0; i < RUN_MAX; ++i) {
-        const int j = i < nlayers ? i : nlayers - 1;
+        const int j = layer_of(i, nlayers);
         LAV_REQUIRE(w_f16[j] && scale[j] && shift[j], "lav_conv3x3_run_f16: null argument of layer %d", j);
         a.w[i] = static_cast<const unsigned char *>(w_f16[j]);
         a.wscale[i] = reinterpret_cast<const float *>(a.w[i] + wbytes);   // (the packing's tail: conv_split.hpp)
@@ -361,8 +373,7 @@ extern "C" int lav_conv3x3_run_f16(int channels, int h, int w, int nlayers, cons
     a.amax_in = amax_in; a.amax_in_count = amax_in_count; a.amax_out = amax_out;
     a.abort_word = reinterpret_cast<int *>(ws); a.words = reinterpret_cast<unsigned long long *>(ws + 16);
     a.sticky = reinterpret_cast<int *>(ws + RUN_STICKY_OFF);
-    const char *lim = getenv("LAV_CHAIN_SPIN_LIMIT");   // test knob: 0 makes every wait that is not satisfied at once a time-out
-    a.spin_limit = lim ? std::max(0ll, atoll(lim)) : (1ll << 21);
+    a.spin_limit = chain_spin_limit();
     a.C = channels; a.H = h; a.W = w; a.L = nlayers; a.NS = c.NS; a.data_bytes = (int)c.data_bytes;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nwg = h * c.NS;
@@ -370,25 +381,12 @@ extern "C" int lav_conv3x3_run_f16(int channels, int h, int w, int nlayers, cons
     LAV_HIP(hipMemsetAsync(ws, 0, (16 + (size_t)(nlayers - 1) * nwg * 8 + 15) / 16 * 16, st));
     const size_t lds = c.data_bytes + RUN_TAIL_LDS;
     const int tok = timer_begin("conv3x3_run", st);
-    bool done = false;
-#define LAV_RUN_CASE(NPB_, NCBW_, KS_, NTK_) if (!done && c.NPB == NPB_ && c.NCBW == NCBW_ && c.KS == KS_ && c.NTK == NTK_) { \
-        static bool attr = false; \
-        if (!attr) { LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv3x3_run_f16<NPB_, NCBW_, KS_, NTK_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr = true; } \
-        hipLaunchKernelGGL((k_conv3x3_run_f16<NPB_, NCBW_, KS_, NTK_>), dim3(nwg), dim3(512), lds, st, a); \
-        done = true; }
-    LAV_RUN_CASE(5, 2, 4, 4) LAV_RUN_CASE(3, 2, 4, 4) LAV_RUN_CASE(3, 2, 4, 2) LAV_RUN_CASE(2, 2, 4, 4) LAV_RUN_CASE(2, 2, 4, 2)
-    LAV_RUN_CASE(2, 1, 8, 4) LAV_RUN_CASE(2, 1, 8, 2) LAV_RUN_CASE(3, 1, 8, 4)
-#undef LAV_RUN_CASE
+    const int rc = build->launch(dim3(nwg), dim3(512), lds, st, 160 * 1024, a);
     timer_end(tok, st);
-    LAV_REQUIRE(done, "lav_conv3x3_run_f16: tile %d x %d / %d / %d not built", c.NPB, c.NCBW, c.KS, c.NTK);
-    LAV_LAUNCH_CHECK();
-    return LAV_OK;
+    return rc;
 }
 
 extern "C" int lav_conv3x3_run_f16_status(const void *workspace, int *h_timeouts_launches2, void *stream) {
     LAV_REQUIRE(workspace && h_timeouts_launches2, "lav_conv3x3_run_f16_status: bad argument");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    LAV_HIP(hipMemcpyAsync(h_timeouts_launches2, static_cast<const char *>(workspace) + RUN_STICKY_OFF, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-    LAV_HIP(hipStreamSynchronize(st));
-    return LAV_OK;
+    return read_status(workspace, RUN_STICKY_OFF, h_timeouts_launches2, static_cast<hipStream_t>(stream));
 }

@@ -194,13 +194,7 @@ int launch_smallcin_t(const SmallCinArgs &a, dim3 grid, hipStream_t st) {
     constexpr int SC_TH = 4 * PPT;
     constexpr int PW = (SC_TW - 1) * S + K, PH = (SC_TH - 1) * S + K, PWS = PW | 1;
     constexpr size_t lds = (size_t)(K * K * CIN * COUT + CIN * PH * PWS + 3 * COUT) * sizeof(float);
-    static bool attr = false;
-    if (!attr) {
-        LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_smallcin<CIN, K, S, COUT, CS, PPT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
-    hipLaunchKernelGGL((k_conv_smallcin<CIN, K, S, COUT, CS, PPT>), grid, dim3(128 * CS), lds, st, a);
-    return LAV_OK;
+    return launch_lds<k_conv_smallcin<CIN, K, S, COUT, CS, PPT>>(grid, dim3(128 * CS), lds, st, (int)lds, a);
 }
 
 inline int launch_smallcin(const lav_conv &c, const Plan &p, const ConvArgs &ca, hipStream_t st) {
@@ -218,7 +212,5 @@ inline int launch_smallcin(const lav_conv &c, const Plan &p, const ConvArgs &ca,
     if (c.kh == 7) rc = launch_smallcin_t<3, 7, 2, 64, 4, 2>(a, grid, st);
     else rc = launch_smallcin_t<3, 3, 2, 16, 2, 2>(a, grid, st);
     timer_end(tok, st);
-    if (rc) return rc;
-    LAV_LAUNCH_CHECK();
-    return LAV_OK;
+    return rc;
 }

@@ -219,11 +219,6 @@ inline SplitPlan choose_split(const lav_conv &c, const Plan &p) {
 
 template <int MP, int MC, int WPX, int NT, int G, bool TP = false>
 int launch_split_g(const SplitArgs &sa, dim3 grid, size_t lds, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_split<MP, MC, WPX, NT, G, TP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr = true;
-    }
     // Round 4 made this workgroup take the CU's whole LDS whatever its tiles need, to keep LDS-using kernels off its CUs: the
     // finite-but-wrong results beside it were taken for an LDS effect.  Round 5 found the cause - packed fp32 instructions with an
     // op_sel bit in the VICTIMS (common.hpp) - and removed those instructions from the library, so the launch asks for what it needs
@@ -233,8 +228,8 @@ int launch_split_g(const SplitArgs &sa, dim3 grid, size_t lds, hipStream_t st) {
         const char *e = getenv("LAV_SPLIT_LDS_EXCLUSIVE"), *g = getenv("LAV_LDS_EXCLUSIVE");
         return (e && atoi(e) != 0) || (g && atoi(g) != 0);
     }();
-    hipLaunchKernelGGL((k_conv_split<MP, MC, WPX, NT, G, TP>), grid, dim3(512), exclusive ? (size_t)160 * 1024 : (lds + 15) / 16 * 16 + 16, st, sa);   // (+ the two sync words, SplitArgs::sync_off)
-    return LAV_OK;
+    // (+ 16: the two sync words, SplitArgs::sync_off)
+    return launch_lds<k_conv_split<MP, MC, WPX, NT, G, TP>>(grid, dim3(512), exclusive ? (size_t)160 * 1024 : (lds + 15) / 16 * 16 + 16, st, 160 * 1024, sa);
 }
 template <int MP, int MC, int WPX>
 int launch_split_t(const SplitArgs &sa, dim3 grid, size_t lds, hipStream_t st) {
@@ -356,20 +351,10 @@ inline int launch_split(const lav_conv &c, const Plan &p, const SplitPlan &sp, c
         const size_t lds16 = lds_in16 + (size_t)3 * G16 * NBLK * 2 * 1024;
         s.sync_off = (int)((lds16 + 15) / 16 * 16);
         rc = launch_split_f16(&s, sizeof(s), sp.MP, sp.MC, sp.WPX, sp.tp, grid.x, grid.y, grid.z, (size_t)s.sync_off + 16, st);
-        if (rc) return rc;
-        if (sp.ksplit > 1) {
-            const long total = (long)c.batch * a.cout * p.OH * p.OW;
-            hipLaunchKernelGGL(k_conv_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a, c.batch, io.out);
-        }
-        timer_end(tok, st);
-        LAV_LAUNCH_CHECK();
-        print_trace();
-        return LAV_OK;
-    }
-    if (sp.tp) {
+    } else if (sp.tp) {
         if (sp.MP == 1 && sp.MC == 2 && sp.WPX == 4 && sp.tap_group == 4) rc = launch_split_g<1, 2, 4, SPLIT_NT_TP, 4, true>(s, grid, sp.lds, st);
         else if (sp.MP == 2 && sp.MC == 2 && sp.WPX == 4 && sp.tap_group == 1) rc = launch_split_g<2, 2, 4, SPLIT_NT_TP, 1, true>(s, grid, sp.lds, st);
-        else return fail(LAV_EINVAL, "lav_conv2d: tap-pair split tile %dx%d/%d G%d not built", sp.MP, sp.MC, sp.WPX, sp.tap_group);
+        else rc = fail(LAV_EINVAL, "lav_conv2d: tap-pair split tile %dx%d/%d G%d not built", sp.MP, sp.MC, sp.WPX, sp.tap_group);
     } else
     switch (sp.MP * 100 + sp.MC * 10 + sp.WPX) {
         case 224: rc = launch_split_t<2, 2, 4>(s, grid, sp.lds, st); break;
@@ -378,14 +363,14 @@ inline int launch_split(const lav_conv &c, const Plan &p, const SplitPlan &sp, c
         case 222: rc = launch_split_t<2, 2, 2>(s, grid, sp.lds, st); break;
         case 122: rc = launch_split_t<1, 2, 2>(s, grid, sp.lds, st); break;
         case 112: rc = launch_split_t<1, 1, 2>(s, grid, sp.lds, st); break;
-        default: return fail(LAV_EINVAL, "lav_conv2d: split tile %dx%d/%d not built", sp.MP, sp.MC, sp.WPX);
+        default: rc = fail(LAV_EINVAL, "lav_conv2d: split tile %dx%d/%d not built", sp.MP, sp.MC, sp.WPX);
     }
-    if (rc) return rc;
-    if (sp.ksplit > 1) {
+    if (!rc && sp.ksplit > 1) {
         const long total = (long)c.batch * a.cout * p.OH * p.OW;
         hipLaunchKernelGGL(k_conv_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a, c.batch, io.out);
     }
-    timer_end(tok, st);
+    timer_end(tok, st);   // (on every path: a slot left open would never be read)
+    if (rc) return rc;
     LAV_LAUNCH_CHECK();
     print_trace();
     return LAV_OK;

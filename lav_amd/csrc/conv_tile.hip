@@ -23,6 +23,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "persistent.hpp"
 #include "split_arith.hpp"
 
 namespace {
@@ -270,13 +271,7 @@ bool tile_config(int channels, int h, int w, int nlayers, TileConfig &c) {
 
 template <int TH, int TW, int L>
 int tile_launch(const TileArgs &a, const TileConfig &c, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv3x3_tile_f16<TH, TW, L>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr = true;
-    }
-    hipLaunchKernelGGL((k_conv3x3_tile_f16<TH, TW, L>), dim3(c.tiles), dim3(512), c.lds, st, a);
-    return LAV_OK;
+    return launch_lds<k_conv3x3_tile_f16<TH, TW, L>>(dim3(c.tiles), dim3(512), c.lds, st, 160 * 1024, a);
 }
 }  // namespace
 
@@ -298,7 +293,7 @@ extern "C" int lav_conv3x3_tile_f16(int channels, int h, int w, int nlayers, con
     LAV_REQUIRE(x && w_f16 && scale && shift && out && amax_in && amax_in_count >= 1, "lav_conv3x3_tile_f16: null argument (the first layer's scale comes from amax_in)");
     TileArgs a;
     for (int i = 0; i < TILE_MAX_L; ++i) {
-        const int j = i < nlayers ? i : nlayers - 1;
+        const int j = layer_of(i, nlayers);
         LAV_REQUIRE(w_f16[j] && scale[j] && shift[j], "lav_conv3x3_tile_f16: null argument of layer %d", j);
         a.w[i] = static_cast<const unsigned char *>(w_f16[j]);
         a.wscale[i] = reinterpret_cast<const float *>(a.w[i] + TILE_W_BYTES);   // (the packing's tail: conv_split.hpp)
@@ -311,8 +306,6 @@ extern "C" int lav_conv3x3_tile_f16(int channels, int h, int w, int nlayers, con
     int rc;
     if (c.th == 8) rc = nlayers == 1 ? tile_launch<8, 16, 1>(a, c, st) : nlayers == 2 ? tile_launch<8, 16, 2>(a, c, st) : tile_launch<8, 16, 3>(a, c, st);
     else rc = nlayers == 1 ? tile_launch<16, 8, 1>(a, c, st) : nlayers == 2 ? tile_launch<16, 8, 2>(a, c, st) : tile_launch<16, 8, 3>(a, c, st);
-    if (rc != LAV_OK) return rc;
-    timer_end(tok, st);
-    LAV_LAUNCH_CHECK();
-    return LAV_OK;
+    timer_end(tok, st);   // (also when the launch failed: the slot that timer_begin opened is closed on every path)
+    return rc;
 }

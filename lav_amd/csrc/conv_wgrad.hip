@@ -588,11 +588,7 @@ int wgrad_blocks(int B, int cin, int cout, int H, int W, int prologue, int tasks
     // Blocks of rows per image, by a cost in steps: a task walks nseg x (rows + 3) steps (three prologue steps per segment fill the row
     // ring), the chip runs one task per CU at a time.  tools/wgrad_probe.py: 64 -> 64 @160 x 32 images 738 us at 20 blocks of 8 rows
     // (640 tasks: three rounds, 27 % prologue) against 460 us at 8 blocks of 20 rows (256 tasks: one round).
-    static const int cus = [] {
-        int dev = 0, v = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-        return v > 0 ? v : 256;
-    }();
+    const int cus = cu_count();
     const long tiles = (long)(cin / T_CI) * (cout / T_CO) * tasks_per_tile;
     const int nseg = (W + PX - 1) / PX;
     int best = 1;
@@ -613,6 +609,16 @@ namespace {
 // row blocks per image of a (kernel size, stride) case; prologue steps and tasks per tile as the three kernels have them
 int wgrad_blocks_of(int batch, int cin, int cout, int h, int w, int ksize, int stride) {
     return ksize == 7 ? wgrad_blocks(batch, cin, cout, h / 2, w / 2, 1, 7) : wgrad_blocks(batch, cin, cout, h / stride, w / stride, stride == 1 ? 3 : 2);
+}
+
+// the kernel of a (kernel size, stride) case on F16 ? two fp16 : three bf16 pieces per operand; every one may use the LDS it needs
+template <bool F16>
+int wgrad_launch(const WgradArgs &a, int ksize, int stride, int nslices, hipStream_t st) {
+    constexpr int NPC = F16 ? 2 : 3;
+    const dim3 grid(a.ntiles, nslices), block(512);
+    if (ksize == 7) return launch_lds<k_conv_wgrad_k7<F16>>(dim3(a.ntiles * 7, nslices), block, lds_bytes_k7(NPC), st, lds_bytes_k7(NPC), a);
+    if (stride == 1) return launch_lds<k_conv_wgrad<F16>>(grid, block, lds_bytes(NPC), st, lds_bytes(NPC), a);
+    return launch_lds<k_conv_wgrad_s2<F16>>(grid, block, lds_bytes_s2(NPC), st, lds_bytes_s2(NPC), a);
 }
 }  // namespace
 
@@ -643,16 +649,6 @@ extern "C" int lav_conv_wgrad_amax(const float *x, const float *dy, int batch, i
     const size_t need = lav_conv_wgrad_workspace_bytes(batch, cin, cout, h, w, ksize, stride);
     if (!workspace || workspace_bytes < need) return fail(LAV_EWORKSPACE, "lav_conv_wgrad: workspace %zu < %zu bytes", workspace_bytes, need);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    static bool attr = false;
-    if (!attr) {
-        LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_wgrad<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(3)));
-        LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_wgrad_s2<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes_s2(3)));
-        LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_wgrad_k7<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes_k7(3)));
-        LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_wgrad<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(2)));
-        LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_wgrad_s2<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes_s2(2)));
-        LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_conv_wgrad_k7<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes_k7(2)));
-        attr = true;
-    }
     const int oh = h / stride, ow = w / stride;
     WgradArgs a;
     a.x = x; a.dy = dy; a.partial = static_cast<float *>(workspace);
@@ -665,19 +661,12 @@ extern "C" int lav_conv_wgrad_amax(const float *x, const float *dy, int batch, i
     const int nslices = batch * a.nblocks;
     LAV_REQUIRE(nslices <= 65535, "lav_conv_wgrad: %d slices", nslices);
     const int tok = timer_begin("conv_wgrad", st);
-    if (f16) {
-        if (ksize == 7) hipLaunchKernelGGL(k_conv_wgrad_k7<true>, dim3(a.ntiles * 7, nslices), dim3(512), lds_bytes_k7(2), st, a);
-        else if (stride == 1) hipLaunchKernelGGL(k_conv_wgrad<true>, dim3(a.ntiles, nslices), dim3(512), lds_bytes(2), st, a);
-        else hipLaunchKernelGGL(k_conv_wgrad_s2<true>, dim3(a.ntiles, nslices), dim3(512), lds_bytes_s2(2), st, a);
-    } else {
-        if (ksize == 7) hipLaunchKernelGGL(k_conv_wgrad_k7<false>, dim3(a.ntiles * 7, nslices), dim3(512), lds_bytes_k7(3), st, a);
-        else if (stride == 1) hipLaunchKernelGGL(k_conv_wgrad<false>, dim3(a.ntiles, nslices), dim3(512), lds_bytes(3), st, a);
-        else hipLaunchKernelGGL(k_conv_wgrad_s2<false>, dim3(a.ntiles, nslices), dim3(512), lds_bytes_s2(3), st, a);
-    }
+    const int rc = f16 ? wgrad_launch<true>(a, ksize, stride, nslices, st) : wgrad_launch<false>(a, ksize, stride, nslices, st);
     const int ntaps = ksize * ksize;
     const long total = (long)a.ntiles * ntaps * T_CO * T_CI;
-    hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.partial, nslices, a.ntiles, a.ntile_ci, cin, cout, ntaps, dw);
+    if (!rc) hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.partial, nslices, a.ntiles, a.ntile_ci, cin, cout, ntaps, dw);
     timer_end(tok, st);
+    if (rc) return rc;
     LAV_LAUNCH_CHECK();
     return LAV_OK;
 }

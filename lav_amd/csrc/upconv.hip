@@ -161,6 +161,10 @@ inline bool up_geom(int batch, int cin, int cout, int ih, int iw, int k, int pad
     g.gz = batch * k;
     return true;
 }
+
+using UpLaunch = int (*)(dim3, dim3, size_t, hipStream_t, int, const UpArgs &);
+template <int S, int CIN, int PAD>
+constexpr UpLaunch up_launch = &launch_lds<k_upconv_pointwise<S, CIN, PAD>, UpArgs>;
 }  // namespace
 
 extern "C" size_t lav_upconv_pointwise_packed_floats(int cin, int cout, int k) {
@@ -205,16 +209,14 @@ extern "C" int lav_upconv_pointwise(int batch, int cin, int cout, int ih, int iw
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(g.gx, g.gy, g.gz);
     const size_t lds = (size_t)4 * cin * 32 * sizeof(float);
+    // [kernel == 4][cin == 128][pad]: the cases up_geom admits (kernel 1 has no padding)
+    static constexpr UpLaunch table[2][2][4] = {{{up_launch<1, 64, 0>}, {up_launch<1, 128, 0>}},
+                                                {{up_launch<4, 64, 0>, up_launch<4, 64, 1>, up_launch<4, 64, 2>, up_launch<4, 64, 3>},
+                                                 {up_launch<4, 128, 0>, up_launch<4, 128, 1>, up_launch<4, 128, 2>, up_launch<4, 128, 3>}}};
+    const UpLaunch launch = table[k == 4][cin == 128][pad];
+    LAV_REQUIRE(launch, "lav_upconv_pointwise: kernel %d with %d channels and padding %d is not built", k, cin, pad);
     const int tok = timer_begin("upconv_pointwise", st);
-#define LAV_UP_CASE(S_, CIN_, PAD_) if (k == S_ && cin == CIN_ && pad == PAD_) { \
-        static bool attr = false; \
-        if (!attr) { LAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_upconv_pointwise<S_, CIN_, PAD_>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024)); attr = true; } \
-        hipLaunchKernelGGL((k_upconv_pointwise<S_, CIN_, PAD_>), grid, dim3(256), lds, st, a); }
-    LAV_UP_CASE(1, 64, 0) LAV_UP_CASE(1, 128, 0)
-    LAV_UP_CASE(4, 64, 0) LAV_UP_CASE(4, 64, 1) LAV_UP_CASE(4, 64, 2) LAV_UP_CASE(4, 64, 3)
-    LAV_UP_CASE(4, 128, 0) LAV_UP_CASE(4, 128, 1) LAV_UP_CASE(4, 128, 2) LAV_UP_CASE(4, 128, 3)
-#undef LAV_UP_CASE
+    const int rc = launch(grid, dim3(256), lds, st, 64 * 1024, a);
     timer_end(tok, st);
-    LAV_LAUNCH_CHECK();
-    return LAV_OK;
+    return rc;
 }

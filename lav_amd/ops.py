@@ -1335,13 +1335,18 @@ class pair_chain_region:
         return False
 
 
-def pair_chain_status(device, stream=None):
-    """(workgroups that gave up, launches) of lav_conv1d_pair_chain on `stream` (default: the current one) since its workspace
-    was created.  Synchronises that stream."""
-    st = stream if stream is not None else torch.cuda.current_stream()
+def _device_and_stream(device, stream):
+    """`device` with its index filled in and `stream` (default: the current one): what the keys of _workspaces are made of"""
     device = torch.device(device)
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
+    return device, stream if stream is not None else torch.cuda.current_stream()
+
+
+def pair_chain_status(device, stream=None):
+    """(workgroups that gave up, launches) of lav_conv1d_pair_chain on `stream` (default: the current one) since its workspace
+    was created.  Synchronises that stream."""
+    device, st = _device_and_stream(device, stream)
     ws = _workspaces.get(("pair_chain", device, st.cuda_stream))
     if ws is None:
         return (0, 0)
@@ -1395,29 +1400,38 @@ class ConvRun:
     def uses_amax(self, B: int, h: int, w: int) -> bool:
         return self.takes(B, h, w)
 
+    _served_by = "lav_conv3x3_run_f16_workspace_bytes"   # (named by the error for an input that takes() refuses)
+
+    def _amax_count(self, lib, ch: int, h: int, w: int) -> int:
+        return lib.lav_conv3x3_run_f16_amax_count(ch, h, w)
+
+    def _launch(self, lib, x, w_f16, scale, shift, out, a_in, n_in, a_out):
+        ch, h, w = x.shape[1:]
+        # one workspace per run, shape AND stream (the maps and the hand-off words are private to the launches of one stream)
+        ws = _workspace(("conv_run", id(self), ch, h, w), lib.lav_conv3x3_run_f16_workspace_bytes(ch, h, w, self._n), x.device)
+        check(lib.lav_conv3x3_run_f16(ch, h, w, self._n, _ptr(x), w_f16, scale, shift, _ptr(out), _ptr(a_in), n_in, _ptr(a_out), _ptr(ws), ws.numel(),
+                                      _stream()), "lav_conv3x3_run_f16")
+
     def __call__(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, amax_in: Optional["Amax"] = None,
                  amax_out: Optional["Amax"] = None) -> torch.Tensor:
         lib = _lib.load()
         x = _f32c(x, "x")
         B, ch, h, w = x.shape
         if ch != self.ch or not self.takes(B, h, w):
-            raise RuntimeError(f"ConvRun: input {tuple(x.shape)} is not served (lav_conv3x3_run_f16_workspace_bytes)")
+            raise RuntimeError(f"{type(self).__name__}: input {tuple(x.shape)} is not served ({self._served_by})")
         if out is None:
             out = torch.empty_like(x)
         n = self._n
-        # one workspace per run, shape AND stream (the maps and the hand-off words are private to the launches of one stream)
-        ws = _workspace(("conv_run", id(self), ch, h, w), lib.lav_conv3x3_run_f16_workspace_bytes(ch, h, w, n), x.device)
         if amax_in is not None and amax_in.count > 0:
             a_in, n_in = amax_in.buf, amax_in.count
         else:   # nobody left the input's maxima: measure it (one launch more)
             a_in = _workspace(("conv_run_amax", id(self)), 512 * 4, x.device).view(torch.float32)
             n_in = 512
             check(lib.lav_absmax_parts(_ptr(x), x.numel(), _ptr(a_in), _stream()), "lav_absmax_parts")
-        a_out = amax_out.take(lib.lav_conv3x3_run_f16_amax_count(ch, h, w)) if amax_out is not None else None
+        a_out = amax_out.take(self._amax_count(lib, ch, h, w)) if amax_out is not None else None
         pa = lambda ts: (C.c_void_p * n)(*[t if isinstance(t, int) else t.data_ptr() for t in ts])
-        check(lib.lav_conv3x3_run_f16(ch, h, w, n, _ptr(x), pa([l.w.data_ptr() + 4 * self._woff for l in self.layers]),
-                                      pa([l.scale for l in self.layers]), pa([l.shift for l in self.layers]), _ptr(out), _ptr(a_in), n_in,
-                                      _ptr(a_out), _ptr(ws), ws.numel(), _stream()), "lav_conv3x3_run_f16")
+        self._launch(lib, x, pa([l.w.data_ptr() + 4 * self._woff for l in self.layers]), pa([l.scale for l in self.layers]),
+                     pa([l.shift for l in self.layers]), out, a_in, n_in, a_out)
         return out
 
 
@@ -1435,40 +1449,24 @@ class ConvTileRun(ConvRun):
     workgroup owns an output tile for all layers, stages the input tile with its halo once and keeps the intermediate maps in LDS.
     The same layer checks, the same calling convention; no workspace and nothing that can time out."""
 
+    _served_by = "lav_conv3x3_tile_f16_lds_bytes"
+
     def takes(self, B: int, h: int, w: int) -> bool:
         return B == 1 and _lib.load().lav_conv3x3_tile_f16_lds_bytes(self.ch, h, w, self._n) > 0
 
-    def __call__(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, amax_in: Optional["Amax"] = None,
-                 amax_out: Optional["Amax"] = None) -> torch.Tensor:
-        lib = _lib.load()
-        x = _f32c(x, "x")
-        B, ch, h, w = x.shape
-        if ch != self.ch or not self.takes(B, h, w):
-            raise RuntimeError(f"ConvTileRun: input {tuple(x.shape)} is not served (lav_conv3x3_tile_f16_lds_bytes)")
-        if out is None:
-            out = torch.empty_like(x)
-        n = self._n
-        if amax_in is not None and amax_in.count > 0:
-            a_in, n_in = amax_in.buf, amax_in.count
-        else:   # nobody left the input's maxima: measure it (one launch more)
-            a_in = _workspace(("conv_run_amax", id(self)), 512 * 4, x.device).view(torch.float32)
-            n_in = 512
-            check(lib.lav_absmax_parts(_ptr(x), x.numel(), _ptr(a_in), _stream()), "lav_absmax_parts")
-        a_out = amax_out.take(lib.lav_conv3x3_tile_f16_amax_count(ch, h, w, n)) if amax_out is not None else None
-        pa = lambda ts: (C.c_void_p * n)(*[t if isinstance(t, int) else t.data_ptr() for t in ts])
-        check(lib.lav_conv3x3_tile_f16(ch, h, w, n, _ptr(x), pa([l.w.data_ptr() + 4 * self._woff for l in self.layers]),
-                                       pa([l.scale for l in self.layers]), pa([l.shift for l in self.layers]), _ptr(out), _ptr(a_in), n_in,
-                                       _ptr(a_out), _stream()), "lav_conv3x3_tile_f16")
-        return out
+    def _amax_count(self, lib, ch: int, h: int, w: int) -> int:
+        return lib.lav_conv3x3_tile_f16_amax_count(ch, h, w, self._n)
+
+    def _launch(self, lib, x, w_f16, scale, shift, out, a_in, n_in, a_out):
+        ch, h, w = x.shape[1:]
+        check(lib.lav_conv3x3_tile_f16(ch, h, w, self._n, _ptr(x), w_f16, scale, shift, _ptr(out), _ptr(a_in), n_in, _ptr(a_out), _stream()),
+              "lav_conv3x3_tile_f16")
 
 
 def bev_run_status(device, stream=None):
     """(workgroups that gave up, launches) of the lav_conv3x3_run_f16 launches on `stream` (default: the current one), summed over
     the runs' workspaces.  Synchronises that stream."""
-    st = stream if stream is not None else torch.cuda.current_stream()
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device, st = _device_and_stream(device, stream)
     tot = [0, 0]
     for (key, dev, s), ws in list(_workspaces.items()):
         if isinstance(key, tuple) and key and key[0] == "conv_run" and dev == device and s == st.cuda_stream:

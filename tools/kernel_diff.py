@@ -5,7 +5,8 @@
 
 Every code object of both libraries is disassembled; functions are compared by mangled name, instruction for instruction, with what
 is positional removed: addresses and encodings (the comment behind every instruction) and the literals of pc-relative address
-arithmetic (the s_add_u32 / s_addc_u32 pair behind an s_getpc_b64).  The kernels' register, scratch and LDS figures are compared
+arithmetic (the s_add_u32 / s_addc_u32 pair behind an s_getpc_b64), the zero fill behind a function's last instruction (it depends
+on which function the compiler emitted next: host code that names the kernels in another order moves it).  The kernels' register, scratch and LDS figures are compared
 too.  Prints the kernels only one side has and the ones that differ; exit status 1 if a kernel of the new library differs or is new.
 """
 import glob
@@ -44,6 +45,8 @@ def kernels(lib):
                     elif pcrel and re.match(r"s_addc?_u32 ", ins):
                         ins, pcrel = re.sub(r"(0x[0-9a-f]+|-?\d+)$", "PCREL", ins), pcrel - 1
                     body.append(ins)
+                while body and body[-1] == "...":   # the zero fill up to the next function's alignment: what follows the kernel, not the kernel
+                    body.pop()
                 assert name not in out, f"{name} is defined in two code objects"
                 out[name] = (body, figs.get(name))
     return out
