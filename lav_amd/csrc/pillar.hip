@@ -427,7 +427,7 @@ __global__ __launch_bounds__(256, 2) void k_rows(RowsArgs a, State *__restrict__
     const long cstride = (long)a.ny * a.nx;
     const int xi_row0 = max(a.ny - 1, 0);                       // first key row that lands on canvas row 0
     const int nlay_over = max(0, a.ny - a.nx + 1) + 1;          // layers of a unit that holds the last canvas column
-    const int nlay_max = min(MAX_LAYERS, max(a.nx - xi_row0 + 1, 1) * nlay_over);
+    const int nlay_max = min(MAX_LAYERS, max(a.nx - xi_row0 + 1, 1) * nlay_over);   // (the host's refusal in lav_pillar_scatter_amax counts the same)
     // walking this workgroup's units: one division here, carries afterwards
     const int step_rb = W / a.UPR, step_cu = W - step_rb * a.UPR, step_b = step_rb / a.ny, step_r = step_rb - step_b * a.ny;
     barrier_lds();   // LDS state set up
@@ -949,8 +949,10 @@ struct Workspace {
     int *load, *perm;  // pairing hint of k_rows' workgroups: loads of the previous call, permutation of this one
     int *cell_count, *cell_rank, *kept_rank, *block_sums, *totals;
     unsigned long long *cell_sums;  // [min(ncells, points)][3] fixed-point coordinate sums (training entry lav_pillar_decorate)
-    int cap, upr;
+    int cap;
 };
+
+int units_per_row(const lav_grid *g) { return (g->nx + UW - 1) / UW; }
 
 int bucket_capacity(int max_points, int units_per_cloud) {
     // room for 8x the mean load of a (unit, sub) bucket: the densest unit of a LiDAR-like cloud (the ego vehicle's
@@ -962,12 +964,11 @@ int bucket_capacity(int max_points, int units_per_cloud) {
 }
 
 size_t carve(Arena &ar, Workspace &w, int batch, int max_points, const lav_grid *g, bool with_buckets) {
-    const int upr = (g->nx + UW - 1) / UW;
+    const int upr = units_per_row(g);
     const size_t nunits = (size_t)batch * g->ny * upr;
     const size_t ncells = (size_t)batch * (g->nx + 1) * (g->ny + 1);
     const size_t total = (size_t)batch * max_points;
     const size_t nmax = ncells > total ? ncells : total;
-    w.upr = upr;
     w.cap = bucket_capacity(max_points, g->ny * upr);
     w.state = ar.take<State>(1);
     w.counters = ar.take<int>(2 * NSUB * align_up(nunits, 4));
@@ -1007,6 +1008,11 @@ int persistent_workgroups() {
         return cus * (per >= 1 && per <= 2 ? per : 2);
     }();
     return n;
+}
+
+// workgroups of k_rows = ownership classes of the units = entries of amax_parts
+int rows_workgroups(int batch, const lav_grid *g) {
+    return std::min(std::min(persistent_workgroups(), batch * g->ny * units_per_row(g)), 2048);   // 2048: the pairing tables (load / perm, k_bin's s_key)
 }
 
 // debug: per-workgroup phase times of one k_rows launch (100 MHz wall clock -> us)
@@ -1050,6 +1056,32 @@ void dump_trace(const unsigned long long *d_trace, int nwg, hipStream_t st) {
     }
 }
 
+// The instantiations of k_rows.  Every point width has the MFMA kernel x {16-byte, scalar stores} x {ZB, not}.  The VALU PointNet
+// (LAV_PILLAR_IMPL=valu) and the traced kernel (LAV_PILLAR_TRACE, 16-byte stores only) are debug variants built for the v2 agent's
+// width alone, D = 11: asked for at another width, they run the MFMA kernel.
+using RowsKernel = decltype(&k_rows<11, true, true, false, false>);
+struct RowsEntry { bool mfma, vec4, trace, zb; RowsKernel kernel; };
+template <int D, bool MFMA, bool VEC4, bool TRACE, bool ZB>
+constexpr RowsEntry rows_entry = {MFMA, VEC4, TRACE, ZB, k_rows<D, MFMA, VEC4, TRACE, ZB>};
+template <int D>
+constexpr RowsEntry rows_mfma[] = {rows_entry<D, true, true, false, false>, rows_entry<D, true, true, false, true>,
+                                   rows_entry<D, true, false, false, false>, rows_entry<D, true, false, false, true>};
+constexpr RowsEntry rows_debug[] = {rows_entry<11, false, true, false, false>, rows_entry<11, false, true, false, true>,
+                                    rows_entry<11, false, false, false, false>, rows_entry<11, false, false, false, true>,
+                                    rows_entry<11, true, true, true, false>, rows_entry<11, true, true, true, true>};
+template <int D>
+const RowsEntry *rows_entry_for(bool valu, bool vec4, bool trace, bool zb) {
+    trace = trace && D == 11 && vec4;   // the trace takes precedence over LAV_PILLAR_IMPL
+    const bool mfma = D != 11 || trace || !valu;
+    auto is = [&](const RowsEntry &e) { return e.mfma == mfma && e.vec4 == vec4 && e.trace == trace && e.zb == zb; };
+    for (const RowsEntry &e : rows_debug) if (is(e)) return &e;
+    return std::find_if(std::begin(rows_mfma<D>), std::end(rows_mfma<D>), is);   // (always found: all four are listed)
+}
+
+RowsArgs rows_args(const PillarArgs &a, const Workspace &w, float *amax) {
+    return {a.batch, a.nx, a.ny, a.UPR, a.NUP, a.cap, a.rstride, a.min_x, a.min_y, a.ppm, w.perm, w.load, nullptr, amax};
+}
+
 template <int D>
 int launch_canvas(const PillarArgs &a, const Workspace &w, const lav_pointnet *net, float *canvas, bool want_keys, float *amax, hipStream_t st) {
     const long total = (long)a.batch * a.max_points;
@@ -1065,61 +1097,29 @@ int launch_canvas(const PillarArgs &a, const Workspace &w, const lav_pointnet *n
                        w.ovf, want_keys ? w.key : nullptr, net->w1, net->b1, net->w2, net->b2, w.wpack, w.load, w.perm, canvas, canvas_floats, nzero);
     timer_end(tok_prep, st);
     LAV_LAUNCH_CHECK();
-    const int W = a.nwg;
     const bool vec4 = a.nx % 4 == 0 && reinterpret_cast<uintptr_t>(canvas) % 16 == 0;
     static const bool want_trace = getenv("LAV_PILLAR_TRACE") != nullptr;
     static unsigned long long *d_trace = nullptr;
     static int trace_runs = 0;
-    RowsArgs at;
-    at.batch = a.batch; at.nx = a.nx; at.ny = a.ny; at.UPR = a.UPR; at.NUP = a.NUP; at.cap = a.cap; at.rstride = a.rstride;
-    at.min_x = a.min_x; at.min_y = a.min_y; at.ppm = a.ppm; at.trace = nullptr;
-    at.perm = w.perm; at.load = w.load; at.amax = amax;
-
-    if (want_trace && vec4) {
+    const RowsEntry &rows = *rows_entry_for<D>(use_valu_impl(), vec4, want_trace, zero_in_bin);
+    RowsArgs at = rows_args(a, w, amax);
+    if (rows.trace) {
         if (!d_trace) LAV_HIP(hipMalloc(&d_trace, (size_t)persistent_workgroups() * 16 * sizeof(unsigned long long)));
         LAV_HIP(hipMemsetAsync(d_trace, 0, (size_t)persistent_workgroups() * 16 * sizeof(unsigned long long), st));
         at.trace = d_trace;
     }
     const int tok = timer_begin("pointnet_scatter", st);
-#define LAV_ROWS(MFMA, VEC, TR)                                                                                                 \
-    do {                                                                                                                        \
-        if (zero_in_bin)                                                                                                        \
-            hipLaunchKernelGGL((k_rows<D, MFMA, VEC, TR, true>), dim3(W), dim3(256), 0, st, at, w.state, w.counters, w.buckets, w.ovf, net->w1, \
-                               net->b1, net->w2, net->b2, w.wpack, canvas);                                                     \
-        else                                                                                                                    \
-            hipLaunchKernelGGL((k_rows<D, MFMA, VEC, TR, false>), dim3(W), dim3(256), 0, st, at, w.state, w.counters, w.buckets, w.ovf, net->w1, \
-                               net->b1, net->w2, net->b2, w.wpack, canvas);                                                     \
-    } while (0)
-    if constexpr (D == 11) {   // debug variants exist for the v2 agent's point width only
-        if (want_trace && vec4) {
-            LAV_ROWS(true, true, true);
-            timer_end(tok, st);
-            LAV_LAUNCH_CHECK();
-            if (++trace_runs == 20) dump_trace(d_trace, W, st);
-            return LAV_OK;
-        }
-        if (use_valu_impl()) {
-            if (vec4) LAV_ROWS(false, true, false); else LAV_ROWS(false, false, false);
-            timer_end(tok, st);
-            LAV_LAUNCH_CHECK();
-            return LAV_OK;
-        }
-    }
-    {
-        if (vec4) LAV_ROWS(true, true, false); else LAV_ROWS(true, false, false);
-    }
-#undef LAV_ROWS
+    hipLaunchKernelGGL(rows.kernel, dim3(a.nwg), dim3(256), 0, st, at, w.state, w.counters, w.buckets, w.ovf, net->w1, net->b1, net->w2, net->b2,
+                       w.wpack, canvas);
     timer_end(tok, st);
     LAV_LAUNCH_CHECK();
+    if (rows.trace && ++trace_runs == 20) dump_trace(d_trace, a.nwg, st);
     return LAV_OK;
 }
 
 int fill_args(PillarArgs &a, const float *points, const int *h_num_points, int batch, int max_points, int D, const lav_grid *grid,
               const Workspace &w, const char *who) {
-    a.points = points;
-    a.batch = batch;
-    a.max_points = max_points;
-    a.D = D;
+    a.points = points; a.batch = batch; a.max_points = max_points; a.D = D;
     for (int b = 0; b < batch; ++b) {
         LAV_REQUIRE(h_num_points[b] >= 0, "%s: negative num_points", who);
         a.n[b] = h_num_points[b] < max_points ? h_num_points[b] : max_points;
@@ -1127,12 +1127,42 @@ int fill_args(PillarArgs &a, const float *points, const int *h_num_points, int b
     for (int b = batch; b < MAX_BATCH; ++b) a.n[b] = 0;
     a.min_x = grid->min_x; a.max_x = grid->max_x; a.min_y = grid->min_y; a.max_y = grid->max_y; a.ppm = grid->ppm;
     a.nx = grid->nx; a.ny = grid->ny; a.KX = grid->nx + 1; a.KY = grid->ny + 1;
-    a.UPR = w.upr;
-    a.NUP = (int)align_up((size_t)batch * grid->ny * w.upr, 4);
+    a.UPR = units_per_row(grid);
+    a.NUP = (int)align_up((size_t)batch * grid->ny * a.UPR, 4);
     a.cap = w.cap;
     a.rstride = rec_stride_host(D);
-    a.nwg = std::min(std::min(persistent_workgroups(), batch * grid->ny * w.upr), 2048);   // 2048: the pairing tables (load / perm, k_bin's s_key)
+    a.nwg = rows_workgroups(batch, grid);
     a.trace = nullptr;
+    return LAV_OK;
+}
+
+// The index outputs (unique_coords, inverse, counts) of both entry points, from the keys in w.key (one per row, -1 = dropped).
+// index_ranks: occupied cells and kept rows, counted and ranked -> w.cell_count, w.cell_rank, w.kept_rank, w.totals = {pillars,
+// kept rows}.  The caller then writes `inverse` from the ranks (k_inverse / k_dec_sums); index_outputs writes the rest.
+int index_ranks(const PillarArgs &a, const Workspace &w, hipStream_t st) {
+    const long ncells = (long)a.batch * a.KX * a.KY, total = (long)a.batch * a.max_points;
+    LAV_HIP(hipMemsetAsync(w.cell_count, 0, ncells * sizeof(int), st));
+    if (total > 0) {
+        hipLaunchKernelGGL(k_cell_count, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, w.key, w.cell_count);
+        LAV_LAUNCH_CHECK();
+    }
+    const int rc = exclusive_scan(w.cell_count, ncells, 1, w.cell_rank, w.block_sums, w.totals + 0, st);   // ncells > 0: totals[0] is always written
+    if (rc) return rc;
+    if (total > 0) return exclusive_scan(w.key, total, 2, w.kept_rank, w.block_sums, w.totals + 1, st);
+    LAV_HIP(hipMemsetAsync(w.totals + 1, 0, sizeof(int), st));   // no rows: no scan writes it
+    return LAV_OK;
+}
+
+int index_outputs(const PillarArgs &a, const Workspace &w, int *unique_coords, int *counts, hipStream_t st) {
+    const long ncells = (long)a.batch * a.KX * a.KY;
+    if (unique_coords) {
+        hipLaunchKernelGGL(k_unique_coords, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, st, a, w.cell_count, w.cell_rank, ncells, unique_coords);
+        LAV_LAUNCH_CHECK();
+    }
+    if (counts) {
+        hipLaunchKernelGGL(k_counts, dim3(1), dim3(1), 0, st, w.totals + 0, w.totals + 1, counts);
+        LAV_LAUNCH_CHECK();
+    }
     return LAV_OK;
 }
 
@@ -1160,8 +1190,7 @@ extern "C" int lav_pillar_workspace_init(void *workspace, size_t workspace_bytes
 
 extern "C" int lav_pillar_amax_count(int batch, const lav_grid *grid) {
     if (!grid || batch <= 0) return 0;
-    const int upr = (grid->nx + UW - 1) / UW;
-    return std::min(std::min(persistent_workgroups(), batch * grid->ny * upr), 2048);   // = PillarArgs.nwg (fill_args)
+    return rows_workgroups(batch, grid);
 }
 
 extern "C" int lav_pillar_scatter(const float *points, const int *h_num_points, int batch, int max_points, int D,
@@ -1193,7 +1222,7 @@ extern "C" int lav_pillar_scatter_amax(const float *points, const int *h_num_poi
     PillarArgs a;
     int rc = fill_args(a, points, h_num_points, batch, max_points, D, grid, w, "lav_pillar_scatter");
     if (rc) return rc;
-    {   // canvas row 0 collects key rows ny-1..nx, the last column collects key columns nx-1..ny (reference clamp)
+    {   // canvas row 0 collects key rows ny-1..nx, the last column collects key columns nx-1..ny (reference clamp); k_rows' nlay_max counts the same
         const long lay = (long)(a.nx - (a.ny - 1) + 1 > 1 ? a.nx - (a.ny - 1) + 1 : 1) * ((a.ny - a.nx + 1 > 0 ? a.ny - a.nx + 1 : 0) + 1);
         LAV_REQUIRE(lay <= MAX_LAYERS, "lav_pillar_scatter: grid %dx%d needs %ld clamp layers (max %d)", a.nx, a.ny, lay, MAX_LAYERS);
     }
@@ -1204,38 +1233,16 @@ extern "C" int lav_pillar_scatter_amax(const float *points, const int *h_num_poi
         case 8: rc = launch_canvas<8>(a, w, net, canvas, want_idx, amax_parts, st); break;
         default: return fail(LAV_EINVAL, "lav_pillar_scatter: point width D=%d not instantiated (4,8,11)", D);
     }
-    if (rc) return rc;
+    if (rc || !want_idx) return rc;
 
-    if (want_idx) {
-        const long ncells = (long)batch * a.KX * a.KY;
-        const long total = (long)batch * max_points;
-        LAV_HIP(hipMemsetAsync(w.cell_count, 0, ncells * sizeof(int), st));
-        if (total > 0) {
-            hipLaunchKernelGGL(k_cell_count, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, w.key, w.cell_count);
-            LAV_LAUNCH_CHECK();
-        }
-        rc = exclusive_scan(w.cell_count, ncells, 1, w.cell_rank, w.block_sums, w.totals + 0, st);
-        if (rc) return rc;
-        if (total > 0) {
-            rc = exclusive_scan(w.key, total, 2, w.kept_rank, w.block_sums, w.totals + 1, st);
-            if (rc) return rc;
-        } else {
-            LAV_HIP(hipMemsetAsync(w.totals + 1, 0, sizeof(int), st));
-        }
-        if (unique_coords) {
-            hipLaunchKernelGGL(k_unique_coords, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, st, a, w.cell_count, w.cell_rank, ncells, unique_coords);
-            LAV_LAUNCH_CHECK();
-        }
-        if (inverse && total > 0) {
-            hipLaunchKernelGGL(k_inverse, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, w.key, w.kept_rank, w.cell_rank, inverse);
-            LAV_LAUNCH_CHECK();
-        }
-        if (counts) {
-            hipLaunchKernelGGL(k_counts, dim3(1), dim3(1), 0, st, w.totals + 0, w.totals + 1, counts);
-            LAV_LAUNCH_CHECK();
-        }
+    rc = index_ranks(a, w, st);   // keys: k_bin's
+    if (rc) return rc;
+    const long total = (long)batch * max_points;
+    if (inverse && total > 0) {
+        hipLaunchKernelGGL(k_inverse, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, total, w.key, w.kept_rank, w.cell_rank, inverse);
+        LAV_LAUNCH_CHECK();
     }
-    return LAV_OK;
+    return index_outputs(a, w, unique_coords, counts, st);
 }
 
 // =========================================================================================================
@@ -1338,6 +1345,26 @@ __global__ __launch_bounds__(256) void k_smax_bwd(const float *__restrict__ grad
     const int a = argmax[i];
     if (a < n) grad_src[(long)a * C + (i % C)] = grad_out[i];  // every source element is the arg-max of at most one output
 }
+
+int decorate_launches(const PillarArgs &a, const Workspace &w, int *unique_coords, int *inverse, int *kept_src, float *decorated, int *counts,
+                      hipStream_t st) {
+    const long ncells = (long)a.batch * a.KX * a.KY, total = (long)a.batch * a.max_points;
+    const unsigned gp = (unsigned)((total + 255) / 256);
+    if (total > 0) {
+        hipLaunchKernelGGL(k_keys, dim3(gp), dim3(256), 0, st, a, w.key);
+        LAV_LAUNCH_CHECK();
+    }
+    const int rc = index_ranks(a, w, st);
+    if (rc) return rc;
+    if (total > 0) {
+        const long nsum = (ncells < total ? ncells : total) * 3;
+        LAV_HIP(hipMemsetAsync(w.cell_sums, 0, nsum * sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(k_dec_sums, dim3(gp), dim3(256), 0, st, a, w.key, w.cell_rank, w.kept_rank, w.cell_sums, inverse, kept_src);
+        hipLaunchKernelGGL(k_dec_write, dim3(gp), dim3(256), 0, st, a, w.key, w.cell_rank, w.cell_count, w.kept_rank, w.cell_sums, decorated);
+        LAV_LAUNCH_CHECK();
+    }
+    return index_outputs(a, w, unique_coords, counts, st);
+}
 }  // namespace
 
 extern "C" int lav_pillar_decorate(const float *points, const int *h_num_points, int batch, int max_points, int D,
@@ -1352,40 +1379,12 @@ extern "C" int lav_pillar_decorate(const float *points, const int *h_num_points,
     carve(ar, w, batch, max_points, grid, false);
     if (!workspace || !ar.ok()) return fail(LAV_EWORKSPACE, "lav_pillar_decorate: workspace %zu < %zu bytes", workspace_bytes, ar.used);
     PillarArgs a;
-    a.points = points; a.batch = batch; a.max_points = max_points; a.D = D;
-    for (int b = 0; b < MAX_BATCH; ++b) a.n[b] = b < batch ? (h_num_points[b] < max_points ? h_num_points[b] : max_points) : 0;
-    for (int b = 0; b < batch; ++b) LAV_REQUIRE(h_num_points[b] >= 0, "lav_pillar_decorate: negative num_points");
-    a.min_x = grid->min_x; a.max_x = grid->max_x; a.min_y = grid->min_y; a.max_y = grid->max_y; a.ppm = grid->ppm;
-    a.nx = grid->nx; a.ny = grid->ny; a.KX = grid->nx + 1; a.KY = grid->ny + 1;
-    a.UPR = w.upr; a.NUP = 0; a.cap = w.cap; a.nwg = 0; a.trace = nullptr;
-    const long ncells = (long)batch * a.KX * a.KY;
-    const long total = (long)batch * max_points;
-    const unsigned gp = (unsigned)((total + 255) / 256);
-    LAV_HIP(hipMemsetAsync(w.cell_count, 0, ncells * sizeof(int), st));
-    LAV_HIP(hipMemsetAsync(w.totals, 0, 4 * sizeof(int), st));
-    if (total > 0) {
-        hipLaunchKernelGGL(k_keys, dim3(gp), dim3(256), 0, st, a, w.key);
-        hipLaunchKernelGGL(k_cell_count, dim3(gp), dim3(256), 0, st, total, w.key, w.cell_count);
-        LAV_LAUNCH_CHECK();
-    }
-    int rc = exclusive_scan(w.cell_count, ncells, 1, w.cell_rank, w.block_sums, w.totals + 0, st);
+    int rc = fill_args(a, points, h_num_points, batch, max_points, D, grid, w, "lav_pillar_decorate");   // (NUP, nwg, rstride: no kernel here reads them)
     if (rc) return rc;
-    if (total > 0) {
-        rc = exclusive_scan(w.key, total, 2, w.kept_rank, w.block_sums, w.totals + 1, st);
-        if (rc) return rc;
-        const long nsum = (ncells < total ? ncells : total) * 3;
-        LAV_HIP(hipMemsetAsync(w.cell_sums, 0, nsum * sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(k_dec_sums, dim3(gp), dim3(256), 0, st, a, w.key, w.cell_rank, w.kept_rank, w.cell_sums, inverse, kept_src);
-        hipLaunchKernelGGL(k_dec_write, dim3(gp), dim3(256), 0, st, a, w.key, w.cell_rank, w.cell_count, w.kept_rank, w.cell_sums, decorated);
-        LAV_LAUNCH_CHECK();
-    }
-    if (unique_coords) {
-        hipLaunchKernelGGL(k_unique_coords, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, st, a, w.cell_count, w.cell_rank, ncells, unique_coords);
-        LAV_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(k_counts, dim3(1), dim3(1), 0, st, w.totals + 0, w.totals + 1, counts);
-    LAV_LAUNCH_CHECK();
-    return LAV_OK;
+    const int tok = timer_begin("pillar_decorate", st);
+    rc = decorate_launches(a, w, unique_coords, inverse, kept_src, decorated, counts, st);
+    timer_end(tok, st);   // (on every path: a slot left open would never be read)
+    return rc;
 }
 
 extern "C" int lav_scatter_max(const float *src, const int *index, int n, int channels, int num_segments, float *out, int *argmax,

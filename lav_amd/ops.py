@@ -68,6 +68,21 @@ def make_grid(min_x, max_x, min_y, max_y, ppm) -> Grid:
     return Grid(float(min_x), float(max_x), float(min_y), float(max_y), float(ppm), nx, ny)
 
 
+def _pillar_cloud(points: torch.Tensor, num_points: Sequence[int]):
+    """cloud(s) (B, Nmax, D) or (N, D) -> (B, Nmax, D) f32 contiguous in HBM, and the host array of row counts the ABI takes"""
+    points = _f32c(points[None] if points.dim() == 2 else points, "points")
+    if len(num_points) != points.shape[0]:
+        raise RuntimeError("num_points must have one entry per cloud")
+    return points, (C.c_int * points.shape[0])(*[int(n) for n in num_points])
+
+
+def _pillar_index_buffers(points: torch.Tensor):
+    """unique_coords, inverse and the two counts {pillars, kept rows} of a (B, Nmax, D) cloud, sized for the worst case"""
+    total, dev = max(points.shape[0] * points.shape[1], 1), points.device
+    return (torch.empty((total, 3), dtype=torch.int32, device=dev), torch.empty((total,), dtype=torch.int32, device=dev),
+            torch.zeros((2,), dtype=torch.int32, device=dev))
+
+
 def pillar_scatter(points: torch.Tensor, num_points: Sequence[int], grid: Grid, w1, b1, w2, b2,
                    want_indices: bool = False, amax: Optional["Amax"] = None):
     """points (B, Nmax, D) or (N, D) f32 in HBM -> canvas (B, C, ny, nx)
@@ -75,12 +90,8 @@ def pillar_scatter(points: torch.Tensor, num_points: Sequence[int], grid: Grid, 
     amax: an Amax that receives the canvas kernel's per-workgroup maxima (lav_pillar_scatter_amax) and is attached to the canvas
     (amax_of): the first BEV convolution then takes its fp16 scale from them instead of measuring the canvas with a launch."""
     lib = _lib.load()
-    if points.dim() == 2:
-        points = points[None]
-    points = _f32c(points, "points")
+    points, h_num = _pillar_cloud(points, num_points)
     B, nmax, D = points.shape
-    if len(num_points) != B:
-        raise RuntimeError("num_points must have one entry per cloud")
     Cc = w2.shape[1]
     net = PointNet(_ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), D + 5, Cc)
     dev = points.device
@@ -89,13 +100,7 @@ def pillar_scatter(points: torch.Tensor, num_points: Sequence[int], grid: Grid, 
     # zero-filled once and kept per geometry: the head of a pillar workspace is state that every call leaves clean
     # (include/lav_amd.h, workspace contract)
     ws = _workspace(("pillar", B, grid.nx, grid.ny), nbytes, dev)
-    h_num = (C.c_int * B)(*[int(n) for n in num_points])
-    uc = inv = cnt = None
-    if want_indices:
-        total = B * nmax
-        uc = torch.empty((max(total, 1), 3), dtype=torch.int32, device=dev)
-        inv = torch.empty((max(total, 1),), dtype=torch.int32, device=dev)
-        cnt = torch.zeros((2,), dtype=torch.int32, device=dev)
+    uc, inv, cnt = _pillar_index_buffers(points) if want_indices else (None, None, None)
     parts = amax.reset().take(lib.lav_pillar_amax_count(B, C.byref(grid))) if amax is not None else None
     rc = lib.lav_pillar_scatter_amax(_ptr(points) if nmax > 0 else None, h_num, B, nmax, D, C.byref(grid), C.byref(net),
                                      _ptr(canvas), _ptr(uc), _ptr(inv), _ptr(cnt), _ptr(parts), _ptr(ws), ws.numel(), _stream())
@@ -107,7 +112,7 @@ def pillar_scatter(points: torch.Tensor, num_points: Sequence[int], grid: Grid, 
         _drop_workspace(("pillar", B, grid.nx, grid.ny), dev)
     check(rc, "lav_pillar_scatter")
     if want_indices:
-        p, k = [int(v) for v in cnt.tolist()]
+        p, k = cnt.tolist()   # {pillars, kept rows}: the call's one device->host copy
         return canvas, uc[:p], inv[:k]
     return canvas
 
@@ -116,23 +121,16 @@ def pillar_decorate(points: torch.Tensor, num_points: Sequence[int], grid: Grid)
     """Training-side front end of PointPillarNet: points (B, Nmax, D) -> decorated (N_kept, D+5), unique_coords (P,3),
     inverse (N_kept,), kept_src (N_kept,) (int32, all in HBM).  One device->host copy (the two counts)."""
     lib = _lib.load()
-    if points.dim() == 2:
-        points = points[None]
-    points = _f32c(points.detach(), "points")
+    points, h_num = _pillar_cloud(points.detach(), num_points)
     B, nmax, D = points.shape
-    dev = points.device
-    total = max(B * nmax, 1)
-    uc = torch.empty((total, 3), dtype=torch.int32, device=dev)
-    inv = torch.empty((total,), dtype=torch.int32, device=dev)
-    src = torch.empty((total,), dtype=torch.int32, device=dev)
-    dec = torch.empty((total, D + 5), dtype=torch.float32, device=dev)
-    cnt = torch.zeros((2,), dtype=torch.int32, device=dev)
+    uc, inv, cnt = _pillar_index_buffers(points)
+    src = torch.empty_like(inv)
+    dec = torch.empty((inv.shape[0], D + 5), dtype=torch.float32, device=points.device)
     nbytes = lib.lav_pillar_decorate_workspace_bytes(B, nmax, C.byref(grid))
-    ws = _workspace("pillar_decorate", nbytes, dev)
-    h_num = (C.c_int * B)(*[int(n) for n in num_points])
+    ws = _workspace("pillar_decorate", nbytes, points.device)
     check(lib.lav_pillar_decorate(_ptr(points) if nmax > 0 else None, h_num, B, nmax, D, C.byref(grid), _ptr(uc), _ptr(inv),
                                   _ptr(src), _ptr(dec), _ptr(cnt), _ptr(ws), ws.numel(), _stream()), "lav_pillar_decorate")
-    p, k = [int(v) for v in cnt.tolist()]
+    p, k = cnt.tolist()
     return dec[:k], uc[:p], inv[:k], src[:k]
 
 

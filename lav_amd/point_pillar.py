@@ -2,8 +2,8 @@
 signature (lav/models/point_pillar.py:12-116), running on liblav_amd's pillar kernels.
 
 The modules only hold parameters; forward() folds the eval-mode BatchNorm1d into the two Linear
-layers once and enqueues lav_pillar_scatter (voxelise -> sort -> PointNet on MFMA -> scatter-max ->
-canvas).  There is no torch fallback: tensors must live in HBM.
+layers once and enqueues lav_pillar_scatter (bin the points by canvas unit -> PointNet on MFMA ->
+scatter-max -> canvas).  There is no torch fallback: tensors must live in HBM.
 """
 from __future__ import annotations
 

@@ -206,6 +206,23 @@ def test_decorate_refuses_other_widths(D):
     P.assert_exact(dec.cpu().numpy(), ref_of(case)[1].dec, f"{case.name}: decorated after the refusal")
 
 
+def test_decorate_without_points():
+    """S31 at batch 2 without a kept row - max_points = 0, then 16 rows per cloud that all lie outside the grid: every output is empty
+    (the kept-row total comes from a memset in the first call, from the scan in the second); a call with points after them is exact."""
+    empty = P.x_scan_case(0)
+    grid, D = ops.make_grid(*empty.grid.args), empty.D
+    assert empty.points.shape == (2, 0, D) and (empty.grid.nx, empty.grid.ny) == (31, 31)
+    outside = torch.full((2, 16, D), 100.0, device=DEV)
+    for what, pts, n in (("max_points 0", torch.from_numpy(empty.points).to(DEV), empty.n), ("rows outside the grid", outside, [16, 16])):
+        dec, uc, inv, src = ops.pillar_decorate(pts, n, grid)
+        assert (dec.shape, uc.shape, inv.shape, src.shape) == ((0, D + 5), (0, 3), (0,), (0,)), what
+    case = P.x_case("S34", 4, "spread")
+    dec, uc, inv, src = ops.pillar_decorate(torch.from_numpy(case.points).to(DEV), case.n, ops.make_grid(*case.grid.args))
+    ref = ref_of(case)[1]
+    for got, want, name in ((uc, ref.unique_coords, "unique_coords"), (inv, ref.inverse, "inverse"), (src, ref.kept, "kept_src"), (dec, ref.dec, "decorated")):
+        P.assert_exact(got.cpu().numpy(), want, f"{case.name} after the empty calls: {name}")
+
+
 KNOB_ENVS = [{"LAV_PILLAR_ZERO": "bin"}, {"LAV_PILLAR_REC": "48"}, {"LAV_PILLAR_WG_PER_CU": "1"}, {"LAV_PILLAR_ZERO": "bin", "LAV_PILLAR_WG_PER_CU": "1"}]
 
 
