@@ -11,15 +11,14 @@ import torch
 from torch import nn
 
 from . import ops
-from .lidar import _Engine
-from .planner_common import _hip_train, DecoderMixin, crop_feature, crop_feature_torch, picked_others, sample_others, select_others
+from .planner_common import PlannerBase, picked_others, sample_others, select_others
 from .resnet import resnet18
 
 # BEVPlanner.infer_batch's result: forward's six outputs, then the (sample, actor) index of every forecast (actor counts locs[:, 1:])
 BatchInference = collections.namedtuple("BatchInference", "other_locs other_cast other_cmds ego_plan ego_cast ego_cmds sample actor")
 
 
-class BEVPlanner(DecoderMixin, _Engine):
+class BEVPlanner(PlannerBase):
     def __init__(self, pixels_per_meter=2, crop_size=64, x_offset=0, y_offset=0.75, feature_x_jitter=1,
                  feature_angle_jitter=10, num_plan=10, k=16, num_out_feature=64, num_cmds=6, max_num_cars=5,
                  num_plan_iter=1, num_frame_stack=0):
@@ -38,41 +37,9 @@ class BEVPlanner(DecoderMixin, _Engine):
         self.cast_grus = nn.ModuleList([nn.GRU(512, 64, batch_first=True) for _ in range(num_cmds)])
         self.cast_mlps = nn.ModuleList([nn.Linear(64, 2) for _ in range(num_cmds)])
         self.cast_cmd_pred = nn.Sequential(nn.Linear(512, num_cmds), nn.Sigmoid())
-        self._drop()
-
-    def _drop(self):
-        super()._drop()
-        self._drop_dec()
-        object.__setattr__(self, "_offsets", None)
-
-    def _mark_stale(self):
-        """Parameters may have changed in place (train()/eval() toggle, load_state_dict): the conv engines re-pack themselves at
-        their next use; the stacked decoder weights and the cached offsets are plain copies, so they are dropped and rebuilt."""
-        super()._mark_stale()
-        self._drop_dec()
-        object.__setattr__(self, "_offsets", None)
-
-    def offsets(self):
-        """(offset_x, offset_y) as host floats, read from the parameters once (no device->host sync per frame;
-        keeps the forward HIP-graph capturable)."""
-        if getattr(self, "_offsets", None) is None:
-            object.__setattr__(self, "_offsets", (float(self.offset_x), float(self.offset_y)))
-        return self._offsets
 
     def _cast_modules(self):
         return self.cast_grus, self.cast_mlps
-
-    def crop_feature(self, features, rel_locs, rel_oris, pixels_per_meter=4, crop_size=96, map_index=None):
-        """map_index (int32, per crop): take crop i from features[map_index[i]] instead of features[i] - the training
-        forwards crop several vehicles out of each sample's map without materialising one copy of the map per vehicle."""
-        ox, oy = self.offsets()
-        if map_index is not None and features.is_cuda and (_hip_train("CROP") or not self.training):   # HIP forward + backward (autograd.Function)
-            return ops.crop_rotate_indexed(features, map_index, rel_locs, rel_oris, pixels_per_meter, crop_size, ox, oy)
-        if map_index is not None:
-            features = features[map_index.long()]
-        if self.training:   # autograd path (affine_grid + grid_sample)
-            return crop_feature_torch(features, rel_locs, rel_oris, pixels_per_meter, crop_size, ox, oy)
-        return crop_feature(features, rel_locs, rel_oris, pixels_per_meter, crop_size, ox, oy)
 
     @torch.no_grad()
     def infer(self, bev, nxps):

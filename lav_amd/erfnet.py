@@ -16,14 +16,14 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from .engine import Engine
 from .ops import Conv1dPair, Conv1dPairChain, ConvLayer, GroupedDeconv, infer_precision
 
 _USE_PAIRS = os.environ.get("LAV_ERFNET_PAIRS", "1") != "0"   # A/B switch: 0 = four lav_conv2d launches per block
 
 
 def _affine(bn, sl):
-    s = (bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps))
-    t = bn.bias.detach().double() - bn.running_mean.detach().double() * s
+    s, t = ops.bn_fold(bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps)
     return s[sl].float()[None, :, None, None].contiguous(), t[sl].float()[None, :, None, None].contiguous()
 
 
@@ -191,38 +191,29 @@ class Decoder(nn.Module):
         return self.output_conv(x)
 
 
-class ERFNet(nn.Module):
+class ERFNet(Engine):
     def __init__(self, num_classes):
         super().__init__()
         self.encoder = Encoder(num_classes)
         self.decoder = Decoder(num_classes)
-        object.__setattr__(self, "_eng", None)
 
-    def _drop(self):
-        object.__setattr__(self, "_eng", None)
-
-    def _apply(self, fn, *a, **k):
-        self._drop()
-        return super()._apply(fn, *a, **k)
-
-    def train(self, mode: bool = True):
-        self._drop()
-        return super().train(mode)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._drop()
-        return super()._load_from_state_dict(*a, **k)
+    _mark_stale = Engine._drop      # (the pair kernels' packed weights are plain copies without a refresh(): rebuilt at the next use)
 
     def _engine(self, device, input_affine=None, softmax=False):
-        key = (device, input_affine, softmax, infer_precision())   # (the runs of blocks are built for the precision in force: fp16 pieces under LAV_CONV_F16X3)
-        if self._eng is None or self._eng[0] != key:
+        def build():
             stages = [self.encoder.initial_block.engine(device, input_affine)]
             stages += [m.engine(device) for m in self.encoder.layers]
             stages += [m.engine(device) for m in self.decoder.layers]
             stages = _chain_blocks(stages)
             stages.append(GroupedDeconv([self.decoder.output_conv], softmax=softmax, device=device))   # 16 -> classes, k2 s2: memory bound
-            object.__setattr__(self, "_eng", (key, stages))
-        return self._eng[1]
+            return stages
+        # (the runs of blocks are built for the precision in force: fp16 pieces under LAV_CONV_F16X3)
+        return self._engine_for(device, (input_affine, softmax, infer_precision()), build)
+
+    def chains(self, precision):
+        """The persistent runs (Conv1dPairChain) of the engines built for `precision` so far."""
+        return [s.chain for key, stages in (self.__dict__.get("_eng") or {}).items() if isinstance(key, tuple) and key[2] == precision
+                for s in stages if getattr(s, "chain", None) is not None]
 
     def forward(self, x, input_affine=None, softmax=False):
         """input_affine=(s, t): x is the raw input and the network behaves as on s*x + t (folded into the first block in

@@ -14,77 +14,11 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import ops
+from .engine import Engine, _bn_tuple
 from .ops import Amax, ConvLayer, ConvRun, ConvTileRun, GroupedDeconv, PointwiseUpconv
 from .point_pillar import PointPillarNet
 
 _NORM = dict(eps=1e-3, momentum=0.01)
-
-
-def _refreshable(obj):
-    """Every layer object with a refresh() inside an engine (nested dicts / lists / tuples)."""
-    if isinstance(obj, dict):
-        for v in obj.values():
-            yield from _refreshable(v)
-    elif isinstance(obj, (list, tuple)):
-        for v in obj:
-            yield from _refreshable(v)
-    elif hasattr(obj, "refresh"):
-        yield obj
-
-
-class _Engine(nn.Module):
-    """Mixin: cache of packed ConvLayers.  When the parameters may have changed IN PLACE (a train()/eval() toggle around optimiser
-    steps, load_state_dict) the cached engine is marked stale and re-packed on the device from the live parameters at its next use
-    (ConvLayer.refresh: one gather launch per layer - the trainer's per-step log inference, lav_final_v2.py:228-236, used to rebuild
-    ~45 layers on the host per step); when the tensors themselves may have been replaced (_apply: .to() / .float()) it is dropped."""
-
-    def _drop(self):
-        object.__setattr__(self, "_eng", None)
-        object.__setattr__(self, "_stale", False)
-
-    def _mark_stale(self):
-        if self.__dict__.get("_eng") is not None:
-            object.__setattr__(self, "_stale", True)
-
-    def _tensor_ids(self):
-        return tuple(id(t) for t in self.parameters()) + tuple(id(t) for t in self.buffers())
-
-    def _fresh(self, device):
-        """The cached engine for `device`, brought up to date; None when there is none (or when a parameter OBJECT was replaced -
-        load_state_dict(assign=True), module.weight = nn.Parameter(...) - since the engine was packed: the layers re-pack from
-        the tensors they were built from, so such an engine is dropped and rebuilt from the module)."""
-        eng = self.__dict__.get("_eng")
-        if eng is None or eng.get("device") != device:
-            return None
-        if self.__dict__.get("_stale"):
-            if eng["tensor_ids"] != self._tensor_ids():
-                self._drop()
-                return None
-            for layer in _refreshable(eng):
-                layer.refresh()
-            object.__setattr__(self, "_stale", False)
-        return eng
-
-    def _apply(self, fn, *a, **k):
-        self._drop()
-        return super()._apply(fn, *a, **k)
-
-    def train(self, mode: bool = True):
-        if mode != self.training:     # packed engines only go stale when the mode really changes (or weights do: _apply / load)
-            self._mark_stale()
-        return super().train(mode)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._mark_stale()
-        return super()._load_from_state_dict(*a, **k)
-
-    def _need_eval(self):
-        if self.training:
-            raise NotImplementedError(f"{type(self).__name__}: the fused HIP path is eval-only; train mode runs forward_train")
-
-
-def _bn_tuple(bn: nn.BatchNorm2d):
-    return (bn.running_mean, bn.running_var, bn.weight, bn.bias)
 
 
 def _stage(cin, cout, n):
@@ -101,7 +35,7 @@ def _up(cin, cout, k, s, p=0, op=0):
                          nn.BatchNorm2d(cout, **_NORM))
 
 
-class ConvBackbone(_Engine):
+class ConvBackbone(Engine):
     def __init__(self, num_feature=64, norm_cfg=None):
         super().__init__()
         f = num_feature
@@ -112,16 +46,14 @@ class ConvBackbone(_Engine):
         self.upconv2 = _up(2 * f, 2 * f, 4, 2, 1)
         self.upconv3 = _up(2 * f, 2 * f, 4, 4, 1, 2)
         self.out_channels = 6 * f
-        self._drop()
 
     def _engine(self, device):
         """The packed layers for the calling thread's inference precision (ops.infer_precision: the frame pipelines ask for
         LAV_CONV_F16X3, a trainer's log inference gets the default) - one engine per precision, cached side by side."""
         prec = ops.infer_precision()
-        eng = self._fresh(device) or dict(device=device)
-        key = ("backbone", prec)
-        if key in eng:
-            return eng[key]
+        return self._engine_for(device, ("backbone", prec), lambda: self._build(device, prec))
+
+    def _build(self, device, prec):
         def stage(seq):
             out = []
             for j in range(0, len(seq), 3):
@@ -142,20 +74,18 @@ class ConvBackbone(_Engine):
                                      output_padding=ct.output_padding[0], bn=_bn_tuple(bn), bn_eps=bn.eps, relu_pre=True,
                                      out_c_total=self.out_channels, out_c_offset=off, precision=prec, device=device))
             off += ct.weight.shape[1]
-        eng[key] = dict(s1=stage(self.conv1), s2=stage(self.conv2), s3=stage(self.conv3), ups=ups, amax={}, f16=prec == _lib.CONV_F16X3)
+        e = dict(s1=stage(self.conv1), s2=stage(self.conv2), s3=stage(self.conv3), ups=ups, amax={}, f16=prec == _lib.CONV_F16X3)
         # layers 2..n of a stage share one geometry: one persistent launch each where LAV_BEV_RUN asks for it (ops.ConvRun; the choice
         # sits here, so the eager and the graphed pipeline run the same kernels)
         want = ops.bev_run_stages() if prec == _lib.CONV_F16X3 else ()
-        eng[key]["runs"] = [ConvRun(eng[key][s][1:]) if s in want and len(eng[key][s]) > 2 else None for s in ("s1", "s2", "s3")]
+        e["runs"] = [ConvRun(e[s][1:]) if s in want and len(e[s]) > 2 else None for s in ("s1", "s2", "s3")]
         # a 64-channel stage of at most 3 such layers that is not a persistent run (s1): one launch on halo tiles (ops.ConvTileRun)
         if prec == _lib.CONV_F16X3 and ops.bev_tile_enabled():
             for i, s in enumerate(("s1", "s2", "s3")):
-                st = eng[key][s]
-                if eng[key]["runs"][i] is None and 2 < len(st) <= 4 and st[1].cin == 64:
-                    eng[key]["runs"][i] = ConvTileRun(st[1:])
-        eng["tensor_ids"] = self._tensor_ids()   # recorded where the engine is built, not at its first use
-        object.__setattr__(self, "_eng", eng)
-        return eng[key]
+                st = e[s]
+                if e["runs"][i] is None and 2 < len(st) <= 4 and st[1].cin == 64:
+                    e["runs"][i] = ConvTileRun(st[1:])
+        return e
 
     def forward_train(self, x):
         """Train mode (autograd, BatchNorm on batch statistics): the nn modules themselves (lidar.py:110-143)."""
@@ -215,7 +145,7 @@ class ConvBackbone(_Engine):
         return ops.tag_amax(out, am_out)
 
 
-class Head(_Engine):
+class Head(Engine):
     def __init__(self, num_input, num_output, num_hidden=64, norm_cfg=None, output_activation=nn.Identity()):
         super().__init__()
         self.net = nn.Sequential(
@@ -225,7 +155,6 @@ class Head(_Engine):
             nn.ConvTranspose2d(num_hidden, num_output, 3, 2, 1, 1),
         )
         self.output_activation = output_activation
-        self._drop()
 
     @property
     def _sigmoid(self):
@@ -242,17 +171,14 @@ class Head(_Engine):
         if self.training:
             from .train.hipnn import bn_act
             return self.output_activation(self.net[3](bn_act(self.net[2], self.net[0](x), relu_pre=True)))
-        if self._fresh(x.device) is None:
-            conv, bn = self.net[0], self.net[2]
-            eng = dict(device=x.device,
-                       conv=ConvLayer(conv.weight, padding=1, bn=_bn_tuple(bn), bn_eps=bn.eps, relu_pre=True, device=x.device),
-                       deconv=self.deconv_layer(x.device))
-            eng["tensor_ids"] = self._tensor_ids()   # recorded where the engine is built, not at its first use
-            object.__setattr__(self, "_eng", eng)
-        return self._eng["deconv"](self._eng["conv"](x))
+        conv, bn = self.net[0], self.net[2]
+        e = self._engine_for(x.device, "net", lambda: dict(
+            conv=ConvLayer(conv.weight, padding=1, bn=_bn_tuple(bn), bn_eps=bn.eps, relu_pre=True, device=x.device),
+            deconv=self.deconv_layer(x.device)))
+        return e["deconv"](e["conv"](x))
 
 
-class LiDARModel(_Engine):
+class LiDARModel(Engine):
     def __init__(self, num_input=9, num_features=(32, 32), backbone="swin", min_x=-10, max_x=70, min_y=-40, max_y=40,
                  pixels_per_meter=4):
         super().__init__()
@@ -266,7 +192,6 @@ class LiDARModel(_Engine):
         self.box_head = Head(6 * nf, 2)
         self.ori_head = Head(6 * nf, 2)
         self.seg_head = Head(6 * nf, 3, output_activation=torch.sigmoid)
-        self._drop()
 
     def _head_engine(self, names, device):
         """Fused engine of a subset of the heads: ONE convolution 384 -> 64*len(names) (the 39 MB feature map is read once)
@@ -275,10 +200,8 @@ class LiDARModel(_Engine):
         prec = ops.infer_precision()
         if prec == 0 and getattr(self, "heads_precision", 0):   # (round 5's per-model knob, still honoured when somebody sets it)
             prec = self.heads_precision
-        eng = self._fresh(device) or dict(device=device)
-        names = (names, prec)
-        if names not in eng:
-            hs = [getattr(self, n) for n in names[0]]
+        def build():
+            hs = [getattr(self, n) for n in names]
             for h in hs:
                 if not (h._sigmoid or isinstance(h.output_activation, nn.Identity)):
                     raise RuntimeError("Head.output_activation must be identity or sigmoid for the fused epilogue")
@@ -289,13 +212,11 @@ class LiDARModel(_Engine):
             bn = lambda: tuple(torch.cat([getattr(h.net[2], n).detach() for h in hs]) for n in ("running_mean", "running_var", "weight", "bias"))
             cts = [h.net[3] for h in hs]
             outs = [ct.weight.shape[1] for ct in cts]
-            eng[names] = dict(outs=outs,
-                              conv=ConvLayer(w, padding=1, bn=bn, bn_eps=hs[0].net[2].eps, relu_pre=True, device=device,
-                                             precision=prec),   # (the frame pipelines ask for LAV_CONV_F16X3)
-                              deconv=GroupedDeconv(cts, sigmoid_from=sum(outs[:-1]) if sig[-1] else -1, device=device))
-            eng["tensor_ids"] = self._tensor_ids()   # recorded where the engine is built, not at its first use
-            object.__setattr__(self, "_eng", eng)
-        return self._eng[names]
+            return dict(outs=outs,
+                        conv=ConvLayer(w, padding=1, bn=bn, bn_eps=hs[0].net[2].eps, relu_pre=True, device=device,
+                                       precision=prec),   # (the frame pipelines ask for LAV_CONV_F16X3)
+                        deconv=GroupedDeconv(cts, sigmoid_from=sum(outs[:-1]) if sig[-1] else -1, device=device))
+        return self._engine_for(device, (names, prec), build)
 
     ALL_HEADS = ("center_head", "box_head", "ori_head", "seg_head")
 

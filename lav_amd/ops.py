@@ -896,6 +896,13 @@ def amax_key(x):
     return tuple(x.shape), torch.cuda.current_stream(x.device).cuda_stream
 
 
+def bn_fold(mean, var, gamma, beta, eps):
+    """Eval-mode BatchNorm as y = x * scale + shift: (scale, shift) in float64, on the device the statistics live on."""
+    mean, var, gamma, beta = (t.detach().double() for t in (mean, var, gamma, beta))
+    scale = gamma / torch.sqrt(var + eps)
+    return scale, beta - mean * scale
+
+
 class ConvLayer:
     """One fused convolution of the C ABI: packed weights + epilogue vectors resident in HBM.
 
@@ -935,8 +942,7 @@ class ConvLayer:
                          int(padding[1]), int(dilation[0]), int(dilation[1]), int(bool(transposed)),
                          int(output_padding), self.out_c_total, out_c_offset, int(relu_pre), int(relu_post),
                          int(sigmoid), int(target_cus), float(pad_value), int(precision))
-        probe = Conv.from_buffer_copy(self.desc)
-        probe.h, probe.w = 64, 64
+        probe = self._desc()
         nfl = lib.lav_conv_packed_weight_floats(C.byref(probe))
         if nfl == 0:
             raise RuntimeError("lav_conv_packed_weight_floats: " + lib.lav_last_error().decode())
@@ -947,11 +953,14 @@ class ConvLayer:
         self.bias = None if bias is None else bias.detach().to(dev, torch.float32).contiguous()
         self._ws_bytes = {}
         self.scale = self.shift = None
-        if bn is not None:  # eval-mode BatchNorm as y = x*scale + shift, folded in float64
-            mean, var, gamma, beta = [t.detach().to("cpu", torch.float64) for t in bn]
-            scale = gamma / torch.sqrt(var + bn_eps)
-            self.scale = scale.to(torch.float32).to(dev)
-            self.shift = (beta - mean * scale).to(torch.float32).to(dev)
+        if bn is not None:  # eval-mode BatchNorm as y = x*scale + shift, folded in float64 on the host
+            self.scale, self.shift = (v.to(torch.float32).to(dev) for v in bn_fold(*[t.detach().cpu() for t in bn], bn_eps))
+
+    def _desc(self, B=1, h=64, w=64):
+        """A copy of the descriptor for a (B, ., h, w) input (the default: a probe for the calls that only read the layer's geometry)."""
+        d = Conv.from_buffer_copy(self.desc)
+        d.batch, d.h, d.w = B, h, w
+        return d
 
     def refresh(self):
         """Re-pack the weights and re-fold the epilogue vectors from the CURRENT values of the tensors this layer was built from
@@ -963,8 +972,7 @@ class ConvLayer:
         get = lambda v: v() if callable(v) else v
         w, bias, bn = get(src["weight"]), get(src["bias"]), get(src["bn"])
         dev = self.w.device
-        probe = Conv.from_buffer_copy(self.desc)
-        probe.h, probe.w = 64, 64
+        probe = self._desc()
         if dev.type == "cuda" and w.device == dev and self._map is not False:
             if self._map is None:
                 n = lib.lav_conv_pack_map_ints(C.byref(probe))
@@ -993,10 +1001,9 @@ class ConvLayer:
                 check(lib.lav_bn_fold(_ptr(mean), _ptr(var), _ptr(gamma), _ptr(beta), src["bn_eps"], mean.numel(), _ptr(self.scale),
                                       _ptr(self.shift), _stream()), "lav_bn_fold")
             else:
-                mean, var, gamma, beta = [t.detach().to("cpu", torch.float64) for t in bn]
-                scale = gamma / torch.sqrt(var + src["bn_eps"])
+                scale, shift = bn_fold(*[t.detach().cpu() for t in bn], src["bn_eps"])
                 self.scale.copy_(scale.to(torch.float32))
-                self.shift.copy_((beta - mean * scale).to(torch.float32))
+                self.shift.copy_(shift.to(torch.float32))
 
     @classmethod
     def from_module(cls, conv, bn=None, bn_slice=None, **kw):
@@ -1015,10 +1022,8 @@ class ConvLayer:
                    device=kw.pop("device", conv.weight.device), **kw)
 
     def out_hw(self, h: int, w: int):
-        d = Conv.from_buffer_copy(self.desc)
-        d.h, d.w = h, w
         oh, ow = C.c_int(), C.c_int()
-        check(_lib.load().lav_conv_out_hw(C.byref(d), C.byref(oh), C.byref(ow)), "lav_conv_out_hw")
+        check(_lib.load().lav_conv_out_hw(C.byref(self._desc(1, h, w)), C.byref(oh), C.byref(ow)), "lav_conv_out_hw")
         return oh.value, ow.value
 
     def uses_amax(self, B: int, h: int, w: int) -> bool:
@@ -1028,10 +1033,8 @@ class ConvLayer:
         if v is None:
             v = False
             if self.desc.precision == _lib.CONV_F16X3:
-                d = Conv.from_buffer_copy(self.desc)
-                d.batch, d.h, d.w = B, h, w
                 info = (C.c_int * 9)()
-                v = _lib.load().lav_conv_tile_info(C.byref(d), info) == 0 and info[0] == -1 and info[7] >= 200
+                v = _lib.load().lav_conv_tile_info(C.byref(self._desc(B, h, w)), info) == 0 and info[0] == -1 and info[7] >= 200
             self._ws_bytes[key] = v
         return v
 
@@ -1042,8 +1045,7 @@ class ConvLayer:
         B, ct, h, w = x.shape
         if ct != self.in_c_total:
             raise RuntimeError(f"conv input has {ct} channels, layer expects {self.in_c_total}")
-        d = Conv.from_buffer_copy(self.desc)
-        d.batch, d.h, d.w = B, h, w
+        d = self._desc(B, h, w)
         oh, ow = self.out_hw(h, w)
         if out is None:
             out = torch.empty((B, self.out_c_total, oh, ow), dtype=torch.float32, device=x.device)
@@ -1059,11 +1061,6 @@ class ConvLayer:
         if nbytes is None:
             nbytes = self._ws_bytes[key] = lib.lav_conv_workspace_bytes(C.byref(d))
         ws = _workspace("conv", nbytes, x.device) if nbytes else None
-        if amax_in is None and amax_out is None:
-            check(lib.lav_conv2d(C.byref(d), _ptr(x), _ptr(self.w), _ptr(self.bias), _ptr(self.scale), _ptr(self.shift),
-                                 _ptr(residual), _ptr(out), _ptr(ws), ws.numel() if ws is not None else 0, _stream()),
-                  "lav_conv2d")
-            return out
         a_in = amax_in.buf if amax_in is not None and amax_in.count > 0 else None
         a_out = None
         if amax_out is not None:
@@ -1077,7 +1074,7 @@ class ConvLayer:
         check(lib.lav_conv2d_amax(C.byref(d), _ptr(x), _ptr(self.w), _ptr(self.bias), _ptr(self.scale), _ptr(self.shift),
                                   _ptr(residual), _ptr(out), _ptr(ws), ws.numel() if ws is not None else 0,
                                   _ptr(a_in), amax_in.count if a_in is not None else 0, _ptr(a_out), _stream()),
-              "lav_conv2d_amax")
+              "lav_conv2d" if amax_in is None and amax_out is None else "lav_conv2d_amax")   # (lav_conv2d is this call with no maxima)
         return out
 
 
@@ -1173,8 +1170,7 @@ class PointwiseUpconv:
         else:             # [ci][co][ky][kx] -> [ky][32-cout tile][kx][ci][32]
             p = w.reshape(self.cin, self.cout // 32, 32, 4, 4).permute(3, 1, 4, 0, 2)
         p = p.contiguous().reshape(-1).to(self.device)
-        scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-        shift = bn.bias.detach().double() - bn.running_mean.detach().double() * scale
+        scale, shift = bn_fold(bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps)
         if self.w is None:
             self.w, self.scale, self.shift = p, scale.float().to(self.device).contiguous(), shift.float().to(self.device).contiguous()
         else:     # in place: HIP graphs hold these addresses
@@ -1232,9 +1228,7 @@ class Conv1dPair:
         self.bb = conv_b.bias.detach().to(dev, torch.float32).contiguous()
         self.scale = self.shift = None
         if bn is not None:
-            s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-            self.scale = s.float().to(dev)
-            self.shift = (bn.bias.detach().double() - bn.running_mean.detach().double() * s).float().to(dev)
+            self.scale, self.shift = (v.float().to(dev) for v in bn_fold(bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps))
         self.relu_post = bool(relu_post)
 
     def supported(self, x: torch.Tensor) -> bool:
@@ -1384,9 +1378,7 @@ class ConvRun:
                     and l.bias is None and l.scale is not None and d.relu_pre and not d.relu_post and not d.sigmoid and d.pad_value == 0.0):
                 raise RuntimeError("ConvRun: layers must be identical conv3x3 / ReLU / BatchNorm layers packed for LAV_CONV_F16X3")
         self.layers, self.ch = layers, l0.cin
-        probe = Conv.from_buffer_copy(l0.desc)
-        probe.h, probe.w = 64, 64
-        self._woff = int(lib.lav_conv_f16_weights_offset(C.byref(probe)))
+        self._woff = int(lib.lav_conv_f16_weights_offset(C.byref(l0._desc())))
         if self._woff < 0 or len(layers) > 8:
             raise RuntimeError("ConvRun: at most 8 layers with fp16 packed weights")
         n = len(layers)

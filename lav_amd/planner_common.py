@@ -5,6 +5,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from .engine import Engine
 
 
 def _hip_train(what: str) -> bool:
@@ -122,9 +123,10 @@ def sample_others(self, ego_locs, locs, oris, typs):
     return picked_others(ego_locs, locs, oris, typs, jitter), locs.size(1) - 1
 
 
-class DecoderMixin:
-    """cast()/plan() on the HIP GRU kernels.  Expects self.num_plan, self.num_plan_iter, self.num_cmds,
-    self.plan_gru, self.plan_mlp and a _cast_modules() -> (grus, mlps) hook."""
+class PlannerBase(Engine):
+    """What UniPlanner and BEVPlanner share: the conv engines' cache (Engine), cast()/plan() on the HIP GRU kernels, the cached crop
+    offsets and the rotated crop.  Expects self.num_plan, self.num_plan_iter, self.num_cmds, self.plan_gru, self.plan_mlp,
+    self.offset_x / offset_y and a _cast_modules() -> (grus, mlps) hook."""
 
     def _dec(self, device):
         d = getattr(self, "_dec_cache", None)
@@ -134,8 +136,39 @@ class DecoderMixin:
             object.__setattr__(self, "_dec_cache", d)
         return d
 
-    def _drop_dec(self):
+    def _drop(self):
+        super()._drop()
         object.__setattr__(self, "_dec_cache", None)
+        object.__setattr__(self, "_offsets", None)
+
+    def _mark_stale(self):
+        """Parameters may have changed in place (train()/eval() toggle, load_state_dict): the conv engines re-pack themselves at
+        their next use; the stacked decoder weights and the cached offsets are plain copies, so they are dropped and rebuilt."""
+        super()._mark_stale()
+        object.__setattr__(self, "_dec_cache", None)
+        object.__setattr__(self, "_offsets", None)
+
+    def offsets(self):
+        """(offset_x, offset_y) as host floats, read from the parameters once (no device->host sync per frame;
+        keeps the forward HIP-graph capturable)."""
+        if getattr(self, "_offsets", None) is None:
+            object.__setattr__(self, "_offsets", (float(self.offset_x), float(self.offset_y)))
+        return self._offsets
+
+    def crop_feature(self, features, rel_locs, rel_oris, pixels_per_meter=4, crop_size=96, map_index=None, amax=None):
+        """map_index (int32, per crop): take crop i from features[map_index[i]] instead of features[i] - the training
+        forwards crop several vehicles out of each sample's map without materialising one copy of the map per vehicle.
+        amax (eval, no map_index): the ops.Amax of the feature map - a bilinear crop never exceeds the map's largest magnitude, so
+        the crops carry it on to the stem convolution (LAV_CONV_F16X3's scale, lav_conv2d_amax)."""
+        ox, oy = self.offsets()
+        if map_index is not None and features.is_cuda and (_hip_train("CROP") or not self.training):   # HIP forward + backward (autograd.Function)
+            return ops.crop_rotate_indexed(features, map_index, rel_locs, rel_oris, pixels_per_meter, crop_size, ox, oy)
+        if map_index is not None:
+            features = features[map_index.long()]
+        if self.training:   # autograd path (affine_grid + grid_sample)
+            return crop_feature_torch(features, rel_locs, rel_oris, pixels_per_meter, crop_size, ox, oy)
+        crops = crop_feature(features, rel_locs, rel_oris, pixels_per_meter, crop_size, ox, oy)
+        return ops.tag_amax(crops, amax) if map_index is None else crops
 
     def cast(self, embd, mode="ego"):
         """(B,512) -> (B, num_cmds, num_plan, 2).  Both modes use the *_ego GRUs, as the reference does

@@ -14,9 +14,10 @@ import torch
 from torch import nn
 
 from . import ops
+from .engine import Engine
 
 
-class DynamicPointNet(nn.Module):
+class DynamicPointNet(Engine):
     """Parameter holder for `net` = [Linear, BatchNorm1d, ReLU] x len(num_features) (point_pillar.py:12-26)."""
 
     def __init__(self, num_input: int = 9, num_features: Sequence[int] = (32, 32)):
@@ -27,27 +28,14 @@ class DynamicPointNet(nn.Module):
             blocks += [nn.Linear(width, nf), nn.BatchNorm1d(nf), nn.ReLU(inplace=True)]
             width = nf
         self.net = nn.Sequential(*blocks)
-        self._folded = None
 
-    def _invalidate(self):
-        self._folded = None
-
-    def _apply(self, fn, *a, **k):
-        self._invalidate()
-        return super()._apply(fn, *a, **k)
-
-    def train(self, mode: bool = True):
-        self._invalidate()
-        return super().train(mode)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._invalidate()
-        return super()._load_from_state_dict(*a, **k)
+    _mark_stale = Engine._drop      # (the folded weights are plain copies: rebuilt at the next use)
 
     def folded(self, device):
         """(w1 [K][C], b1 [C], w2 [C][C], b2 [C]) float32 on `device`, BatchNorm (running stats) folded in float64."""
-        if self._folded is not None and self._folded[0].device == device:
-            return self._folded
+        return self._engine_for(device, "folded", lambda: self._fold(device))
+
+    def _fold(self, device):
         lins = [m for m in self.net if isinstance(m, nn.Linear)]
         bns = [m for m in self.net if isinstance(m, nn.BatchNorm1d)]
         if len(lins) != 2:
@@ -58,8 +46,7 @@ class DynamicPointNet(nn.Module):
             w = lin.weight.detach().double() * s[:, None]                       # [out][in]
             b = (lin.bias.detach().double() - bn.running_mean.detach().double()) * s + bn.bias.detach().double()
             out += [w.t().contiguous().float().to(device), b.float().to(device)]  # kernel wants [in][out]
-        self._folded = tuple(out)
-        return self._folded
+        return tuple(out)
 
 
 class PointPillarNet(nn.Module):

@@ -9,7 +9,7 @@ from torch import nn
 import torch.nn.functional as F
 
 from . import _lib
-from .lidar import _Engine, _bn_tuple
+from .engine import Engine, _bn_tuple
 from .ops import Amax, ConvLayer
 
 
@@ -29,7 +29,7 @@ class BasicBlock(nn.Module):
         self.stride = stride
 
 
-class ResNet(_Engine):
+class ResNet(Engine):
     def __init__(self, layers=(2, 2, 2, 2), num_channels=3, num_classes=1000):
         super().__init__()
         self.conv1 = nn.Conv2d(num_channels, 64, 7, 2, 3, bias=False)
@@ -45,28 +45,23 @@ class ResNet(_Engine):
             setattr(self, f"layer{i + 1}", nn.Sequential(*blocks))
         self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
         self.fc = nn.Linear(512, num_classes)  # present in the reference's checkpoints, unused by forward
-        self._drop()
 
     def _engine(self, device):
         """The packed layers for the calling thread's inference precision (ops.infer_precision), one engine per precision."""
         from . import ops
         prec = ops.infer_precision()
-        eng = self._fresh(device) or dict(device=device)
-        key = ("trunk", prec)
-        if key in eng:
-            return eng[key]
         def cl(conv, bn, **kw):
             return ConvLayer(conv.weight, stride=conv.stride[0], padding=conv.padding, bn=_bn_tuple(bn), bn_eps=bn.eps,
                              device=device, target_cus=getattr(self, "target_cus", 0), precision=prec, **kw)
-        blocks = []
-        for i in range(1, 5):
-            for blk in getattr(self, f"layer{i}"):
-                blocks.append(dict(c1=cl(blk.conv1, blk.bn1, relu_post=True), c2=cl(blk.conv2, blk.bn2, relu_post=True),
-                                   down=None if blk.downsample is None else cl(blk.downsample[0], blk.downsample[1])))
-        eng[key] = dict(stem=cl(self.conv1, self.bn1, relu_post=True), blocks=blocks, amax={}, f16=prec == _lib.CONV_F16X3)
-        eng["tensor_ids"] = self._tensor_ids()   # (recorded where the engine is built: lidar.py:_Engine._fresh)
-        object.__setattr__(self, "_eng", eng)
-        return eng[key]
+
+        def build():
+            blocks = []
+            for i in range(1, 5):
+                for blk in getattr(self, f"layer{i}"):
+                    blocks.append(dict(c1=cl(blk.conv1, blk.bn1, relu_post=True), c2=cl(blk.conv2, blk.bn2, relu_post=True),
+                                       down=None if blk.downsample is None else cl(blk.downsample[0], blk.downsample[1])))
+            return dict(stem=cl(self.conv1, self.bn1, relu_post=True), blocks=blocks, amax={}, f16=prec == _lib.CONV_F16X3)
+        return self._engine_for(device, ("trunk", prec), build)
 
     def forward_train(self, x):
         """Train mode (autograd, BatchNorm on batch statistics): plain torch ops over the same modules."""

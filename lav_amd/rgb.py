@@ -11,6 +11,7 @@ import torch
 from torch import nn
 import torch.nn.functional as F
 
+from .engine import Engine
 from .erfnet import ERFNet
 from . import ops
 from . import resnet as _hip_resnet
@@ -146,7 +147,9 @@ class _ResNet18(_hip_resnet.ResNet):
         return x
 
 
-class RGBBrakePredictionModel(nn.Module):
+class RGBBrakePredictionModel(Engine):
+    _mark_stale = Engine._drop      # (its engine is the folded input normalisation, a plain copy: rebuilt at the next use)
+
     def __init__(self, seg_channels, pretrained=False):
         super().__init__()
         self.conv_backbone = _ResNet18(3)
@@ -161,12 +164,10 @@ class RGBBrakePredictionModel(nn.Module):
         called by the frame pipeline when it runs the two images' trunks as separate graphs."""
         if not self.training and rgb.is_cuda and rgb.dtype == torch.float32 and rgb.shape[2] * rgb.shape[3] % 4 == 0:
             # normalize(rgb / 255) = rgb * (1 / (255 std)) - mean / std: one launch per image instead of three
-            st = self.__dict__.get("_norm_affine")      # (constants of the module: computed once per device, not per frame)
-            if st is None or st[0].device != rgb.device:
+            def affine():      # (computed once per device, not per frame; a plain copy of the two parameters: _mark_stale)
                 std, mean = self.normalize.std.detach().double(), self.normalize.mean.detach().double()
-                st = ((1.0 / (255.0 * std)).float().reshape(-1).to(rgb.device), (-mean / std).float().reshape(-1).to(rgb.device))
-                object.__setattr__(self, "_norm_affine", st)
-            s_, t_ = st
+                return (1.0 / (255.0 * std)).float().reshape(-1).to(rgb.device), (-mean / std).float().reshape(-1).to(rgb.device)
+            s_, t_ = self._engine_for(rgb.device, "norm_affine", affine)
             return self.conv_backbone(ops.channel_affine(rgb, s_, t_))
         return self.conv_backbone(self.normalize(rgb / 255.))
 

@@ -209,15 +209,15 @@ def trunk_arithmetic(resnet, code: int) -> str:
     return "/".join(sorted(names))
 
 
-def erfnet_arithmetic(erfnet, shape) -> str:
-    """What the ERFNet's runs of blocks ran at on a call of `shape` (B, 3, H, W), read off the engine that call built: f16x3 only if
+def erfnet_arithmetic(erfnet, code: int, shape) -> str:
+    """What the ERFNet's runs of blocks ran at on a call of `shape` (B, 3, H, W) under ops.precision(code), read off the engine that call built: f16x3 only if
     every persistent run is the fp16 one AND takes the shape (else the blocks fall back to their own bf16x6 launches); f32 under
     LAV_CONV_PRECISION=f32, whatever ops.precision says."""
     if _env_f32():
         return "f32"
     B, _, H, W = shape
     device = next(erfnet.parameters()).device
-    chains = [s.chain for s in erfnet._eng[1] if getattr(s, "chain", None) is not None]
+    chains = erfnet.chains(int(code))
     stride = {16: 2, 64: 4, 128: 8}
     for c in chains:
         ch = c.pairs[0].ch
@@ -256,7 +256,7 @@ class SegEvaluator(EvaluatorBase):
             part = x[j:j + self.images_per_call]
             with ops.precision(self.code):
                 logits = self.model(part)
-            self.in_force.add(erfnet_arithmetic(self.model.erfnet, part.shape))
+            self.in_force.add(erfnet_arithmetic(self.model.erfnet, self.code, part.shape))
             self._add("eval_seg", eval_seg_numpy, "seg", logits, labels[j:j + self.images_per_call], 1)
         self.images += x.shape[0]
 

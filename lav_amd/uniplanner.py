@@ -9,12 +9,11 @@ import torch
 from torch import nn
 
 from . import ops
-from .lidar import _Engine
-from .planner_common import _hip_train, DecoderMixin, crop_feature, crop_feature_torch, sample_others, transform_points
+from .planner_common import PlannerBase, sample_others, transform_points
 from .resnet import resnet18
 
 
-class UniPlanner(DecoderMixin, _Engine):
+class UniPlanner(PlannerBase):
     def __init__(self, bev_planner, pixels_per_meter=2, crop_size=64, x_offset=0, y_offset=0.75, feature_x_jitter=1,
                  feature_angle_jitter=10, num_plan=10, k=16, num_input_feature=96, num_out_feature=64, num_cmds=6,
                  max_num_cars=4, num_plan_iter=1):
@@ -38,26 +37,6 @@ class UniPlanner(DecoderMixin, _Engine):
         self.cast_grus_other = nn.ModuleList([nn.GRU(512, 64, batch_first=True) for _ in range(num_cmds)])
         self.cast_mlps_other = nn.ModuleList([nn.Linear(64, 2) for _ in range(num_cmds)])
         self.cast_cmd_pred = nn.Sequential(nn.Linear(512, num_cmds), nn.Sigmoid())
-        self._drop()
-
-    def _drop(self):
-        super()._drop()
-        self._drop_dec()
-        object.__setattr__(self, "_offsets", None)
-
-    def _mark_stale(self):
-        """Parameters may have changed in place (train()/eval() toggle, load_state_dict): the conv engines re-pack themselves at
-        their next use; the stacked decoder weights and the cached offsets are plain copies, so they are dropped and rebuilt."""
-        super()._mark_stale()
-        self._drop_dec()
-        object.__setattr__(self, "_offsets", None)
-
-    def offsets(self):
-        """(offset_x, offset_y) as host floats, read from the parameters once (no device->host sync per frame;
-        keeps the forward HIP-graph capturable)."""
-        if getattr(self, "_offsets", None) is None:
-            object.__setattr__(self, "_offsets", (float(self.offset_x), float(self.offset_y)))
-        return self._offsets
 
     def train(self, mode: bool = True):
         """The privileged teacher rides along as a submodule but is frozen: it stays in eval mode (the reference re-applies
@@ -74,24 +53,6 @@ class UniPlanner(DecoderMixin, _Engine):
 
     def _cast_modules(self):
         return self.cast_grus_ego, self.cast_mlps_ego
-
-    def crop_feature(self, features, rel_locs, rel_oris, pixels_per_meter=4, crop_size=96, map_index=None, amax=None):
-        """map_index (int32, per crop): take crop i from features[map_index[i]] instead of features[i] - the training
-        forwards crop several vehicles out of each sample's map without materialising one copy of the map per vehicle.
-        amax (eval): the ops.Amax of the feature map - a bilinear crop never exceeds the map's largest magnitude, so the crops carry
-        it on to the stem convolution (LAV_CONV_F16X3's scale, lav_conv2d_amax)."""
-        if amax is not None and not self.training and map_index is None:
-            ox, oy = self.offsets()
-            crops = crop_feature(features, rel_locs, rel_oris, pixels_per_meter, crop_size, ox, oy)
-            return ops.tag_amax(crops, amax)
-        ox, oy = self.offsets()
-        if map_index is not None and features.is_cuda and (_hip_train("CROP") or not self.training):   # HIP forward + backward (autograd.Function)
-            return ops.crop_rotate_indexed(features, map_index, rel_locs, rel_oris, pixels_per_meter, crop_size, ox, oy)
-        if map_index is not None:
-            features = features[map_index.long()]
-        if self.training:   # autograd path (affine_grid + grid_sample)
-            return crop_feature_torch(features, rel_locs, rel_oris, pixels_per_meter, crop_size, ox, oy)
-        return crop_feature(features, rel_locs, rel_oris, pixels_per_meter, crop_size, ox, oy)
 
     def embed_cast(self, crops, oris=None, locs=None, want_cmds=False):
         """Eval-mode tail of both branches in two steps instead of ~17 launches: the ResNet-18 trunk on the crops, then ONE

@@ -236,6 +236,56 @@ def test_engines_follow_in_place_parameter_updates_across_train_eval_toggles():
         assert torch.equal(a, b)
 
 
+def _erfnet(prec):
+    from lav_amd.erfnet import ERFNet
+    x = torch.rand(1, 3, 32, 256, device=DEV) * 255       # the three downsamplers give the pair kernels' widths 128, 64 and 32
+
+    def run(m):
+        with ops.precision(prec):
+            return m(x, input_affine=(2.0 / 255.0, -1.0), softmax=True)
+    return (lambda: ERFNet(5)), run
+
+
+def _brake_trunk():
+    from lav_amd.rgb import RGBBrakePredictionModel
+    x = torch.rand(1, 3, 64, 64, device=DEV) * 255
+    return (lambda: RGBBrakePredictionModel([4, 6, 7, 10, 18])), (lambda m: m.trunk(x))
+
+
+def _pillar():
+    from lav_amd.point_pillar import PointPillarNet
+    pts = torch.rand(1, 300, 11, device=DEV)
+    pts[..., 0] *= 16; pts[..., 1] = pts[..., 1] * 16 - 8                 # inside the 32x32 grid
+    return (lambda: PointPillarNet(16, [64, 64], min_x=0, max_x=16, min_y=-8, max_y=8, pixels_per_meter=2)), (lambda m: m(pts, [300]))
+
+
+@pytest.mark.parametrize("case", ["erfnet-f16x3", "erfnet-default", "brake-trunk", "pillar"])
+def test_engines_of_the_other_modules_follow_in_place_updates_across_train_eval_toggles(case):
+    """The same pattern on the modules whose caches are plain copies (ERFNet's packed pairs at both precisions, the folded PointNet,
+    the brake net's input affine) or sit behind another module (its ResNet-18 trunk): eval output, train(), every parameter and running
+    statistic changed in place, eval() - bit for bit what a model freshly built from the new state_dict gives."""
+    import copy
+    torch.manual_seed(21)
+    make, run = {"erfnet-f16x3": lambda: _erfnet(_lib.CONV_F16X3), "erfnet-default": lambda: _erfnet(0),
+                 "brake-trunk": _brake_trunk, "pillar": _pillar}[case]()
+    m = make().to(DEV).eval()
+    with torch.no_grad():
+        y0 = run(m).clone()
+        m.train()
+        for p in m.parameters():
+            p.add_(torch.randn_like(p) * 0.02)
+        for b in m.modules():
+            if isinstance(b, torch.nn.modules.batchnorm._BatchNorm):
+                b.running_mean.add_(0.05); b.running_var.mul_(1.2)
+        m.eval()
+        y1 = run(m).clone()
+        ref = make()
+        ref.load_state_dict(copy.deepcopy(m.state_dict()))
+        y2 = run(ref.to(DEV).eval())
+    assert y0.shape == y1.shape and not torch.equal(y0, y1)
+    assert torch.equal(y1, y2)
+
+
 @pytest.mark.parametrize("B,cin,cout,H", [(57, 128, 64, 12), (2, 256, 128, 6), (16, 64, 32, 40)])
 def test_transposed_convolution_with_empty_parity_classes(B, cin, cout, H):
     """ConvTranspose2d(k=1, stride=2, output_padding=1) - the adjoint of ResNet's 1x1 stride-2 down-sampling convolutions: three
