@@ -633,8 +633,8 @@ extern "C" int lav_embed_cast(const float *feat, int B, int embd_dim, int hw, fl
     LAV_REQUIRE(B >= 0 && embd_dim > 0 && embd_dim <= 1024 && hw >= 1 && num_cmds > 0 && T > 0, "lav_embed_cast: bad sizes");
     LAV_REQUIRE(H == CAST_H, "lav_embed_cast: hidden size %d not instantiated (%d)", H, CAST_H);
     LAV_REQUIRE(B <= 65535, "lav_embed_cast: B too large");
+    if (B == 0) return LAV_OK;   // (before any pointer check: the buffers of an empty batch may all be null)
     LAV_REQUIRE((cmd_w == nullptr) == (cmds_out == nullptr) && (cmd_w == nullptr) == (cmd_b == nullptr), "lav_embed_cast: cmd_w, cmd_b and cmds_out come together");
-    if (B == 0) return LAV_OK;
     LAV_REQUIRE(feat && w_ih && w_hh && b_ih && b_hh && mlp_w && mlp_b && out, "lav_embed_cast: null argument");
     const int tok = timer_begin("gru_cast", static_cast<hipStream_t>(stream));
     hipLaunchKernelGGL(k_gru_cast, dim3(num_cmds, B), dim3(CAST_THREADS), 0, static_cast<hipStream_t>(stream), feat, embd_dim,
@@ -660,7 +660,7 @@ int plan_launch(bool allow_persistent, const float *embd, const float *nxp, cons
                 const float *w_hh, const float *b_ih, const float *b_hh, const float *mlp_w,
                 const float *mlp_b, float *out, void *workspace, size_t workspace_bytes, void *stream) {
     LAV_REQUIRE(B >= 0 && num_cmds > 0 && T > 0 && T <= 64 && iters > 0, "lav_gru_plan: bad sizes");
-    LAV_REQUIRE(H % 64 == 0 && H <= 64 * PLAN_MAXK && H % PLAN_UNITS == 0, "lav_gru_plan: hidden size %d unsupported", H);
+    LAV_REQUIRE(H > 0 && H % 64 == 0 && H <= 64 * PLAN_MAXK && H % PLAN_UNITS == 0, "lav_gru_plan: hidden size %d unsupported", H);
     LAV_REQUIRE(cmd >= -1 && cmd < num_cmds, "lav_gru_plan: cmd %d out of range", cmd);
     if (B == 0) return LAV_OK;
     LAV_REQUIRE(embd && nxp && cast_locs && w_ih && w_hh && b_ih && b_hh && mlp_w && mlp_b && out, "lav_gru_plan: null argument");
