@@ -389,7 +389,8 @@ int lav_crop_rotate_backward(const float *grad_out, int num_maps, const int *map
  *    det_inference() (:95-121) from size [size_c][h][w] and ori [ori_c][h][w].
  *    out [ncls][max_det][3 + size_c + ori_c] = (score, x, y, size..., ori...), rows by descending score, ties by
  *    ascending pixel index; if a plane has fewer than max_det non-suppressed pixels the remaining rows carry
- *    score -1e5.  The last 256 bytes of the workspace are counters: zero before the first use, left zero.
+ *    score -1e5 and zeros.  A NaN is ignored inside every window, and a NaN pixel itself survives and sorts by its bit
+ *    pattern (a +NaN before every number).  The last 256 bytes of the workspace are counters: zero before the first use, left zero.
  * ------------------------------------------------------------------------------------------ */
 int lav_merge_ticks(const float *tick, float *prev, int rows, int dim, float *cur, void *stream);
 int lav_stack_sweeps(const float *fused, float *ring, const long *d_slot, const long *d_sweeps, const float *d_R,
@@ -433,6 +434,7 @@ int lav_attn_train_backward(const float *x, int batch, int C, int N, int heads, 
  * Sticky and device resident: enqueued behind a frame's last kernels (it is part of the HIP graphs), read by the host when it
  * likes.  The reference checks its waypoints on the host every tick (lav_agent_fast.py:325-328, np.isnan after .cpu()); this is
  * the same question asked without a device->host copy per tensor, so that a benchmark loop can prove every timed frame finite.
+ * A tensor of zero elements is finite, and its pointer may be NULL.
  */
 int lav_nonfinite_count(int n, const float *const *tensors, const long *numel, int *counter2, void *stream);
 

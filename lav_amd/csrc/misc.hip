@@ -365,7 +365,7 @@ extern "C" int lav_nonfinite_count(int n, const float *const *tensors, const lon
     for (int i = 0; i < FINITE_MAX; ++i) {
         a.p[i] = i < n ? tensors[i] : nullptr;
         a.n[i] = i < n ? numel[i] : 0;
-        if (i < n) LAV_REQUIRE(tensors[i] != nullptr && numel[i] >= 0, "lav_nonfinite_count: tensor %d is null", i);
+        if (i < n) LAV_REQUIRE(numel[i] >= 0 && (tensors[i] != nullptr || numel[i] == 0), "lav_nonfinite_count: tensor %d is null", i);
     }
     hipLaunchKernelGGL(k_nonfinite_count, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), a, counter2);
     LAV_LAUNCH_CHECK();

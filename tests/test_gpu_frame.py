@@ -9,6 +9,7 @@ import torch
 from lav_amd import ops, synth
 from oracle import bev as obev
 from oracle import frame as oframe
+from tests import frame_ref_util
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
@@ -78,6 +79,8 @@ def test_extract_peaks_matches_oracle(shape, seed):
     rows = ops.extract_peaks(logits.to(DEV), size.to(DEV), ori.to(DEV), apply_sigmoid=True).cpu()
     rows2 = ops.extract_peaks(torch.sigmoid(logits).to(DEV), size.to(DEV), ori.to(DEV)).cpu()
     hm = torch.sigmoid(logits)
+    # the pre-sigmoided call bit for bit against the documented rule (ties by ascending pixel index): the plateau's order counts
+    np.testing.assert_array_equal(rows2.numpy(), frame_ref_util.peaks_ref(hm.numpy(), size.numpy(), ori.numpy(), 7, 15)[0])
     for c in range(ncls):
         score, loc = obev.extract_peak(hm[c])
         for r in (rows, rows2):
