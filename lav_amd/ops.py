@@ -1483,19 +1483,25 @@ train_work = {"crop_rotate_backward_bytes": 0, "crop_rotate_backward_calls": 0, 
               "bn_train_fwd_bytes": 0, "bn_train_bwd_bytes": 0, "conv_wgrad_flops": 0}
 
 
+def _crop_args(features, locs, oris, crop):
+    """The tensors both crop entry points pass on, and their output: features (M,C,H,W), locs (n,2), oris (n,), out (n,C,crop,crop)."""
+    features = _f32c(features, "features")
+    locs, oris = _f32c(locs.detach().reshape(-1, 2), "locs"), _f32c(oris.detach().reshape(-1), "oris")
+    out = torch.empty((locs.shape[0], features.shape[1], crop, crop), dtype=torch.float32, device=features.device)
+    return features, locs, oris, out
+
+
 class _CropRotateIndexed(torch.autograd.Function):
     """Rotated crops taken from per-sample feature maps by index, differentiable in the maps (training path)."""
 
     @staticmethod
     def forward(ctx, features, map_index, locs, oris, ppm, crop, ox, oy):
         lib = _lib.load()
-        features = _f32c(features, "features")
-        locs, oris = _f32c(locs.detach().reshape(-1, 2), "locs"), _f32c(oris.detach().reshape(-1), "oris")
+        features, locs, oris, out = _crop_args(features, locs, oris, crop)
         if map_index.dtype != torch.int32 or not map_index.is_cuda:
             raise RuntimeError("crop_rotate_indexed: map_index must be an int32 tensor in HBM")
         M, Cc, H, W = features.shape
         n = locs.shape[0]
-        out = torch.empty((n, Cc, crop, crop), dtype=torch.float32, device=features.device)
         check(lib.lav_crop_rotate_indexed(_ptr(features), M, _ptr(map_index), Cc, H, W, _ptr(locs), _ptr(oris), n, float(ppm), int(crop),
                                           float(ox), float(oy), _ptr(out), _stream()), "lav_crop_rotate_indexed")
         ctx.save_for_backward(map_index, locs, oris)
@@ -1681,14 +1687,11 @@ def crop_rotate(features: torch.Tensor, locs: torch.Tensor, oris: torch.Tensor, 
                 offset_x: float, offset_y: float) -> torch.Tensor:
     """features (1 or N, C, H, W), locs (N,2), oris (N,) in HBM -> (N, C, crop, crop)."""
     lib = _lib.load()
-    features = _f32c(features, "features")
-    locs = _f32c(locs.reshape(-1, 2), "locs")
-    oris = _f32c(oris.reshape(-1), "oris")
+    features, locs, oris, out = _crop_args(features, locs, oris, crop)
     fb, Cc, H, W = features.shape
     n = locs.shape[0]
     if fb not in (1, n):
         raise RuntimeError("features batch must be 1 (shared map) or N")
-    out = torch.empty((n, Cc, crop, crop), dtype=torch.float32, device=features.device)
     check(lib.lav_crop_rotate(_ptr(features), fb, Cc, H, W, _ptr(locs), _ptr(oris), n, float(pixels_per_meter), int(crop),
                               float(offset_x), float(offset_y), _ptr(out), _stream()), "lav_crop_rotate")
     return out

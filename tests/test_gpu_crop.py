@@ -253,3 +253,47 @@ def test_non_square_maps_forward_backward_vs_grid_sample_float64(H, W, crop):
     out2 = ops.crop_rotate_indexed(f_gpu, idx.to(DEV), locs.to(DEV), oris.to(DEV), 2.0, crop, 0.0, 0.75)
     (out2 * w.to(DEV)).sum().backward()
     assert torch.equal(first, f_gpu.grad)                                                       # run-to-run identical bits
+
+
+_single = {}
+
+
+def single_data(geom):
+    """40 random channels of one map and an output gradient per pose, once per geometry: at 32 channels per workgroup one whole and
+    one partial block, at 16 (what the staged forward takes for a single crop) two whole and one partial."""
+    if geom not in _single:
+        H, W, crop = geom
+        g = torch.Generator().manual_seed(11)
+        _single[geom] = (torch.randn((1, 40, H, W), generator=g).to(DEV), torch.randn((16, 40, crop, crop), generator=g).to(DEV))
+    return _single[geom]
+
+
+@pytest.mark.parametrize("n", [1, 2])
+@pytest.mark.parametrize("geom", [(24, 24, 13), (40, 40, 24)], ids=cu.geom_id)
+def test_one_and_two_crops_staged_kernels_equal_the_general_ones(geom, n, monkeypatch):
+    """A launch of a single crop (and of two, the first count that takes 32 channels per workgroup again) on random data, which the
+    matrix tests above do not make: the staged forward gives the gathering forward's bits and the staged backward the general
+    backward's, at 16 of the poses (every third: all six kinds of location), the crops of a launch sharing the one map."""
+    assert cu.GEOMETRIES[geom] == ("staged", "staged")
+    off = cu.OFFSETS[0]
+    locs, oris, kinds, names = poses(geom, off)
+    feat, grads = single_data(geom)
+    pick = list(range(0, 48, 3))
+    assert len(pick) == 16 and {kinds[i] for i in pick} == set(cu.LOC_KINDS)
+    largest = 0.0
+    for a in range(0, 16, n):
+        sel = torch.tensor(pick[a:a + n])
+        lo, orr, idx = locs[sel].to(DEV), oris[sel].to(DEV), torch.zeros(n, dtype=torch.int32, device=DEV)
+        got = {}
+        for kernels in ("dispatch", "fwd_general", "bwd_general"):
+            select(monkeypatch, kernels)
+            f = feat.clone().requires_grad_(True)
+            out = ops.crop_rotate_indexed(f, idx, lo, orr, PPM, geom[2], *off)
+            out.backward(grads[a:a + n])
+            got[kernels] = (out.detach(), f.grad)
+        what = ", ".join(names[i] for i in sel.tolist())
+        assert torch.equal(got["dispatch"][0], got["fwd_general"][0]), f"{cu.geom_id(geom)}: staged forward != gathering forward at {what}"
+        assert torch.equal(got["dispatch"][0], ops.crop_rotate(feat, lo, orr, PPM, geom[2], *off)), f"lav_crop_rotate differs at {what}"
+        assert torch.equal(got["dispatch"][1], got["bwd_general"][1]), f"{cu.geom_id(geom)}: staged backward != general backward at {what}"
+        largest = max(largest, float(got["dispatch"][1].abs().max()))
+    assert largest > 0
