@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 41
+#define LAV_ABI_VERSION 42
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -996,6 +996,43 @@ size_t lav_eval_plans_words(int iters);
 int lav_eval_plans(const float *ego_plan, const float *ego_cast, const float *ego_cmds, const float *ego_locs, const int *cmds,
                    const unsigned char *bras, int batch, int iters, int num_plan, const float *other_cast, const float *other_cmds,
                    const float *other_locs, int num_others, long long *acc, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Open-loop metrics of the agent's rule layer over one evaluated frame (ABI 42; eval_drive_v2.py, lav_amd.train.evaluate_drive): one
+ * launch of one workgroup on `stream` that ADDS integers into an int64 accumulator in HBM; nothing is copied to the host.
+ * Specification: lav_amd.train.evaluate_drive.eval_drive_numpy, word for word, which also has the definitions in full.  The reference
+ * tuned these rules in closed-loop CARLA and has no evaluator: the definitions are this project's, parity is UNPINNED.
+ *
+ * ego_plan, ego_cast [num_plan][2] (the cast is the commanded mode), ego_locs [num_plan + 1][2]; other_cast [num_others <= 64][6]
+ * [num_plan][2], other_cmds [num_others][6], both may be NULL when num_others is 0; locs [max_objs <= 64][num_plan + 1][2], typs
+ * [max_objs] int32, of which the first num_objs count (both may be NULL when num_objs is 0).  2 <= num_plan <= 64, cmd in 0 .. 5, bra
+ * (the expert's brake label) 0 or 1, aim = the agent's aim_point[cmd] < num_plan, 1 <= nbins <= 1024.  The rule parameters are those of
+ * LAVAgent: brake_speed (metres per step), cmd_thresh, plan_collide's dist_static and dist_moving (metres), behind = 0.5
+ * pixels_per_meter and ego_radius = 4 / pixels_per_meter (metres); finite, at most 1e6, and all but cmd_thresh and behind not negative.
+ *
+ * q(a, b) = llrint(|a - b| * 2^20) in float64, lav_eval_frame's rule; P(p) the sum of a path's num_plan - 1 step quanta; S =
+ * llrint(brake_speed (num_plan - 1) 2^20), L(x) = llrint(x 2^20); slow(p) = P(p) < S.  The driven path wp is ego_cast for commands 4
+ * and 5, else ego_plan.  A trajectory is static when P < S, and hits when min_t q(traj[t], wp[t]) < L(dist_static) - or L(dist_moving)
+ * when it is not static.  The accumulator has 92 + 6 nbins words, as the size function says (0 for nbins outside 1 .. 1024), in this
+ * order:
+ *   frames; plan_nonfinite: frames with a step of wp or q(wp[aim], ego_locs[1 + aim]) not below 2^32 m, which add to nothing else;
+ *   expert_nonfinite: frames with such a step in ego_locs[1 ..], which add nothing to expert, speed and aim;
+ *   cause [bra][slow(wp) | static hit << 1 | moving hit << 2] over the forecasts: vehicle k is skipped when (double)other_cast[k][0][0][1]
+ *   > behind, its mode m when (double)other_cmds[k][m] < cmd_thresh (a NaN score stays);
+ *   gt_cause: the same over the tracks of type 1 but those with x^2 + y^2 <= ego_radius^2 at frame 0 or locs[g][1][1] > behind, traj =
+ *   locs[g][1 ..];  collide_conf [any track hit][any forecast hit];  ped [bra][a track of type 0 within L(dist_static) of wp];
+ *   expert [bra][slow(ego_locs[1 ..])];  speed [cmd][frames, P(wp), P(expert), |difference|];  aim [cmd][q(wp[aim], ego_locs[1 + aim]),
+ *   llrint(|dx| 2^20)];  modes [considered, static, hits, nonfinite] (a mode with a step or a distance that is not finite cannot hit);
+ *   vehicles_behind;  clear_none [bra][kind] and clear_hist [bra][kind][min(nbins - 1, C >> 17)], C the least min_t q over the
+ *   considered finite modes of that kind (0 static, 1 moving), none without one;  speed_hist [bra][min(nbins - 1, (P(wp) / (num_plan -
+ *   1)) >> 14)], which stands before clear_hist.
+ * One wave per mode and per track, four waves in all; one 64-bit atomic per counter that changes.
+ */
+size_t lav_eval_drive_words(int nbins);
+int lav_eval_drive(const float *ego_plan, const float *ego_cast, const float *ego_locs, int num_plan, int cmd, int bra, int aim,
+                   const float *other_cast, const float *other_cmds, int num_others, const float *locs, const int *typs, int max_objs,
+                   int num_objs, double brake_speed, double cmd_thresh, double dist_static, double dist_moving, double behind,
+                   double ego_radius, int nbins, long long *acc, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Baseline JPEG scans of RGB frames in HBM (ABI 41; the agent's MJPEG recording).  Specification: lav_amd.agent.mjpeg.scan_numpy,

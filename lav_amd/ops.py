@@ -649,6 +649,67 @@ def eval_plans(acc: torch.Tensor, ego_plan: torch.Tensor, ego_cast: torch.Tensor
     return acc
 
 
+def eval_drive_words(nbins: int = 64) -> int:
+    """Length of lav_eval_drive's accumulator, 92 + 6 nbins (lav_eval_drive_words; host only, no device needed)."""
+    n = int(_lib.load().lav_eval_drive_words(int(nbins)))
+    if n == 0:
+        raise ValueError(f"eval_drive: {nbins} histogram bins (1 .. 1024)")
+    return n
+
+
+def eval_drive(acc: torch.Tensor, ego_plan: torch.Tensor, ego_cast: torch.Tensor, cmd: int, bra: int, ego_locs: torch.Tensor, other_cast,
+               other_cmds, locs: torch.Tensor, typs: torch.Tensor, n: int, *, rules, nbins: int = 64) -> torch.Tensor:
+    """The open-loop metrics of the agent's brake and aim rules over one frame, ADDED into `acc` (int64, ops.eval_drive_words(nbins) words,
+    in HBM) by one launch on the current stream (lav_eval_drive); nothing comes back to the host.  ego_plan, ego_cast (T, 2) float32 (the
+    cast is the commanded mode, as UniPlanner.infer_all returns it), cmd 0 .. 5, bra 0 or 1 (the expert's brake label), ego_locs
+    (T + 1, 2); other_cast (N <= 64, 6, T, 2), other_cmds (N, 6) - with N = 0 they may be None or empty tensors on any device
+    (UniPlanner.infer_all returns CPU zeros then); locs (G <= 64, T + 1, 2) float32, typs (G,) int32 and n <= G: the ground truth as
+    the loaders return it.  2 <= T <= 64.  `rules` has the agent's constants as attributes (lav_amd.train.evaluate_drive.DriveRules):
+    brake_speed, cmd_thresh, dist_static, dist_moving, behind, ego_radius and aim_point, six indices below T.  Word for word
+    lav_amd.train.evaluate_drive.eval_drive_numpy, which has the definitions and names the accumulator's slices (DriveLayout).  Wrong
+    shapes, dtypes, devices or values raise ValueError before anything is launched."""
+    _eval_section("eval_drive", acc, eval_drive_words(nbins), "acc")
+    need = _eval_tensor("eval_drive", "evaluate_drive.eval_drive_numpy", acc, copy=True)
+    ego_plan = need("ego_plan", ego_plan, torch.float32, (None, 2))
+    T = ego_plan.shape[0]
+    if not 2 <= T <= 64:
+        raise ValueError(f"eval_drive: {T} waypoints (2 .. 64)")
+    ego_cast = need("ego_cast", ego_cast, torch.float32, (T, 2))
+    ego_locs = need("ego_locs", ego_locs, torch.float32, (T + 1, 2))
+    locs = need("locs", locs, torch.float32, (None, T + 1, 2))
+    G = locs.shape[0]
+    typs = need("typs", typs, torch.int32, (G,))
+    if isinstance(bra, torch.Tensor):
+        bra = bra.item()
+    n, cmd = int(n), int(cmd)
+    if G > 64 or not 0 <= n <= G:
+        raise ValueError(f"eval_drive: n = {n} of {G} tracks (at most 64)")
+    if not 0 <= cmd < 6:
+        raise ValueError(f"eval_drive: command {cmd} (0 .. 5)")
+    if bra not in (0, 1):
+        raise ValueError(f"eval_drive: brake label {bra!r} (0 or 1)")
+    count = lambda t: 0 if t is None else (t.shape[0] if t.dim() else 1)
+    N = count(other_cast)
+    if count(other_cmds) != N or N > 64:
+        raise ValueError(f"eval_drive: {count(other_cmds)} rows of command scores for {N} vehicles (at most 64)")
+    if N > 0:
+        other_cast = need("other_cast", other_cast, torch.float32, (N, 6, T, 2))
+        other_cmds = need("other_cmds", other_cmds, torch.float32, (N, 6))
+    else:
+        other_cast = other_cmds = None
+    aim_point = [int(a) for a in rules.aim_point]
+    if len(aim_point) != 6 or min(aim_point) < 0 or max(aim_point) >= T:
+        raise ValueError(f"eval_drive: aim_point {aim_point}: six waypoint indices below {T}")
+    scalars = [float(rules.brake_speed), float(rules.cmd_thresh), float(rules.dist_static), float(rules.dist_moving), float(rules.behind),
+               float(rules.ego_radius)]
+    if not all(np.isfinite(scalars)) or max(abs(s) for s in scalars) > 1e6 or min(scalars[0], scalars[2], scalars[3], scalars[5]) < 0:
+        raise ValueError("eval_drive: the rule parameters must be finite, at most 1e6, and speeds, limits and the radius not negative")
+    check(_lib.load().lav_eval_drive(_ptr(ego_plan), _ptr(ego_cast), _ptr(ego_locs), T, cmd, int(bra), aim_point[cmd], _ptr(other_cast),
+                                     _ptr(other_cmds), N, _ptr(locs) if G else None, _ptr(typs) if G else None, G, n, *scalars, int(nbins),
+                                     _ptr(acc), _stream()), "lav_eval_drive")
+    return acc
+
+
 # ------------------------------------------------------------------------------------------ GRU decoders
 def gru_cast(embd, w_ih, w_hh, b_ih, b_hh, mlp_w, mlp_b, T: int):
     """embd (B, E); stacked per-command GRU/MLP weights -> (B, num_cmds, T, 2)."""

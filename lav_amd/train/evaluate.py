@@ -248,8 +248,9 @@ class Evaluator(EvaluatorBase):
         return len(self._batch["cmds"])
 
     @torch.no_grad()
-    def frame(self, i):
-        """Sample i of the uploaded batch: InferModel.forward's chain with the trainers' 20 peaks per class, then the metrics launch."""
+    def forward(self, i) -> dict:
+        """Sample i of the uploaded batch through InferModel.forward's chain with the trainers' 20 peaks per class: what the metrics
+        launches read, all of it in HBM but other_row (and the CPU zeros of a frame without forecasts)."""
         from .. import ops
         b, im = self._batch, self.infer
         lm, up = im.lidar_model, im.uniplanner
@@ -262,10 +263,22 @@ class Evaluator(EvaluatorBase):
             rows_host = rows.cpu().numpy()              # the copy InferModel.forward makes: the others branch is sized on the host
             dets, _, _ = im.det_decode_fast(rows_host)
             other_row = forecast_rows(im, rows_host, dets[1])
-            _, ego_plan, _, other_cast, other_cmds = up.infer_all(features[0], dets[1], cmd, b["nxps"][i], amax=ops.amax_of(features))
+            _, ego_plan, ego_cast, other_cast, other_cmds = up.infer_all(features[0], dets[1], cmd, b["nxps"][i], amax=ops.amax_of(features))
+        return dict(pred_bev=pred_bev[0], rows=rows, cmd=cmd, ego_plan=ego_plan, ego_cast=ego_cast, other_cast=other_cast, other_cmds=other_cmds,
+                    other_row=other_row)
+
+    def metrics(self, i, out):
+        """The metrics launch of sample i on what `forward` returned."""
+        b = self._batch
         n = min(b["n"][i], b["locs"].shape[1])
-        args = (pred_bev[0], b["bev"][i], self.mask, rows, b["locs"][i], b["typs"][i], n, ego_plan, b["ego_locs"][i], cmd, other_cast, other_cmds)
-        self._add("eval_frame", eval_frame_numpy, None, *args, torch.from_numpy(other_row).to(self.device), **self.kw)
+        args = (out["pred_bev"], b["bev"][i], self.mask, out["rows"], b["locs"][i], b["typs"][i], n, out["ego_plan"], b["ego_locs"][i], out["cmd"],
+                out["other_cast"], out["other_cmds"])
+        self._add("eval_frame", eval_frame_numpy, None, *args, torch.from_numpy(out["other_row"]).to(self.device), **self.kw)
+
+    @torch.no_grad()
+    def frame(self, i):
+        """Sample i of the uploaded batch: the forward chain, then the metrics launch."""
+        self.metrics(i, self.forward(i))
         self.frames += 1
 
     def run(self, batches, max_frames=None) -> int:
