@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 42
+#define LAV_ABI_VERSION 43
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -996,6 +996,43 @@ size_t lav_eval_plans_words(int iters);
 int lav_eval_plans(const float *ego_plan, const float *ego_cast, const float *ego_cmds, const float *ego_locs, const int *cmds,
                    const unsigned char *bras, int batch, int iters, int num_plan, const float *other_cast, const float *other_cmds,
                    const float *other_locs, int num_others, long long *acc, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The LiDAR student beside the BEV teacher it was distilled from, on the same frames and the same crops (ABI 43; eval_distill_v2.py,
+ * lav_amd.train.evaluate_distill): one launch per group of frames on `stream` that ADDS the PAIRED integers - what two separate
+ * lav_eval_plans accumulators cannot give - into an int64 accumulator in HBM; nothing is copied to the host.  Specification:
+ * lav_amd.train.evaluate_distill.eval_distill_numpy, word for word.  The reference has no evaluator: the definitions are this
+ * project's, parity with a reference is UNPINNED.
+ *
+ * s_* the student's and t_* the teacher's outputs, lav_eval_plans' shapes: ego_plan [batch][iters][6][num_plan][2], ego_cast [batch][6]
+ * [num_plan][2], ego_cmds [batch][6], other_cast [num_others][6][num_plan][2], other_cmds [num_others][6]; ego_locs [batch][num_plan + 1]
+ * [2], cmds [batch] int32, other_locs [num_others][num_plan][2]; the five forecast tensors may be NULL when num_others is 0.  batch >= 1,
+ * num_others >= 0, 1 <= num_plan <= 64, 1 <= iters <= 8.
+ *
+ * S = iters + 1 stages: stage 0 is the cast, stage s refinement s - 1 of the plan.  q_t = llrint(sqrt(dx^2 + dy^2) * 2^20) in float64,
+ * lav_eval_frame's rule, and a path with a distance that is not below 2^32 m is non-finite; a score gap is llrint(|s - t| * 2^20) in
+ * float64, non-finite where the difference is not below 2^32 (NaN, Inf).  The accumulator has 114 + 38 S words, as the size function says
+ * (0 for iters outside 1 .. 8), in this order:
+ *   frames; bad_cmd: frames whose command is outside 0 .. 5, which add to nothing else;
+ *   ego_gap [S][6 modes][items, sum of q_t, q_{T-1}], the student's waypoints against the teacher's; ego_gap_nonfinite [S]: the
+ *   non-finite (stage, mode) pairs, which count here instead;
+ *   ego_closer [S][command][student, teacher, tie]: at the frame's command, whose sum of q_t against ego_locs[.][1 ..] is the smaller;
+ *   ego_unjudged [S]: frames where either arm's is non-finite at that stage, which count here instead;
+ *   cmd_agree [teacher's first maximum of ego_cmds][student's; a NaN counts as a maximum];
+ *   cmd_gap [6 modes][items, sum of the score gaps]; cmd_nonfinite: the non-finite (frame, mode) gaps, which count here instead;
+ *   others: forecasts scored; oth_nonfinite: forecasts with a non-finite path - either arm against other_locs or the student against
+ *   the teacher, any mode - or a non-finite score gap, which add to nothing else;
+ *   oth_gap [6 modes][sum of q_t, q_{T-1}], the student's forecast against the teacher's;
+ *   oth_closer [student, teacher, tie] by each arm's smallest sum over its modes against other_locs, oth_closer_top [3] by the sum of
+ *   each arm's own top mode (the first maximum of its other_cmds); oth_same_min: forecasts where both arms' min mode (the first
+ *   minimum) is the same; oth_top_agree [teacher's top mode][student's]; oth_cmd_gap [6 modes]: sums of the score gaps.
+ * One wave per frame and per forecast, four to a workgroup; one 64-bit atomic per workgroup and counter.
+ */
+size_t lav_eval_distill_words(int iters);
+int lav_eval_distill(const float *s_ego_plan, const float *s_ego_cast, const float *s_ego_cmds, const float *t_ego_plan,
+                     const float *t_ego_cast, const float *t_ego_cmds, const float *ego_locs, const int *cmds, int batch, int iters,
+                     int num_plan, const float *s_other_cast, const float *s_other_cmds, const float *t_other_cast,
+                     const float *t_other_cmds, const float *other_locs, int num_others, long long *acc, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Open-loop metrics of the agent's rule layer over one evaluated frame (ABI 42; eval_drive_v2.py, lav_amd.train.evaluate_drive): one

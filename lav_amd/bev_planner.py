@@ -4,18 +4,13 @@ exist for drop-in loading; its cast/plan decoders run on the same HIP GRU kernel
 """
 from __future__ import annotations
 
-import collections
-
 import numpy as np
 import torch
 from torch import nn
 
-from . import ops
-from .planner_common import PlannerBase, picked_others, sample_others, select_others
+from . import planner_common
+from .planner_common import BatchInference, PlannerBase, sample_others  # noqa: F401  (BatchInference: infer_batch's result, read here too)
 from .resnet import resnet18
-
-# BEVPlanner.infer_batch's result: forward's six outputs, then the (sample, actor) index of every forecast (actor counts locs[:, 1:])
-BatchInference = collections.namedtuple("BatchInference", "other_locs other_cast other_cmds ego_plan ego_cast ego_cmds sample actor")
 
 
 class BEVPlanner(PlannerBase):
@@ -60,31 +55,7 @@ class BEVPlanner(PlannerBase):
         BatchInference: other_locs (K, T, 2), other_cast (K, 6, T, 2), other_cmds (K, 6), ego_plan (B, I, 6, T, 2), ego_cast
         (B, 6, T, 2), ego_cmds (B, 6), sample (K,) and actor (K,) int32; K = 0 gives empty tensors on the device.  Eval mode only (the
         module has no HIP train-mode decoders); the convolutions follow ops.precision; the global generators are not touched."""
-        if self.training:
-            raise RuntimeError("BEVPlanner.infer_batch runs the eval-mode kernels: call .eval() first")
-        if others not in ("ahead", "all"):
-            raise ValueError(f"infer_batch: others={others!r} (ahead or all)")
-        if not bev.is_cuda:
-            raise RuntimeError("BEVPlanner.infer_batch: the batch must be in HBM; lav_amd has no CPU inference path")
-        ppm, crop, B = self.pixels_per_meter, self.crop_size * 2, bev.size(0)
-        z = dict(dtype=bev.dtype, device=bev.device)
-        picked = select_others(ego_locs, locs, typs, ahead=others == "ahead")
-        pick = picked_others(ego_locs, locs, oris, picked, lambda K, device: (torch.zeros((K, 2), **z), torch.zeros((K,), **z)))
-        K = pick["sample"].size(0)
-        other_embd = None      # (the launches in forward's order: the others' crops, then the ego's)
-        if K:
-            other_embd = self.bev_conv_emb(ops.crop_rotate_indexed(bev, pick["sample"], pick["crop_locs"], pick["crop_oris"], ppm, crop, *self.offsets()))
-            other_cmds = self.cast_cmd_pred(other_embd)
-        ego_embd = self.bev_conv_emb(ops.crop_rotate_indexed(bev, torch.arange(B, dtype=torch.int32, device=bev.device), bev.new_zeros((B, 2)),
-                                                             bev.new_zeros((B,)), ppm, crop, *self.offsets()))
-        if K:
-            both = self.cast(torch.cat([other_embd, ego_embd]))      # (one cast() over others + ego, as forward)
-            other_cast, ego_cast = both[:K], both[K:]
-        else:
-            ego_cast = self.cast(ego_embd)
-            other_cast, other_cmds = torch.zeros((0, self.num_cmds, self.num_plan, 2), **z), torch.zeros((0, self.num_cmds), **z)
-        ego_plan = self.plan(ego_embd, nxps, cast_locs=ego_cast, pixels_per_meter=ppm, crop_size=crop)
-        return BatchInference(pick["other_locs"], other_cast, other_cmds, ego_plan, ego_cast, self.cast_cmd_pred(ego_embd), pick["sample"], pick["actor"])
+        return planner_common.infer_batch(self, self.bev_conv_emb, bev, ego_locs, locs, oris, nxps, typs, others, self.pixels_per_meter, self.crop_size * 2)
 
     def forward(self, bev, ego_locs, locs, oris, nxps, typs):
         """Training forward of the privileged planner (bev_planner_v2.py:72-174): forecasts for up to `max_num_cars`

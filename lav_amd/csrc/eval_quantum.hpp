@@ -39,4 +39,13 @@ __device__ __forceinline__ int first_max(const float *v) {
     }
     return top;
 }
+
+// the gap of two scores (eval_distill.hip): g = llrint(|a - b| * 2^20) in float64; false where the difference is not below 2^32 - a NaN,
+// an Inf, or a pair of absurd scores whose quanta would not fit the 64-bit sums
+__device__ __forceinline__ bool scalar_gap(float a, float b, long long &g) {
+    const double d = fabs((double)a - (double)b);
+    const bool ok = d < EVAL_FAR;
+    g = ok ? llrint(d * EVAL_Q) : 0;
+    return ok;
+}
 }  // namespace lav

@@ -649,6 +649,62 @@ def eval_plans(acc: torch.Tensor, ego_plan: torch.Tensor, ego_cast: torch.Tensor
     return acc
 
 
+def eval_distill_words(iters: int) -> int:
+    """Length of lav_eval_distill's accumulator for `iters` plan iterations, 114 + 38 (iters + 1) (lav_eval_distill_words; host only, no
+    device needed)."""
+    n = int(_lib.load().lav_eval_distill_words(int(iters)))
+    if n == 0:
+        raise ValueError(f"eval_distill: {iters} plan iterations (1 .. 8)")
+    return n
+
+
+def eval_distill(acc: torch.Tensor, s_ego_plan: torch.Tensor, s_ego_cast: torch.Tensor, s_ego_cmds: torch.Tensor, t_ego_plan: torch.Tensor,
+                 t_ego_cast: torch.Tensor, t_ego_cmds: torch.Tensor, ego_locs: torch.Tensor, cmds: torch.Tensor, s_other_cast=None,
+                 s_other_cmds=None, t_other_cast=None, t_other_cmds=None, other_locs=None) -> torch.Tensor:
+    """The student (s_*) beside the teacher (t_*) over one group of frames, the paired counters ADDED into `acc` (int64,
+    ops.eval_distill_words(I) words, in HBM) by one launch on the current stream (lav_eval_distill); nothing comes back to the host.  Per
+    arm ego_plan (B, I, 6, T, 2), ego_cast (B, 6, T, 2), ego_cmds (B, 6), other_cast (K, 6, T, 2), other_cmds (K, 6) float32; ego_locs
+    (B, T + 1, 2) float32; cmds (B,) int32; other_locs (K, T, 2) float32 - with K = 0 the five forecast tensors may be None or empty.
+    B >= 1, 1 <= T <= 64, 1 <= I <= 8.  Word for word lav_amd.train.evaluate_distill.eval_distill_numpy, which names the accumulator's
+    slices (PairLayout).  Wrong shapes, dtypes, devices or an accumulator of another length raise ValueError before anything is launched."""
+    if not isinstance(acc, torch.Tensor) or not acc.is_cuda or acc.dtype != torch.int64 or acc.dim() != 1 or not acc.is_contiguous():
+        raise ValueError("eval_distill: acc must be a contiguous int64 tensor in HBM (lav_amd.train.evaluate_distill.eval_distill_numpy is the CPU specification)")
+    need = _eval_tensor("eval_distill", "evaluate_distill.eval_distill_numpy", acc)
+    if not isinstance(s_ego_plan, torch.Tensor) or s_ego_plan.dim() != 5:
+        raise ValueError("eval_distill: s_ego_plan must be a float32 tensor of shape (B, I, 6, T, 2)")
+    B, I, _, T, _ = s_ego_plan.shape
+    if B < 1 or B > 1 << 20 or not 1 <= T <= 64 or not 1 <= I <= 8:
+        raise ValueError(f"eval_distill: s_ego_plan {tuple(s_ego_plan.shape)}: at least one frame, 1 .. 8 iterations, 1 .. 64 waypoints")
+    words = eval_distill_words(I)
+    if acc.shape[0] != words:
+        raise ValueError(f"eval_distill: acc has {acc.shape[0]} words, {I} plan iterations take {words}")
+    s_ego_plan = need("s_ego_plan", s_ego_plan, torch.float32, (B, I, 6, T, 2))
+    t_ego_plan = need("t_ego_plan", t_ego_plan, torch.float32, (B, I, 6, T, 2))
+    s_ego_cast = need("s_ego_cast", s_ego_cast, torch.float32, (B, 6, T, 2))
+    t_ego_cast = need("t_ego_cast", t_ego_cast, torch.float32, (B, 6, T, 2))
+    s_ego_cmds = need("s_ego_cmds", s_ego_cmds, torch.float32, (B, 6))
+    t_ego_cmds = need("t_ego_cmds", t_ego_cmds, torch.float32, (B, 6))
+    ego_locs = need("ego_locs", ego_locs, torch.float32, (B, T + 1, 2))
+    cmds = need("cmds", cmds, torch.int32, (B,))
+    count = lambda t: 0 if t is None else (t.shape[0] if t.dim() else 1)
+    others = dict(s_other_cast=s_other_cast, s_other_cmds=s_other_cmds, t_other_cast=t_other_cast, t_other_cmds=t_other_cmds, other_locs=other_locs)
+    K = count(s_other_cast)
+    if any(count(t) != K for t in others.values()):
+        raise ValueError(f"eval_distill: {K} forecasts, but " + ", ".join(f"{count(t)} rows of {k}" for k, t in others.items()))
+    if K > 1 << 24:
+        raise ValueError(f"eval_distill: {K} forecasts (at most 2^24)")
+    if K > 0:
+        shapes = dict(s_other_cast=(K, 6, T, 2), s_other_cmds=(K, 6), t_other_cast=(K, 6, T, 2), t_other_cmds=(K, 6), other_locs=(K, T, 2))
+        others = {k: need(k, t, torch.float32, shapes[k]) for k, t in others.items()}
+    else:
+        others = dict.fromkeys(others)
+    check(_lib.load().lav_eval_distill(_ptr(s_ego_plan), _ptr(s_ego_cast), _ptr(s_ego_cmds), _ptr(t_ego_plan), _ptr(t_ego_cast), _ptr(t_ego_cmds),
+                                       _ptr(ego_locs), _ptr(cmds), B, I, T, _ptr(others["s_other_cast"]), _ptr(others["s_other_cmds"]),
+                                       _ptr(others["t_other_cast"]), _ptr(others["t_other_cmds"]), _ptr(others["other_locs"]), K, _ptr(acc),
+                                       _stream()), "lav_eval_distill")
+    return acc
+
+
 def eval_drive_words(nbins: int = 64) -> int:
     """Length of lav_eval_drive's accumulator, 92 + 6 nbins (lav_eval_drive_words; host only, no device needed)."""
     n = int(_lib.load().lav_eval_drive_words(int(nbins)))

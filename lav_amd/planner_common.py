@@ -1,6 +1,8 @@
 """Pieces shared by UniPlanner and BEVPlanner: the GRU decoders on liblav_amd and the rotated crop."""
 from __future__ import annotations
 
+import collections
+
 import torch
 import torch.nn.functional as F
 
@@ -121,6 +123,45 @@ def sample_others(self, ego_locs, locs, oris, typs):
         oris_jitter = (torch.rand((K,)) * 2 - 1).float().to(device) * self.feature_angle_jitter
         return locs_jitter, oris_jitter
     return picked_others(ego_locs, locs, oris, typs, jitter), locs.size(1) - 1
+
+
+# infer_batch's result: forward's six outputs, then the (sample, actor) index of every forecast (actor counts locs[:, 1:])
+BatchInference = collections.namedtuple("BatchInference", "other_locs other_cast other_cmds ego_plan ego_cast ego_cmds sample actor")
+
+
+def infer_batch(planner, embed, maps, ego_locs, locs, oris, nxps, typs, others, map_ppm, map_crop):
+    """What BEVPlanner.infer_batch and UniPlanner.infer_batch share: a loader batch through `planner` with no random draw.  The picks
+    are select_others + picked_others with zero jitter (every vehicle among locs[:, 1:] that qualifies, no cap at max_num_cars); `embed`
+    (the planner's crop embedder) reads map_crop-pixel crops of `maps` at map_ppm pixels per metre, the others' first and then the B
+    ego crops, as the forwards launch them; one cast() over others + ego, cast_cmd_pred, and plan for all six commands and every
+    refinement.  Returns BatchInference; K = 0 gives empty tensors on the device.  Eval mode only, `maps` in HBM; the global generators
+    are not touched."""
+    name = type(planner).__name__
+    if planner.training:
+        raise RuntimeError(f"{name}.infer_batch runs the eval-mode kernels: call .eval() first")
+    if others not in ("ahead", "all"):
+        raise ValueError(f"infer_batch: others={others!r} (ahead or all)")
+    if not maps.is_cuda:
+        raise RuntimeError(f"{name}.infer_batch: the batch must be in HBM; lav_amd has no CPU inference path")
+    ppm, crop, B = planner.pixels_per_meter, planner.crop_size * 2, maps.size(0)
+    z = dict(dtype=maps.dtype, device=maps.device)
+    picked = select_others(ego_locs, locs, typs, ahead=others == "ahead")
+    pick = picked_others(ego_locs, locs, oris, picked, lambda K, device: (torch.zeros((K, 2), **z), torch.zeros((K,), **z)))
+    K = pick["sample"].size(0)
+    other_embd = None      # (the launches in forward's order: the others' crops, then the ego's)
+    if K:
+        other_embd = embed(ops.crop_rotate_indexed(maps, pick["sample"], pick["crop_locs"], pick["crop_oris"], map_ppm, map_crop, *planner.offsets()))
+        other_cmds = planner.cast_cmd_pred(other_embd)
+    ego_embd = embed(ops.crop_rotate_indexed(maps, torch.arange(B, dtype=torch.int32, device=maps.device), maps.new_zeros((B, 2)),
+                                             maps.new_zeros((B,)), map_ppm, map_crop, *planner.offsets()))
+    if K:
+        both = planner.cast(torch.cat([other_embd, ego_embd]), mode="ego")      # (one cast() over others + ego, as forward)
+        other_cast, ego_cast = both[:K], both[K:]
+    else:
+        ego_cast = planner.cast(ego_embd, mode="ego")
+        other_cast, other_cmds = torch.zeros((0, planner.num_cmds, planner.num_plan, 2), **z), torch.zeros((0, planner.num_cmds), **z)
+    ego_plan = planner.plan(ego_embd, nxps, cast_locs=ego_cast, pixels_per_meter=ppm, crop_size=crop)
+    return BatchInference(pick["other_locs"], other_cast, other_cmds, ego_plan, ego_cast, planner.cast_cmd_pred(ego_embd), pick["sample"], pick["actor"])
 
 
 class PlannerBase(Engine):

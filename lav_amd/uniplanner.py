@@ -8,7 +8,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import ops
+from . import ops, planner_common
 from .planner_common import PlannerBase, sample_others, transform_points
 from .resnet import resnet18
 
@@ -126,6 +126,19 @@ class UniPlanner(PlannerBase):
         ego_plan_locs = self.plan(ego_embd, nxps, cast_locs=ego_cast_locs, pixels_per_meter=ppm, crop_size=crop * 2)
         return (other_locs, other_cast_locs, other_cast_cmds, other_cast_locs_expert, other_cast_cmds_expert,
                 ego_locs, ego_plan_locs, ego_cast_locs, self.cast_cmd_pred(ego_embd), ego_cast_locs_expert, ego_plan_locs_expert)
+
+    @torch.no_grad()
+    def infer_batch(self, features, ego_locs, locs, oris, nxps, typs, others="ahead"):
+        """The student over a loader batch with no random draw (eval_distill_v2.py), the twin of BEVPlanner.infer_batch on the same
+        picks: forecasts for EVERY vehicle among locs[:, 1:] - others="ahead": those that pass filter_cars; "all": all of them; no cap
+        at max_num_cars - from its un-jittered crop of the LiDAR feature map, and cast, command scores and every refinement of the plan
+        from the B ego crops.  forward's eval-mode arithmetic in forward's launch order: crop_rotate_indexed at pixels_per_meter / 2 and
+        crop_size (with no activation bound, as forward hands none) -> lidar_conv_emb -> one cast(mode="ego") over others and ego /
+        cast_cmd_pred -> plan (all six commands); the poses are the GROUND TRUTH's, not detections (that is infer_all's path).
+        features (B, C, H, W) in HBM, the rest as forward's.  Returns planner_common.BatchInference; K = 0 gives empty tensors on the
+        device.  Eval mode only; the convolutions follow ops.precision; the global generators are not touched."""
+        return planner_common.infer_batch(self, self.lidar_conv_emb, features, ego_locs, locs, oris, nxps, typs, others, self.pixels_per_meter / 2,
+                                          self.crop_size)
 
     @torch.no_grad()
     def infer(self, features, det, cmd, nxp):
