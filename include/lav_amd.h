@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 43
+#define LAV_ABI_VERSION 44
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -399,6 +399,24 @@ size_t lav_extract_peaks_workspace_bytes(int ncls, int h, int w);
 int lav_extract_peaks(const float *heat, int ncls, int h, int w, int ks, int max_det, int apply_sigmoid,
                       const float *size, int size_c, const float *ori, int ori_c, float *out, void *workspace,
                       size_t workspace_bytes, void *stream);
+
+/* lav_heads_at_peaks (ABI 44): heads of the form conv3x3(cin -> hidden, padding 1, no bias) -> ReLU -> y * scale + shift (the folded
+ *    eval BatchNorm, fmaf(max(v, 0), scale, shift)) -> ConvTranspose2d(hidden -> outs, kernel 3, stride 2, padding 1, output_padding 1)
+ *    evaluated ONLY at the pixels named by peak rows, instead of on the whole [2h][2w] map: an output pixel depends on 1, 2 or 4 hidden
+ *    pixels by the parity of its coordinates, each hidden pixel on a 3 x 3 x cin window of the zero-padded feature map.
+ *    feat [cin][h][w] float32; rows [ncls][max_det][3] = (score, x, y) as lav_extract_peaks writes them with size_c = ori_c = 0;
+ *    per head g < nheads (1 .. 4): w1_packed[g] the first convolution's weights as [kpad][64] floats, kpad = 9 cin rounded up to 128,
+ *    row k = ci * 9 + ky * 3 + kx, column = hidden channel, zeros elsewhere (lav_heads_at_peaks_packed_floats(cin, hidden) floats; 0 for
+ *    bad sizes); scale[g], shift[g] [hidden[g]]; wt[g] the transposed convolution's weights [hidden[g]][outs[g]][3][3]; bias[g]
+ *    [outs[g]] or NULL; hidden[g] in 1 .. 64, outs[g] in 1 .. 4 (host arrays of device pointers / ints, read before the call returns).
+ *    out [ncls][max_det][3 + sum of outs]: columns 0 .. 2 copied, then head 0's values, head 1's, ... - the rows lav_det_decode takes.
+ *    A row with score <= -1e4 (lav_extract_peaks' "no candidate" rows carry -1e5) or with x / y non-finite or outside [0, 2w) x [0, 2h)
+ *    gets zeros behind its three columns; no address is formed from an unchecked row value.  Plain fp32 fmaf chains, combined in an order fixed
+ *    by (cin, hidden): results do not depend on the other rows and two launches are bit-identical.  No workspace. */
+size_t lav_heads_at_peaks_packed_floats(int cin, int hidden);
+int lav_heads_at_peaks(const float *feat, int cin, int h, int w, const float *rows, int ncls, int max_det, int nheads,
+                       const float *const *w1_packed, const float *const *scale, const float *const *shift, const float *const *wt,
+                       const float *const *bias, const int *hidden, const int *outs, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * 6b. Single-query attention pooling of the brake net.  Replaces Attention.forward, lav/models/attention.py:21-38

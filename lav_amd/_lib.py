@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LAV_AMD_LIB") or os.path.join(HERE, "liblav_amd.so")   # LAV_AMD_LIB: A/B a second build
 
-ABI_VERSION = 43
+ABI_VERSION = 44
 MAX_CAM = 4
 MAX_CAM_F64 = 8
 
@@ -157,6 +157,8 @@ SIGNATURES = {
     "lav_stack_sweeps": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "lav_extract_peaks_workspace_bytes": (_Z, [_I, _I, _I]),
     "lav_extract_peaks": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _Z, _P]),
+    "lav_heads_at_peaks_packed_floats": (_Z, [_I, _I]),
+    "lav_heads_at_peaks": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lav_augment_u8": (_I, [_P, _P, _I, _I, _I, _P, C.c_ulonglong, _P]),
     "lav_bev_stack_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "lav_bev_stack_tile_paths": (_I, [C.POINTER(C.c_double), C.POINTER(_I), _I, _I, C.POINTER(_I)]),

@@ -28,7 +28,8 @@ _BRAKE_AFTER = os.environ.get("LAV_BRAKE_AFTER", "in")       # "in": the brake g
 _BRAKE_SPLIT = os.environ.get("LAV_BRAKE_SPLIT", "wide")    # "wide" (round 6 default) | "tele": the brake net as two graphs on its stream - that image's trunk with the frame, the other's + poolings + classifier behind the lidar graph; "0": one graph with the frame
 if _BRAKE_SPLIT in ("0", "off", "none"):
     _BRAKE_SPLIT = ""
-_DIAG_SKIP = set(filter(None, os.environ.get("LAV_DIAG_SKIP", "").split(",")))   # timing diagnosis: skip side graphs
+_HEADS_AT_PEAKS = ops.frame_heads_at_peaks()                 # LAV_HEADS_AT_PEAKS=0: the dense four-head maps, gathered at the peaks (both frame paths, LiDARModel.detect)
+_DIAG_SKIP =set(filter(None, os.environ.get("LAV_DIAG_SKIP", "").split(",")))   # timing diagnosis: skip side graphs
 
 
 def ego_box_mask(lidar: torch.Tensor) -> torch.Tensor:
@@ -71,7 +72,8 @@ class FramePipeline:
         # engines are cached per precision on their modules, a model that a trainer owns keeps its default engines.
         # LAV_INFER_PRECISION=bf16x6 (or round 5's LAV_HEADS_PRECISION=bf16x6) switches the mode off; LAV_CONV_PRECISION=f32 too.
         self.precision = ops.frame_precision()
-        self.infer_model = InferModel(lidar_model, uniplanner, camera_x, camera_z, device=device, precision=self.precision)
+        self.infer_model = InferModel(lidar_model, uniplanner, camera_x, camera_z, device=device, precision=self.precision,
+                                      heads_at_peaks=_HEADS_AT_PEAKS)
         self.seg_model, self.bra_model = seg_model, bra_model
         self.num_frame_stack = num_frame_stack
         self.num_frame_keep = (num_frame_stack + 1) * GAP
@@ -262,8 +264,7 @@ class GraphedFramePipeline(FramePipeline):
         return dict(lidar_points=lidar_points)
 
     def _g_heads(self):
-        heat, size, ori, pred_bev = self.infer_model.lidar_model.heads(self.b_features)
-        det_raw = ops.extract_peaks(heat[0], size[0], ori[0], apply_sigmoid=True)                                 # (2,15,7)
+        det_raw, pred_bev = self.infer_model.lidar_model.detect(self.b_features, at_peaks=self.infer_model.heads_at_peaks)   # (2,15,7)
         if self.device_others:   # who the other vehicles are and how many: decided on the device (model_inference.py:95-144)
             im, up = self.infer_model, self.infer_model.uniplanner
             ox, oy = up.offsets()

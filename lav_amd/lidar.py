@@ -230,6 +230,27 @@ class LiDARModel(Engine):
         fused = e["deconv"](e["conv"](features, amax_in=ops.amax_of(features)))          # (B, sum(outs), 2H, 2W)
         return tuple(torch.split(fused, e["outs"], dim=1))
 
+    def detect(self, features, at_peaks=True):
+        """(det_rows (2, 15, 7) = (score, x, y, w, h, cos, sin) per class, pred_bev) of one frame's feature map (1, C, H, W): what
+        the frame needs of the four heads.  The box and orientation maps are read at the 2 x 15 peak pixels only, so they are not
+        made: the centre and segmentation heads run densely (the fused engine at 128 couts), lav_extract_peaks finds the peaks on the
+        heat map, and lav_heads_at_peaks evaluates the box / orientation heads at those rows in exact fp32.  at_peaks=False
+        (LAV_HEADS_AT_PEAKS=0) is the dense four-head path, the maps gathered by lav_extract_peaks."""
+        if features.shape[0] != 1:
+            raise RuntimeError("LiDARModel.detect: one frame (batch 1) expected")
+        if not at_peaks:
+            heat, size, ori, pred_bev = self.heads(features)
+            return ops.extract_peaks(heat[0], size[0], ori[0], apply_sigmoid=True), pred_bev
+        heat, pred_bev = self.heads(features, ("center_head", "seg_head"))
+        rows = ops.extract_peaks(heat[0], apply_sigmoid=True)
+        names = ("box_head", "ori_head")
+        def build():
+            hs = [getattr(self, n) for n in names]
+            if not all(isinstance(h.output_activation, nn.Identity) for h in hs):
+                raise RuntimeError("LiDARModel.detect: the box / orientation heads must have no output activation")
+            return ops.HeadsAtPeaks([(h.net[0], h.net[2], h.net[3]) for h in hs], device=features.device)
+        return self._engine_for(features.device, ("at_peaks", names), build)(features[0], rows), pred_bev
+
     def _heads_train(self, features, names):
         """Train mode: the heads' first convolutions (384 -> 64 each, lidar.py:147-161) as ONE convolution 384 -> 64*len(names)
         over the concatenated weights - the feature map is read once forward and its gradient is produced by one data-gradient

@@ -82,12 +82,14 @@ def extract_peak(heatmap, max_pool_ks: int = 7, min_score: float = 0.1, max_det:
 
 
 class InferModel(nn.Module):
-    def __init__(self, lidar_model, uniplanner, camera_x, camera_z, device=torch.device("cuda"), precision=None):
+    def __init__(self, lidar_model, uniplanner, camera_x, camera_z, device=torch.device("cuda"), precision=None, heads_at_peaks=None):
         """precision: lav_conv.precision of the eval engines this wrapper runs its modules at (default ops.frame_precision():
         LAV_CONV_F16X3 - every split-kernel convolution on two fp16 pieces, the scale handed from layer to layer; waypoints stay
         within 1e-4 of the reference, tests/test_gpu_e2e.py).  The engines are cached per precision on the modules."""
         super().__init__()
         self.precision = ops.frame_precision() if precision is None else int(precision)
+        # box / orientation heads at the peak rows only (LiDARModel.detect; default LAV_HEADS_AT_PEAKS, ops.frame_heads_at_peaks)
+        self.heads_at_peaks = ops.frame_heads_at_peaks() if heads_at_peaks is None else bool(heads_at_peaks)
         self.lidar_model = lidar_model
         self.uniplanner = uniplanner
         self.coord_converters = [CoordConverter(yaw, lidar_xyz=[0, 0, camera_z], cam_xyz=[camera_x, 0, camera_z],
@@ -113,8 +115,8 @@ class InferModel(nn.Module):
         with ops.precision(self.precision):
             canvas = lm.point_pillar_net([lidar_points], [len(lidar_points)])
             features = lm.backbone(canvas)
-            heat, size, ori, pred_bev = lm.heads(features)
-            det = self.det_decode(ops.extract_peaks(heat[0], size[0], ori[0], apply_sigmoid=True).cpu().tolist())
+            det_rows, pred_bev = lm.detect(features, at_peaks=self.heads_at_peaks)
+            det = self.det_decode(det_rows.cpu().tolist())
             ego_embd, ego_plan, ego_cast, other_cast, other_cmds = self.uniplanner.infer_all(features[0], det[1], cmd_value, nxps, amax=ops.amax_of(features))
         return ego_embd, ego_plan, ego_cast, other_cast, other_cmds, pred_bev, det
 

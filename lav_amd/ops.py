@@ -947,6 +947,12 @@ class precision:
         return False
 
 
+def frame_heads_at_peaks() -> bool:
+    """LAV_HEADS_AT_PEAKS (default 1): the frame pipelines evaluate the box / orientation heads at the peak rows only
+    (LiDARModel.detect, lav_heads_at_peaks); 0 restores the dense four-head maps gathered by lav_extract_peaks."""
+    return _os.environ.get("LAV_HEADS_AT_PEAKS", "1") != "0"
+
+
 def frame_precision() -> int:
     """What the inference pipelines run at: LAV_CONV_F16X3 unless LAV_CONV_PRECISION asks for the exact-fp32 kernels or
     LAV_INFER_PRECISION / LAV_HEADS_PRECISION (round 5's knob) say bf16x6."""
@@ -1843,17 +1849,92 @@ def stack_sweeps(fused: torch.Tensor, ring: torch.Tensor, slot: torch.Tensor, sw
     return out
 
 
-def extract_peaks(heat: torch.Tensor, size: torch.Tensor, ori: torch.Tensor, ks: int = 7, max_det: int = 15,
-                  apply_sigmoid: bool = False) -> torch.Tensor:
-    """heat (ncls,H,W), size (cs,H,W), ori (co,H,W) -> (ncls, max_det, 3+cs+co) rows (score, x, y, size.., ori..)."""
+def extract_peaks(heat: torch.Tensor, size: Optional[torch.Tensor] = None, ori: Optional[torch.Tensor] = None, ks: int = 7,
+                  max_det: int = 15, apply_sigmoid: bool = False) -> torch.Tensor:
+    """heat (ncls,H,W), size (cs,H,W), ori (co,H,W) -> (ncls, max_det, 3+cs+co) rows (score, x, y, size.., ori..).  size / ori None:
+    no gathered columns (size_c = ori_c = 0) - the (score, x, y) rows HeadsAtPeaks takes."""
     lib = _lib.load()
-    heat, size, ori = _f32c(heat, "heat"), _f32c(size, "size"), _f32c(ori, "ori")
+    heat = _f32c(heat, "heat")
+    size, ori = (None if size is None else _f32c(size, "size")), (None if ori is None else _f32c(ori, "ori"))
     ncls, H, W = heat.shape
-    if size.shape[1:] != (H, W) or ori.shape[1:] != (H, W):
+    if any(m is not None and m.shape[1:] != (H, W) for m in (size, ori)):
         raise RuntimeError("extract_peaks: size / ori maps must match the heat map")
-    out = torch.empty((ncls, max_det, 3 + size.shape[0] + ori.shape[0]), dtype=torch.float32, device=heat.device)
+    cs, co = (0 if size is None else size.shape[0]), (0 if ori is None else ori.shape[0])
+    out = torch.empty((ncls, max_det, 3 + cs + co), dtype=torch.float32, device=heat.device)
     nbytes = lib.lav_extract_peaks_workspace_bytes(ncls, H, W)
     ws = _workspace("peaks", nbytes, heat.device)
-    check(lib.lav_extract_peaks(_ptr(heat), ncls, H, W, ks, max_det, int(apply_sigmoid), _ptr(size), size.shape[0], _ptr(ori),
-                                ori.shape[0], _ptr(out), _ptr(ws), ws.numel(), _stream()), "lav_extract_peaks")
+    check(lib.lav_extract_peaks(_ptr(heat), ncls, H, W, ks, max_det, int(apply_sigmoid), _ptr(size), cs, _ptr(ori), co, _ptr(out),
+                                _ptr(ws), ws.numel(), _stream()), "lav_extract_peaks")
     return out
+
+
+class HeadsAtPeaks:
+    """Heads conv3x3(cin -> hidden <= 64) -> ReLU -> eval BatchNorm -> ConvTranspose2d(hidden -> outs <= 4, 3, 2, 1, 1) evaluated at
+    peak rows only, as ONE lav_heads_at_peaks launch: `heads` is a list of (conv, bn, deconv) modules (1 .. 4 of them).  The first
+    convolutions' weights are re-laid-out once, here, as [9 cin rounded up to 128][64] for the kernel's contiguous stream; refresh()
+    re-reads every parameter into the same buffers (captured graphs hold their addresses).  __call__(feat (cin,H,W), rows
+    (ncls,max_det,3)) -> (ncls, max_det, 3 + sum(outs))."""
+
+    def __init__(self, heads, device=None):
+        lib = _lib.load()
+        self._heads = [tuple(h) for h in heads]
+        conv0, _, ct0 = self._heads[0]
+        if not 1 <= len(self._heads) <= 4:
+            raise RuntimeError("HeadsAtPeaks: 1 .. 4 heads")
+        for conv, bn, ct in self._heads:
+            if (conv.kernel_size, conv.stride, conv.padding, conv.dilation, conv.groups, conv.in_channels) != ((3, 3), (1, 1), (1, 1), (1, 1), 1, conv0.in_channels) \
+                    or conv.bias is not None or conv.padding_mode != "zeros":
+                raise RuntimeError("HeadsAtPeaks: first layer must be Conv2d(cin, hidden, 3, 1, 1, bias=False)")
+            if (ct.kernel_size, ct.stride, ct.padding, ct.output_padding, ct.dilation, ct.groups, ct.in_channels) != \
+                    ((3, 3), (2, 2), (1, 1), (1, 1), (1, 1), 1, conv.out_channels) or bn.num_features != conv.out_channels:
+                raise RuntimeError("HeadsAtPeaks: tail must be ConvTranspose2d(hidden, outs, 3, 2, 1, 1) behind a BatchNorm2d(hidden)")
+        self._dev = device if device is not None else conv0.weight.device
+        self.cin = conv0.in_channels
+        self.hidden = [conv.out_channels for conv, _, _ in self._heads]
+        self.outs = [ct.out_channels for _, _, ct in self._heads]
+        n = [lib.lav_heads_at_peaks_packed_floats(self.cin, h) for h in self.hidden]
+        if not all(n) or max(self.outs) > 4:
+            raise RuntimeError("HeadsAtPeaks: hidden width <= 64 and at most 4 outputs per head")
+        f = dict(dtype=torch.float32, device=self._dev)
+        self.w1 = [torch.zeros((k // 64, 64), **f) for k in n]
+        self.scale = [torch.empty((h,), **f) for h in self.hidden]
+        self.shift = [torch.empty((h,), **f) for h in self.hidden]
+        self.wt = [torch.empty((h, o, 3, 3), **f) for h, o in zip(self.hidden, self.outs)]
+        self.bias = [None if ct.bias is None else torch.empty((o,), **f) for (_, _, ct), o in zip(self._heads, self.outs)]
+        self.refresh()
+        G = len(self._heads)
+        arr = lambda ts: (C.c_void_p * G)(*[_ptr(t) for t in ts])
+        self._args = (arr(self.w1), arr(self.scale), arr(self.shift), arr(self.wt), arr(self.bias), (C.c_int * G)(*self.hidden),
+                      (C.c_int * G)(*self.outs))
+
+    def refresh(self):
+        """(Re-)read the modules' parameters, in place."""
+        for g, (conv, bn, ct) in enumerate(self._heads):
+            hid = self.hidden[g]
+            w = conv.weight.detach().to(self._dev, torch.float32)                        # (hidden, cin, 3, 3) -> [ci * 9 + tap][hidden]
+            self.w1[g][:9 * self.cin, :hid].copy_(w.permute(1, 2, 3, 0).reshape(9 * self.cin, hid))
+            scale, shift = bn_fold(*[t.detach().cpu() for t in (bn.running_mean, bn.running_var, bn.weight, bn.bias)], bn.eps)
+            self.scale[g].copy_(scale.to(torch.float32))
+            self.shift[g].copy_(shift.to(torch.float32))
+            self.wt[g].copy_(ct.weight.detach())
+            if self.bias[g] is not None:
+                self.bias[g].copy_(ct.bias.detach())
+
+    def __call__(self, feat: torch.Tensor, rows: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        feat, rows = _f32c(feat, "feat"), _f32c(rows, "rows")
+        if feat.dim() != 3 or feat.shape[0] != self.cin or rows.dim() != 3 or rows.shape[2] != 3:
+            raise RuntimeError(f"heads_at_peaks: feature map (cin = {self.cin}, H, W) and rows (ncls, max_det, 3) expected")
+        ncls, max_det = rows.shape[:2]
+        shape = (ncls, max_det, 3 + sum(self.outs))
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=feat.device)
+        elif tuple(out.shape) != shape or not out.is_contiguous() or out.dtype != torch.float32:
+            raise RuntimeError(f"heads_at_peaks: output buffer must be contiguous float32 {shape}")
+        check(_lib.load().lav_heads_at_peaks(_ptr(feat), self.cin, feat.shape[1], feat.shape[2], _ptr(rows), ncls, max_det,
+                                            len(self._heads), *self._args, _ptr(out), _stream()), "lav_heads_at_peaks")
+        return out
+
+
+def heads_at_peaks(layer: HeadsAtPeaks, feat: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+    """Function form of HeadsAtPeaks.__call__ (one lav_heads_at_peaks launch)."""
+    return layer(feat, rows)
