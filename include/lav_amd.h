@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 44
+#define LAV_ABI_VERSION 45
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -1051,6 +1051,41 @@ int lav_eval_distill(const float *s_ego_plan, const float *s_ego_cast, const flo
                      const float *t_ego_cast, const float *t_ego_cmds, const float *ego_locs, const int *cmds, int batch, int iters,
                      int num_plan, const float *s_other_cast, const float *s_other_cmds, const float *t_other_cast,
                      const float *t_other_cmds, const float *other_locs, int num_others, long long *acc, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Rotated-box metrics of one evaluated frame's detections (ABI 45; eval_det_v2.py, lav_amd.train.evaluate_det): one launch of one
+ * workgroup on `stream` that ADDS integers into an int64 accumulator in HBM; nothing is copied to the host.  Specification:
+ * lav_amd.train.evaluate_det.eval_det_numpy, word for word, which has the definitions in full and the final word on the order of every
+ * operation.  The reference has no evaluator: the definitions are this project's, parity is UNPINNED.
+ *
+ * rows [2][max_det <= 32][7] = (score, x, y, w, h, cos, sin) as lav_extract_peaks / lav_heads_at_peaks leave them; locs [max_objs <= 64]
+ * [num_plan + 1][2] of which frame 0 is read, typs [max_objs] int32, the first num_objs count (both may be NULL when num_objs is 0);
+ * size_map, ori_map [2][h][w]: the loader's regression targets, from which actor g's box is read at (min(w - 1, int(px + 0.5)), iy
+ * likewise), (px, py) = (double)loc * ppm + centre, kept when inside [0, w) x [0, h).  iou_q [num_iou <= 3] = llrint(threshold 2^20) in
+ * 1 .. 2^20, range2 [num_range <= 3] = (edge ppm)^2 in squared pixels, heading_cos [num_heading <= 7] = cos(edge): HOST arrays, read
+ * before the launch.  1 <= nbins <= 1024, min_score >= 0.
+ *
+ * A box (C, w, h, c, s) is valid when all are finite, w > 0, h > 0 and c c + s s is finite and > 0; its corners are C -+ w u -+ h v with
+ * u = (s^, -c^), v = (c^, s^) the normalised direction, counter-clockwise.  iou_q(P, G) = llrint(IoU 2^20), at most 2^20, by clipping
+ * P's corners against G's four edges (Sutherland-Hodgman, at most 8 vertices); 0 where a box is invalid.  Float64, + - * /, sqrt and
+ * comparisons only.  Per class, rows with (double)score > min_score in order, four arms with their own taken sets: arm 0 takes the
+ * nearest free actor within radius_px (lav_eval_frame's rule), arm 1 + k the free actor with the largest iou_q if that is >= iou_q[k]
+ * and > 0; ties to the lowest index.  The accumulator has 135 + 16 nbins words, as the size function says (0 for nbins outside
+ * 1 .. 1024), in this order:
+ *   frames; n_gt [class][range bin]; gt_invalid [class]: in-map actors whose gathered box is invalid (they still count in n_gt);
+ *   pred_invalid [class]: rows above min_score whose box is invalid; det [arm][class][range bin][tp, fp] over (double)score > det_score,
+ *   range bin = the number of edges with d2 >= range2, d2 from the centre to the matched actor (tp) or to the row (fp);
+ *   pairs [class][range bin]: arm 0's true positives above det_score; pair_invalid [class]: those with an invalid box on either side,
+ *   which add to nothing below; sum_centre, sum_dw, sum_dh [class][range bin]: llrint(min(v, 2^32) 2^20) of sqrt(d2) / ppm, |w_p - w_g|
+ *   / ppm, |h_p - h_g| / ppm; sum_iou: iou_q; heading [class][8]: the number of edges with c^_p c^_g + s^_p s^_g < heading_cos (a NaN:
+ *   num_heading); hist [arm][class][tp, fp][min(nbins - 1, (int)(score * (float)nbins))].
+ * One wave per arm and class, one lane per actor; 64-bit LDS atomics, then one 64-bit vector atomic per counter that changed and per counted row.
+ */
+size_t lav_eval_det_words(int nbins);
+int lav_eval_det(const float *rows, int max_det, const float *locs, const int *typs, int max_objs, int num_objs, int num_plan,
+                 const float *size_map, const float *ori_map, int h, int w, double ppm, double centre_x, double centre_y, double radius_px,
+                 double min_score, double det_score, const long long *iou_q, int num_iou, const double *range2, int num_range,
+                 const double *heading_cos, int num_heading, int nbins, long long *acc, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Open-loop metrics of the agent's rule layer over one evaluated frame (ABI 42; eval_drive_v2.py, lav_amd.train.evaluate_drive): one

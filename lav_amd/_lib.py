@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LAV_AMD_LIB") or os.path.join(HERE, "liblav_amd.so")   # LAV_AMD_LIB: A/B a second build
 
-ABI_VERSION = 44
+ABI_VERSION = 45
 MAX_CAM = 4
 MAX_CAM_F64 = 8
 
@@ -175,6 +175,8 @@ SIGNATURES = {
     "lav_eval_distill": (_I, [_P] * 8 + [_I, _I, _I] + [_P] * 5 + [_I, _P, _P]),
     "lav_eval_drive_words": (_Z, [_I]),
     "lav_eval_drive": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _I] + [C.c_double] * 6 + [_I, _P, _P]),
+    "lav_eval_det_words": (_Z, [_I]),
+    "lav_eval_det": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _I] + [C.c_double] * 6 + [_P, _I, _P, _I, _P, _I, _I, _P, _P]),
     "lav_jpeg_scan_capacity": (C.c_longlong, [_I, _I, _I]),
     "lav_jpeg_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "lav_jpeg_encode": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, C.c_longlong, _P, _P, _Z, _P]),

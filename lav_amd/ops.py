@@ -7,6 +7,7 @@ current stream.  No function here has a torch/CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os as _os
 import threading as _threading
 from typing import Optional, Sequence
@@ -763,6 +764,63 @@ def eval_drive(acc: torch.Tensor, ego_plan: torch.Tensor, ego_cast: torch.Tensor
     check(_lib.load().lav_eval_drive(_ptr(ego_plan), _ptr(ego_cast), _ptr(ego_locs), T, cmd, int(bra), aim_point[cmd], _ptr(other_cast),
                                      _ptr(other_cmds), N, _ptr(locs) if G else None, _ptr(typs) if G else None, G, n, *scalars, int(nbins),
                                      _ptr(acc), _stream()), "lav_eval_drive")
+    return acc
+
+
+def eval_det_words(nbins: int = 256) -> int:
+    """Length of lav_eval_det's accumulator, 135 + 16 nbins (lav_eval_det_words; host only, no device needed)."""
+    n = int(_lib.load().lav_eval_det_words(int(nbins)))
+    if n == 0:
+        raise ValueError(f"eval_det: {nbins} score bins (1 .. 1024)")
+    return n
+
+
+@functools.lru_cache(maxsize=16)
+def _eval_det_thresholds(ppm, iou_thresholds, range_edges_m, heading_edges_deg):
+    """lav_amd.train.evaluate_det.thresholds as the three host arrays lav_eval_det reads, computed once per setting."""
+    from .train.evaluate_det import thresholds
+    L, range2, hcos = thresholds(ppm, iou_thresholds, range_edges_m, heading_edges_deg)
+    return ((C.c_longlong * max(1, len(L)))(*[int(v) for v in L]), len(L), (C.c_double * max(1, len(range2)))(*[float(v) for v in range2]), len(range2),
+            (C.c_double * max(1, len(hcos)))(*[float(v) for v in hcos]), len(hcos))
+
+
+def eval_det(acc: torch.Tensor, rows: torch.Tensor, locs: torch.Tensor, typs: torch.Tensor, n: int, size_map: torch.Tensor, ori_map: torch.Tensor,
+             *, ppm: float, centre, radius_px: float, iou_thresholds=(0.3, 0.5, 0.7), range_edges_m=(15, 30, 50),
+             heading_edges_deg=(5, 10, 20, 45, 90, 135, 175), min_score: float = 0.1, det_score: float = 0.2, nbins: int = 256) -> torch.Tensor:
+    """The rotated-box metrics of one frame's detections, ADDED into `acc` (int64, ops.eval_det_words(nbins) words, in HBM) by one launch
+    on the current stream (lav_eval_det); nothing comes back to the host.  rows (2, D <= 32, 7) float32 = (score, x, y, w, h, cos, sin)
+    of extract_peaks / LiDARModel.detect, read where they are; locs (G <= 64, T + 1, 2) float32, typs (G,) int32 and n: the ground truth
+    as the loaders return it; size_map, ori_map (2, H, W) float32: the loaders' regression targets, from which the ground-truth boxes
+    are read.  centre = the ego pixel (x, y).  At most 3 IoU thresholds in (0, 1], 3 ascending range edges (metres) and 7 ascending
+    heading edges (degrees); they reach the kernel as lav_amd.train.evaluate_det.thresholds makes them.  Word for word
+    lav_amd.train.evaluate_det.eval_det_numpy, which has the definitions and names the accumulator's slices (DetLayout).  Wrong shapes,
+    dtypes, devices or values raise ValueError before anything is launched."""
+    _eval_section("eval_det", acc, eval_det_words(nbins), "acc")
+    need = _eval_tensor("eval_det", "evaluate_det.eval_det_numpy", acc, copy=True)
+    rows = need("rows", rows, torch.float32, (2, None, 7))
+    D = rows.shape[1]
+    if not 1 <= D <= 32:
+        raise ValueError(f"eval_det: {D} rows per class (1 .. 32)")
+    locs = need("locs", locs, torch.float32, (None, None, 2))
+    G, T = locs.shape[0], locs.shape[1] - 1
+    if G > 64 or T < 0:
+        raise ValueError(f"eval_det: locs {tuple(locs.shape)}: at most 64 actors, at least their position")
+    typs = need("typs", typs, torch.int32, (G,))
+    n = int(n)
+    if not 0 <= n <= G:
+        raise ValueError(f"eval_det: n = {n} of {G} actors")
+    size_map = need("size_map", size_map, torch.float32, (2, None, None))
+    H, W = size_map.shape[1:]
+    if not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise ValueError(f"eval_det: maps of {H} x {W} pixels")
+    ori_map = need("ori_map", ori_map, torch.float32, (2, H, W))
+    scalars = [float(ppm), float(centre[0]), float(centre[1]), float(radius_px), float(min_score), float(det_score)]
+    if not all(np.isfinite(scalars)) or not 0 < scalars[0] <= 1e6 or scalars[3] < 0 or scalars[4] < 0:
+        raise ValueError("eval_det: scalars must be finite, pixels per metre positive, the radius and min_score not negative")
+    L, nl, range2, nr, hcos, nh = _eval_det_thresholds(scalars[0], tuple(float(t) for t in iou_thresholds), tuple(float(e) for e in range_edges_m),
+                                                       tuple(float(e) for e in heading_edges_deg))
+    check(_lib.load().lav_eval_det(_ptr(rows), D, _ptr(locs) if G else None, _ptr(typs) if G else None, G, n, T, _ptr(size_map), _ptr(ori_map), H, W,
+                                   *scalars, L, nl, range2, nr, hcos, nh, int(nbins), _ptr(acc), _stream()), "lav_eval_det")
     return acc
 
 

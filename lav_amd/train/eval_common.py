@@ -1,6 +1,6 @@
-"""What the evaluation tools share (eval_full_v2, eval_seg, eval_bra_v2, eval_bev_v2, eval_drive_v2, eval_distill_v2): the layout of an int64
+"""What the evaluation tools share (eval_full_v2, eval_seg, eval_bra_v2, eval_bev_v2, eval_drive_v2, eval_distill_v2, eval_det_v2): the layout of an int64
 accumulator, the evaluator base, the checkpoint rule and the command-line driver.  evaluate.py, evaluate_camera.py, evaluate_bev.py,
-evaluate_drive.py and evaluate_distill.py keep what is
+evaluate_drive.py, evaluate_distill.py and evaluate_det.py keep what is
 their own: the metric definitions, the NumPy specification, the summaries, the model's upload / frame / batch code and one description
 of their command line (run_cli's `tool`)."""
 from __future__ import annotations
