@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 45
+#define LAV_ABI_VERSION 46
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -1150,6 +1150,74 @@ size_t lav_jpeg_workspace_bytes(int n, int h, int w, int restart_mcus);
 int lav_jpeg_encode(const unsigned char *frames, int n, int h, int w, int row_stride, const int *quality_tables, int restart_mcus,
                     unsigned char *scans_out, long long scan_stride, int *lengths_out, void *workspace, size_t workspace_bytes,
                     void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Multi-tensor gradient statistics and a guarded Adam step (ABI 46; lav_amd.train.optim.FusedAdam, the trainers' --fused-optim).
+ * Specification: lav_amd.train.optim.fused_adam_numpy, equal in every stored bit; the float64 sum of squares alone is pinned by a
+ * bound (n * 2^-53 relative), its order of summation is the library's.
+ *
+ * The work is cut into chunks of lav_optim_chunk() elements.  Every table lives in DEVICE memory and is only read:
+ * table  [ntensors] rows in chunk order: p, g, m, v float32, dense, 4-byte aligned, numel >= 1 elements each; lr, beta1, beta2, eps of
+ *        this tensor; `state`, the index of its words in `state` (no two rows of a table share one); `chunk0`, the chunks of the rows
+ *        before it (row 0: 0).  total_chunks = the sum of ceil(numel / chunk) over the rows.
+ * watch  [nwatch] rows of read-only float32 buffers that are scanned for values that are not finite (BatchNorm's running statistics);
+ *        chunk0 and watch_chunks as above.  May be null with nwatch = 0.
+ * state  per tensor: step (applied steps), beta1_power = beta1^step and beta2_power = beta2^step as running products in float64 (1
+ *        before the first step), and the two float32 factors of the update, step_size = lr / (1 - beta1_power) and inv_sqrt_bc2 =
+ *        1 / sqrt(1 - beta2_power), both computed in float64 and rounded once.
+ * global applied / skipped steps since the caller zeroed them; of the last call: nonfinite (gradient elements that are NaN or +-Inf),
+ *        sumsq (of the finite ones), clip = float32(min(1, max_norm / (sqrt(sumsq) + 1e-6))) (1 for max_norm <= 0: no limit), apply =
+ *        (nonfinite == 0), watch_nonfinite.
+ *
+ * lav_optim_adam_step: three launches on `stream` (statistics per chunk; one workgroup that reduces them in a fixed order, decides and
+ * advances the words of every tensor of the table; the update per chunk).  With apply set, in float32, every operation rounded on its own
+ * (beta, 1 - beta and eps are the row's float64 values rounded once):
+ *     g' = g * clip;  m = beta1 m + (1 - beta1) g';  v = beta2 v + ((1 - beta2) g') g';  p = p - step_size (m / (sqrt(v) inv_sqrt_bc2 + eps))
+ * Without it nothing is stored but `skipped` + 1 and the statistics words: p, m, v and the tensors' words keep every bit.
+ * lav_optim_grad_stats: the first two launches, writing the five statistics words of `global` only.
+ * No host synchronisation, no float atomic, no dependency between workgroups of one launch; identical inputs give identical bits.
+ * workspace: DEVICE, 256-byte aligned, lav_optim_workspace_bytes(total_chunks, watch_chunks) bytes (0 for counts the calls would
+ * refuse); needs no initialisation.
+ */
+typedef struct lav_optim_tensor {
+    float *p;
+    const float *g;
+    float *m;
+    float *v;
+    long long numel;
+    double lr, beta1, beta2, eps;
+    int state;
+    int chunk0;
+} lav_optim_tensor;
+
+typedef struct lav_optim_watch {
+    const float *data;
+    long long numel;
+    int chunk0;
+    int reserved;
+} lav_optim_watch;
+
+typedef struct lav_optim_state {
+    long long step;
+    double beta1_power, beta2_power;
+    float step_size, inv_sqrt_bc2;
+} lav_optim_state;
+
+typedef struct lav_optim_global {
+    long long applied, skipped, nonfinite;
+    double sumsq;
+    float clip;
+    int apply;
+    long long watch_nonfinite;
+} lav_optim_global;
+
+int lav_optim_chunk(void);
+size_t lav_optim_workspace_bytes(long long total_chunks, long long watch_chunks);
+int lav_optim_grad_stats(const lav_optim_tensor *table, int ntensors, int total_chunks, const lav_optim_watch *watch, int nwatch,
+                         int watch_chunks, lav_optim_global *global, double max_norm, void *workspace, size_t workspace_bytes, void *stream);
+int lav_optim_adam_step(const lav_optim_tensor *table, int ntensors, int total_chunks, const lav_optim_watch *watch, int nwatch,
+                        int watch_chunks, lav_optim_state *state, lav_optim_global *global, double max_norm, void *workspace,
+                        size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

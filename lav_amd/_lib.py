@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LAV_AMD_LIB") or os.path.join(HERE, "liblav_amd.so")   # LAV_AMD_LIB: A/B a second build
 
-ABI_VERSION = 45
+ABI_VERSION = 46
 MAX_CAM = 4
 MAX_CAM_F64 = 8
 
@@ -180,6 +180,10 @@ SIGNATURES = {
     "lav_jpeg_scan_capacity": (C.c_longlong, [_I, _I, _I]),
     "lav_jpeg_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "lav_jpeg_encode": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, C.c_longlong, _P, _P, _Z, _P]),
+    "lav_optim_chunk": (_I, []),
+    "lav_optim_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
+    "lav_optim_grad_stats": (_I, [_P, _I, _I, _P, _I, _I, _P, C.c_double, _P, _Z, _P]),
+    "lav_optim_adam_step": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, C.c_double, _P, _Z, _P]),
 }
 
 _lib = None

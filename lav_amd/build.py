@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblav_amd.so")
-SOURCES = ["misc.hip", "pillar.hip", "paint.hip", "paint_frames.hip", "gru.hip", "gru_seq.hip", "conv.hip", "conv_f16.hip", "conv_pair.hip", "conv_run.hip", "conv_tile.hip", "deconv.hip", "crop.hip", "frame.hip", "heads_peaks.hip", "attn.hip", "bn_train.hip", "conv_wgrad.hip", "upconv.hip", "conv_pair_train.hip", "augment.hip", "bev_stack.hip", "debug_view.hip", "log_view.hip", "eval_metrics.hip", "eval_camera.hip", "eval_plans.hip", "eval_drive.hip", "eval_distill.hip", "eval_det.hip", "jpeg.hip"]
+SOURCES = ["misc.hip", "pillar.hip", "paint.hip", "paint_frames.hip", "gru.hip", "gru_seq.hip", "conv.hip", "conv_f16.hip", "conv_pair.hip", "conv_run.hip", "conv_tile.hip", "deconv.hip", "crop.hip", "frame.hip", "heads_peaks.hip", "attn.hip", "bn_train.hip", "conv_wgrad.hip", "upconv.hip", "conv_pair_train.hip", "augment.hip", "bev_stack.hip", "debug_view.hip", "log_view.hip", "eval_metrics.hip", "eval_camera.hip", "eval_plans.hip", "eval_drive.hip", "eval_distill.hip", "eval_det.hip", "jpeg.hip", "optim.hip"]
 # Parity-critical arithmetic (float32 cell ids, decoration, camera projection; bev_stack.hip's float64 inverse maps) must round every multiply and
 # add separately, like the oracle: these translation units are compiled with FMA contraction off (the header
 # helpers __fadd_rn/__fmul_rn are plain operators that clang would otherwise fuse after inlining).
@@ -36,7 +36,9 @@ EXTRA_FLAGS = {"pillar.hip": ["-ffp-contract=off"], "paint.hip": ["-ffp-contract
                # eval_det.hip: box corners, clipping and areas in float64, every product and sum rounded as Python rounds it
                "eval_det.hip": ["-ffp-contract=off"],
                # eval_distill.hip: the same distances, between two networks' outputs
-               "eval_distill.hip": ["-ffp-contract=off"]}
+               "eval_distill.hip": ["-ffp-contract=off"],
+               # optim.hip: the Adam update in float32 and its words in float64 as NumPy rounds them, one rounding per operation
+               "optim.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]}
 # -fno-slp-vectorize (round 5): the SLP vectoriser turns pairs of scalar float operations into packed fp32 instructions
 # (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) and selects halves of register pairs with op_sel.  On gfx950 a packed fp32 instruction
 # whose op_sel bit is set (low result from the HIGH register of a source pair) returns wrong values in lanes 48-63 when waves of a

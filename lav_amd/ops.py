@@ -1777,6 +1777,45 @@ def nonfinite_count(tensors, counter: torch.Tensor) -> None:
                                           _ptr(counter), _stream()), "lav_nonfinite_count")
 
 
+def _optim_args(op, table, ntensors, chunks, watch, nwatch, watch_chunks, words):
+    """The checked arguments the two lav_optim_* calls share: uint8 tables in HBM long enough for their row counts, the workspace."""
+    from .train import optim as O
+    dev = words["global"].device
+    sizes = [(table, ntensors * O.TENSOR_DTYPE.itemsize, "table"), (watch, nwatch * O.WATCH_DTYPE.itemsize, "watch"),
+             (words["global"], O.GLOBAL_DTYPE.itemsize, "global")]
+    if "state" in words:        # (a row per tensor of the table at the least; the rows' own indices are the caller's)
+        sizes.append((words["state"], ntensors * O.STATE_DTYPE.itemsize, "state"))
+    for t, nbytes, name in sizes:
+        if t is None and nbytes == 0:
+            continue
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() >= nbytes
+                and (t.numel() == 0 or t.data_ptr() % 8 == 0)):
+            raise ValueError(f"{op}: {name} must be a contiguous, 8-byte aligned uint8 tensor of at least {nbytes} bytes in HBM, on one device")
+    lib = _lib.load()
+    nbytes = int(lib.lav_optim_workspace_bytes(int(chunks), int(watch_chunks)))
+    if nbytes == 0:
+        raise ValueError(f"{op}: {chunks} + {watch_chunks} chunks")
+    return lib, _workspace(("optim",), nbytes, dev), nbytes
+
+
+def optim_grad_stats(table, ntensors, chunks, watch, nwatch, watch_chunks, glob, max_norm=None) -> None:
+    """The statistics half of optim_adam_step alone (lav_optim_grad_stats: two launches on the current stream): writes nonfinite, sumsq,
+    clip, apply and watch_nonfinite of `glob`; the counters, the tensors and their words are not touched."""
+    lib, ws, nbytes = _optim_args("optim_grad_stats", table, ntensors, chunks, watch, nwatch, watch_chunks, dict(**{"global": glob}))
+    check(lib.lav_optim_grad_stats(_ptr(table), int(ntensors), int(chunks), _ptr(watch), int(nwatch), int(watch_chunks), _ptr(glob),
+                                   float(max_norm or 0.0), _ptr(ws), nbytes, _stream()), "lav_optim_grad_stats")
+
+
+def optim_adam_step(table, ntensors, chunks, watch, nwatch, watch_chunks, state, glob, max_norm=None) -> None:
+    """One guarded Adam step over every tensor of a descriptor table (lav_optim_adam_step: three launches on the current stream, no
+    synchronisation).  table / watch / state / glob: uint8 tensors in HBM holding rows of lav_amd.train.optim's TENSOR_DTYPE /
+    WATCH_DTYPE / STATE_DTYPE / GLOBAL_DTYPE (include/lav_amd.h's structs); chunks / watch_chunks: what fill_chunks returned for them.
+    The library trusts the rows: lav_amd.train.optim.FusedAdam builds them from live tensors.  Equal to fused_adam_numpy in every bit."""
+    lib, ws, nbytes = _optim_args("optim_adam_step", table, ntensors, chunks, watch, nwatch, watch_chunks, dict(state=state, **{"global": glob}))
+    check(lib.lav_optim_adam_step(_ptr(table), int(ntensors), int(chunks), _ptr(watch), int(nwatch), int(watch_chunks), _ptr(state), _ptr(glob),
+                                  float(max_norm or 0.0), _ptr(ws), nbytes, _stream()), "lav_optim_adam_step")
+
+
 def copy_many(pairs, block=None) -> None:
     """[(dst, src), ...] device tensors of equal shape into their destinations in at most two launches: contiguous same-dtype
     16-byte-aligned pairs through lav_copy_many (16-byte words), strided / uint8 sources of up to four dimensions into contiguous

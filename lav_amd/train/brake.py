@@ -14,10 +14,11 @@ from __future__ import annotations
 
 import torch
 import torch.nn.functional as F
-from torch import nn, optim
+from torch import nn
 
 from .. import synth
 from .lav import _ddp
+from .optim import make_adam
 
 BRA_LABELS = [4, 10, 18]        # lav_privileged_v2.py:30 (hard-coded there; not config_v2's seg_channels)
 SEG_SCALE = 4                   # the seg head's logits are at stride 4 of the image (F.interpolate(scale_factor=4))
@@ -85,7 +86,7 @@ class BrakeTrainer:
         # becoming ready (Adam skips a parameter without a gradient either way: the steps are the reference's)
         for p in self.bra_model.conv_backbone.fc.parameters():
             p.requires_grad_(False)
-        self.bra_optim = optim.Adam(self.bra_model.parameters(), lr=cfg.lr)     # lav_privileged_v2.py:46, no scheduler
+        self.bra_optim = make_adam(self.bra_model.parameters(), cfg, [self.bra_model])     # lav_privileged_v2.py:46 (Adam), no scheduler
         self.bra_ddp = _ddp(_BrakeStep(self.bra_model), self.device)
 
     def state_dict(self, model_name="bra"):

@@ -9,7 +9,7 @@ from typing import List
 
 import torch
 import torch.distributed as dist
-from torch import nn, optim
+from torch import nn
 from torch.optim.lr_scheduler import StepLR
 
 from .. import synth
@@ -17,6 +17,7 @@ from ..bev_planner import BEVPlanner
 from ..lidar import LiDARModel
 from ..uniplanner import UniPlanner
 from .losses import DetLoss, bev_losses, build_seg_mask, lidar_losses
+from .optim import make_adam
 
 
 @dataclass
@@ -56,6 +57,8 @@ class TrainConfig:
     log_inference: bool = True     # the reference runs one eval-mode inference of sample 0 per step, for its logs only
     log_every: int = 100           # (lav_final_v2.py:228-236; logged every --num-per-log = 100 steps): here it runs on those steps
     seed: int = 2021
+    fused_optim: bool = False      # --fused-optim: lav_amd.train.optim.FusedAdam (guarded, one update launch) where optim.Adam stands
+    max_grad_norm: float = 0.0     # --max-grad-norm X > 0: clip the global gradient norm inside that step (implies fused_optim)
 
 
 class _Student(nn.Module):
@@ -107,7 +110,7 @@ class LAV:
             self.seg_model = RGBSegmentationModel(cfg.seg_channels)
             self.seg_model.load_state_dict(ck.get("seg") or synth.seeded_state_dict(self.seg_model, prefix="seg."))
             self.seg_model.to(self.device).train()
-            self.seg_optim = optim.Adam(self.seg_model.parameters(), lr=cfg.lr)
+            self.seg_optim = make_adam(self.seg_model.parameters(), cfg, [self.seg_model])
             self.seg_ddp = _ddp(self.seg_model, self.device)
             return
         y_off = 1 + cfg.min_x / ((cfg.max_x - cfg.min_x) / 2)
@@ -127,7 +130,7 @@ class LAV:
             p.requires_grad_(False)
         if what == "bev":
             self.bev_planner.train()
-            self.bev_optim = optim.Adam([p for p in self.bev_planner.parameters() if p.requires_grad], lr=cfg.lr)
+            self.bev_optim = make_adam([p for p in self.bev_planner.parameters() if p.requires_grad], cfg, [self.bev_planner])
             self.bev_scheduler = StepLR(self.bev_optim, step_size=32, gamma=0.5)
             self.bev_ddp = _ddp(self.bev_planner, self.device)
             return
@@ -163,7 +166,7 @@ class LAV:
             params += list(self.lidar_model.parameters())
         self.student = _Student(self.lidar_model, self.uniplanner).to(self.device).train()
         self.bev_planner.eval()
-        self.lidar_optim = optim.Adam(params, lr=cfg.lr)
+        self.lidar_optim = make_adam(params, cfg, trainable + ([] if cfg.motion_only else [self.lidar_model]))
         self.lidar_scheduler = StepLR(self.lidar_optim, step_size=4, gamma=0.5)
         self.det_criterion = DetLoss()
         self.seg_mask = build_seg_mask(h=H, w=W, cx=self.bev_center[0], cy=self.bev_center[1]).to(self.device)

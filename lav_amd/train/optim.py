@@ -1,0 +1,321 @@
+"""A guarded, fused Adam step for the trainers (--fused-optim): `fused_adam_numpy`, the specification, and `FusedAdam`, a
+torch.optim.Optimizer over liblav_amd's lav_optim_adam_step (csrc/optim.hip, include/lav_amd.h) with the specification as its CPU path.
+
+One step reads every gradient once for two statistics - how many elements are NaN or +-Inf, and the float64 sum of the squares of the
+others - and decides: with a single element that is not finite the step is SKIPPED (nothing is stored but a counter), otherwise it is
+APPLIED, clipped to `max_norm` by clip_grad_norm_'s factor when one is set:
+
+    clip         = float32(min(1, max_norm / (sqrt(sumsq) + 1e-6)))                 (1 without a limit)
+    per tensor, float64:  step += 1;  beta1_power *= beta1;  beta2_power *= beta2
+                 step_size    = float32(lr / (1 - beta1_power))
+                 inv_sqrt_bc2 = float32(1 / sqrt(1 - beta2_power))
+    per element, float32, every operation rounded on its own (the constants beta and 1 - beta are float64 values rounded once:
+    float32(1) - float32(0.999) is 1.3e-5 away from 0.001, float32(1 - 0.999) is not):
+                 g' = g * clip
+                 m  = beta1 * m + (1 - beta1) * g'
+                 v  = beta2 * v + ((1 - beta2) * g') * g'
+                 p  = p - step_size * (m / (sqrt(v) * inv_sqrt_bc2 + eps))
+
+Running products stand where torch has beta ** step, so that host and device agree bit for bit; steps are counted per tensor, as torch
+counts them (a parameter without a gradient is left out of that step and keeps its own count).  The words are laid out as the C ABI
+lays them out (TENSOR_DTYPE ... GLOBAL_DTYPE = lav_optim_tensor ... lav_optim_global)."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+from torch.optim import Optimizer
+
+TENSOR_DTYPE = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("numel", "<i8"), ("lr", "<f8"), ("beta1", "<f8"),
+                         ("beta2", "<f8"), ("eps", "<f8"), ("state", "<i4"), ("chunk0", "<i4")])
+WATCH_DTYPE = np.dtype([("data", "<u8"), ("numel", "<i8"), ("chunk0", "<i4"), ("reserved", "<i4")])
+STATE_DTYPE = np.dtype([("step", "<i8"), ("beta1_power", "<f8"), ("beta2_power", "<f8"), ("step_size", "<f4"), ("inv_sqrt_bc2", "<f4")])
+GLOBAL_DTYPE = np.dtype([("applied", "<i8"), ("skipped", "<i8"), ("nonfinite", "<i8"), ("sumsq", "<f8"), ("clip", "<f4"), ("apply", "<i4"),
+                         ("watch_nonfinite", "<i8")])
+assert (TENSOR_DTYPE.itemsize, WATCH_DTYPE.itemsize, STATE_DTYPE.itemsize, GLOBAL_DTYPE.itemsize) == (80, 24, 32, 48)
+
+
+def new_state(n):
+    """The words of n tensors before their first step: step 0, both powers 1."""
+    st = np.zeros(n, STATE_DTYPE)
+    st["beta1_power"] = 1.0
+    st["beta2_power"] = 1.0
+    return st
+
+
+def chunk_length():
+    """Elements per workgroup of the device kernels (lav_optim_chunk)."""
+    from .. import _lib
+    return int(_lib.load().lav_optim_chunk())
+
+
+def fill_chunks(rows, chunk):
+    """rows["chunk0"] from rows["numel"]; returns the chunks in all."""
+    n = (rows["numel"] + chunk - 1) // chunk
+    if len(rows) and n.min() < 1:
+        raise ValueError("a row of the table has no element")
+    total = int(n.sum())
+    if total > 0x7FFFFFFF:
+        raise ValueError(f"{total} chunks")
+    rows["chunk0"] = np.cumsum(n) - n
+    return total
+
+
+def fused_adam_numpy(tensors, state, glob, max_norm=None, watch=(), sumsq=None):
+    """The specification of one step (see the module's text).  tensors: one dict per tensor of the step with p, g, m, v (1-D float32
+    arrays; p, m, v are updated in place), lr, beta1, beta2, eps and `state`, its index in `state` (a STATE_DTYPE array, updated in
+    place); glob: a GLOBAL_DTYPE array of one element; watch: float32 arrays that are only scanned; sumsq: taken in place of this
+    function's own float64 sum of squares (whose order is NumPy's) - for a comparison in which the clip factor is in play."""
+    g_all = [np.asarray(t["g"]) for t in tensors]
+    if any(g.dtype != np.float32 for g in g_all):
+        raise TypeError("fused_adam_numpy: float32 gradients")
+    bad = 0
+    own = 0.0
+    for g in g_all:
+        fin = np.isfinite(g)
+        bad += int(g.size - np.count_nonzero(fin))
+        own += float(np.sum(np.square(g[fin].astype(np.float64)), dtype=np.float64))
+    total = np.float64(own if sumsq is None else sumsq)
+    clip = np.float32(1)
+    if max_norm is not None and max_norm > 0:
+        clip = np.float32(min(np.float64(1), np.float64(max_norm) / (np.sqrt(total) + np.float64(1e-6))))
+    w = glob[0] if getattr(glob, "ndim", 0) else glob
+    w["nonfinite"], w["sumsq"], w["clip"], w["apply"] = bad, total, clip, int(bad == 0)
+    w["watch_nonfinite"] = sum(int(b.size - np.count_nonzero(np.isfinite(b))) for b in (np.asarray(b) for b in watch))
+    if bad:
+        w["skipped"] += 1
+        return
+    w["applied"] += 1
+    one = np.float64(1)
+    with np.errstate(all="ignore"):
+        for t, g in zip(tensors, g_all):
+            st = state[t["state"]:t["state"] + 1]
+            b1p = st["beta1_power"][0] * np.float64(t["beta1"])
+            b2p = st["beta2_power"][0] * np.float64(t["beta2"])
+            st["step"] += 1
+            st["beta1_power"], st["beta2_power"] = b1p, b2p
+            step_size = np.float32(np.float64(t["lr"]) / (one - b1p))
+            inv = np.float32(one / np.sqrt(one - b2p))
+            st["step_size"], st["inv_sqrt_bc2"] = step_size, inv
+            beta1, beta2, eps = np.float32(t["beta1"]), np.float32(t["beta2"]), np.float32(t["eps"])
+            om1, om2 = np.float32(one - np.float64(t["beta1"])), np.float32(one - np.float64(t["beta2"]))
+            p, m, v = t["p"], t["m"], t["v"]
+            gs = g * clip
+            m[...] = beta1 * m + om1 * gs
+            v[...] = beta2 * v + (om2 * gs) * gs
+            p[...] = p - step_size * (m / (np.sqrt(v) * inv + eps))
+
+
+_ADAM_DEFAULTS = dict(weight_decay=0.0, amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
+                      decoupled_weight_decay=False)      # torch.optim.Adam's other group keys: a state_dict moves between the two classes
+
+
+class FusedAdam(Optimizer):
+    """Adam (torch.optim.Adam's defaults, no weight decay, no amsgrad) whose step is the module's specification: on cuda parameters
+    three launches of liblav_amd over all of them (lav_optim_adam_step), on CPU parameters fused_adam_numpy.  max_grad_norm: clip the
+    global gradient norm (clip_grad_norm_'s factor) inside the same step; watch: float32 buffers scanned for values that are not finite
+    by the same launch (BatchNorm's running statistics).  step() never waits for the device; health() does, for six words.
+    state_dict() has torch.optim.Adam's layout (step, exp_avg, exp_avg_sq per parameter) plus beta1_power / beta2_power, Python floats
+    (float64: load_state_dict casts tensors to the parameter's dtype, and leaves numbers alone); a torch.optim.Adam state loads into it
+    (a missing power is beta ** step) and its state loads into torch.optim.Adam."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, maximize=False, max_grad_norm=None,
+                 watch=()):
+        if not 0.0 <= lr or not 0.0 <= eps or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"FusedAdam: lr {lr}, eps {eps}, betas {betas}")
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError(f"FusedAdam: max_grad_norm {max_grad_norm} (a positive norm, or None)")
+        defaults = dict(_ADAM_DEFAULTS, lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize)
+        super().__init__(params, defaults)
+        self.max_grad_norm = max_grad_norm
+        self.watch = tuple(watch)
+        for b in self.watch:
+            if not (isinstance(b, torch.Tensor) and b.dtype == torch.float32 and b.layout == torch.strided and b.is_contiguous()):
+                raise TypeError("FusedAdam: watch holds dense float32 tensors")
+        self._check()
+        self._words = None          # STATE_DTYPE rows, one per parameter in group order: a uint8 tensor on the parameters' device
+        self._global = None         # GLOBAL_DTYPE, there too
+        self._key = self._table = self._watch_table = self._host = None
+        self._counts = (0, 0, 0, 0)
+
+    # ------------------------------------------------------------------------------------------------------------
+    def _params(self):
+        return [p for group in self.param_groups for p in group["params"]]
+
+    def _check(self):
+        for group in self.param_groups:
+            for k in ("amsgrad", "maximize"):
+                if group.get(k):
+                    raise ValueError(f"FusedAdam: {k} is not supported")
+            if group.get("weight_decay"):
+                raise ValueError(f"FusedAdam: weight_decay {group['weight_decay']} is not supported (0 only)")
+            for p in group["params"]:
+                if p.dtype != torch.float32:
+                    raise TypeError(f"FusedAdam: float32 parameters only, got {p.dtype}")
+                if p.layout != torch.strided or not p.is_contiguous():
+                    raise ValueError("FusedAdam: dense (contiguous, strided) parameters only")
+        devs = {p.device for p in self._params()}
+        if len(devs) > 1:
+            raise ValueError(f"FusedAdam: parameters on one device only, got {sorted(map(str, devs))}")
+        return next(iter(devs))
+
+    def _ensure_words(self, device):
+        n = len(self._params())
+        if self._words is not None and self._words.numel() == n * STATE_DTYPE.itemsize and self._words.device == device:
+            return
+        self._words = torch.from_numpy(self._state_rows().view(np.uint8)).to(device)
+        if self._global is None or self._global.device != device:
+            self._global = torch.zeros(GLOBAL_DTYPE.itemsize, dtype=torch.uint8, device=device)
+        self._key = None
+
+    def _state_rows(self):
+        """STATE_DTYPE rows from self.state (a parameter without state: step 0)."""
+        params = self._params()
+        rows = new_state(len(params))
+        i = 0
+        for group in self.param_groups:
+            beta1, beta2 = group["betas"]
+            for p in group["params"]:
+                st = self.state.get(p)
+                if st and "step" in st:
+                    step = int(round(float(st["step"])))
+                    b1p = float(st["beta1_power"]) if "beta1_power" in st else float(beta1) ** step
+                    b2p = float(st["beta2_power"]) if "beta2_power" in st else float(beta2) ** step
+                    rows[i] = (step, b1p, b2p, 0.0, 0.0)
+                    if step > 0:
+                        rows[i]["step_size"] = np.float32(np.float64(group["lr"]) / (np.float64(1) - np.float64(b1p)))
+                        rows[i]["inv_sqrt_bc2"] = np.float32(np.float64(1) / np.sqrt(np.float64(1) - np.float64(b2p)))
+                i += 1
+        return rows
+
+    def _rows_host(self):
+        return self._words.cpu().numpy().view(STATE_DTYPE)
+
+    def _pull(self):
+        """The device's words into self.state (one device -> host read)."""
+        if self._words is None:
+            return
+        rows = self._rows_host()
+        for i, p in enumerate(self._params()):
+            st = self.state.get(p)
+            if st:
+                st["step"] = torch.tensor(float(rows[i]["step"]), dtype=torch.float32)
+                st["beta1_power"], st["beta2_power"] = float(rows[i]["beta1_power"]), float(rows[i]["beta2_power"])
+
+    def state_dict(self):
+        self._pull()
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        device = self._check()
+        self._words = None
+        self._ensure_words(device)
+
+    def add_param_group(self, group):
+        super().add_param_group(group)
+        if getattr(self, "_words", None) is not None:
+            self._pull()
+            self._words = None
+
+    def health(self):
+        """The global words: applied / skipped steps of this object, and of the last step `nonfinite` gradient elements, `sumsq` and
+        `grad_norm` = sqrt(sumsq) of the finite ones, `clip`, `apply`, `watch_nonfinite`.  One small device -> host read."""
+        if self._global is None:
+            w = np.zeros(1, GLOBAL_DTYPE)[0]
+        else:
+            w = self._global.cpu().numpy().view(GLOBAL_DTYPE)[0]
+        out = {k: (float(w[k]) if k in ("sumsq", "clip") else int(w[k])) for k in GLOBAL_DTYPE.names}
+        out["grad_norm"] = math.sqrt(out["sumsq"])
+        return out
+
+    # ------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        device = self._check()
+        self._ensure_words(device)
+        used, grads, key, i = [], [], [], 0
+        for group in self.param_groups:
+            lr, (beta1, beta2), eps = float(group["lr"]), group["betas"], float(group["eps"])
+            for p in group["params"]:
+                g = p.grad
+                if g is not None:
+                    if g.is_sparse or g.dtype != torch.float32 or g.device != p.device:
+                        raise ValueError("FusedAdam: dense float32 gradients on the parameter's device only")
+                    if not g.is_contiguous():
+                        g = g.contiguous()
+                    st = self.state[p]
+                    if "exp_avg" not in st:
+                        st.setdefault("step", torch.tensor(0.0, dtype=torch.float32))
+                        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    m, v = st["exp_avg"], st["exp_avg_sq"]
+                    used.append(p)
+                    grads.append(g)         # (alive until the launches are enqueued)
+                    key.append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, float(beta1), float(beta2), eps, i))
+                i += 1
+        key = [row for row in key if row[4] > 0]
+        wkey = [(b.data_ptr(), b.numel()) for b in self.watch if b.numel() > 0]
+        if device.type == "cuda":
+            self._step_device(device, key, wkey)
+        else:
+            self._step_host(used, grads, key)
+        if used:    # a write through a raw pointer moves no version counter, and caches are keyed on it (lav_amd.rgb)
+            torch.autograd.graph.increment_version(used)
+        return loss
+
+    def _step_host(self, used, grads, key):
+        rows = self._words.numpy().view(STATE_DTYPE)
+        glob = self._global.numpy().view(GLOBAL_DTYPE)
+        tensors = []
+        for p, g in zip(used, grads):
+            if p.numel() == 0:
+                continue
+            st = self.state[p]
+            _, _, _, _, _, lr, beta1, beta2, eps, i = key[len(tensors)]
+            tensors.append(dict(p=p.detach().view(-1).numpy(), g=g.detach().view(-1).numpy(), m=st["exp_avg"].view(-1).numpy(),
+                                v=st["exp_avg_sq"].view(-1).numpy(), lr=lr, beta1=beta1, beta2=beta2, eps=eps, state=i))
+        fused_adam_numpy(tensors, rows, glob, self.max_grad_norm, [b.detach().view(-1).numpy() for b in self.watch if b.numel() > 0])
+
+    def _step_device(self, device, key, wkey):
+        from .. import ops
+        full = (tuple(key), tuple(wkey))
+        if full != self._key:
+            # a fresh pinned buffer and a fresh device table per change: the copy is ordered on the stream behind the launches that
+            # read the table it replaces, and a source is never rewritten
+            chunk = chunk_length()
+            table = np.zeros(len(key), TENSOR_DTYPE)
+            for r, row in enumerate(key):
+                table[r] = row + (0,)
+            watch = np.zeros(len(wkey), WATCH_DTYPE)
+            for r, (ptr, n) in enumerate(wkey):
+                watch[r] = (ptr, n, 0, 0)
+            chunks, wchunks = fill_chunks(table, chunk), fill_chunks(watch, chunk)
+            blob = np.concatenate([table.view(np.uint8), watch.view(np.uint8), np.zeros(16, np.uint8)])
+            self._host = torch.from_numpy(blob).pin_memory()
+            dev = self._host.to(device, non_blocking=True)
+            self._table, self._watch_table = dev[:table.nbytes], dev[table.nbytes:table.nbytes + watch.nbytes]
+            self._counts = (len(key), chunks, len(wkey), wchunks)
+            self._key = full
+        n, chunks, nw, wchunks = self._counts
+        ops.optim_adam_step(self._table, n, chunks, self._watch_table, nw, wchunks, self._words, self._global, self.max_grad_norm)
+
+
+def make_adam(params, cfg, modules):
+    """The trainers' optimiser: torch.optim.Adam(params, lr=cfg.lr) as the reference has it, or - cfg.fused_optim, or a cfg.max_grad_norm,
+    which implies it - FusedAdam over the same parameters and lr, watching the float buffers of the trained `modules`."""
+    params = list(params)
+    if not (getattr(cfg, "fused_optim", False) or getattr(cfg, "max_grad_norm", None)):
+        return torch.optim.Adam(params, lr=cfg.lr)
+    seen, watch = set(), []
+    for m in modules:
+        for b in m.buffers():
+            if b.dtype == torch.float32 and id(b) not in seen:
+                seen.add(id(b))
+                watch.append(b)
+    return FusedAdam(params, lr=cfg.lr, max_grad_norm=getattr(cfg, "max_grad_norm", None) or None, watch=watch)

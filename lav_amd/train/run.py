@@ -11,7 +11,7 @@ from typing import Callable, Optional
 import torch
 import torch.distributed as dist
 
-from . import log_view
+from . import log_view, state as run_state
 from .brake import BRA_LABELS, BrakeTrainer
 from .lav import LAV, TrainConfig
 from .synthetic import synthetic_bev_batch, synthetic_bra_batch, synthetic_lidar_batch, synthetic_seg_batch
@@ -274,6 +274,7 @@ def _camera_stepper(images, train):
             if aug is not None:      # uploaded as uint8 and augmented there; the train step converts them as ever
                 batch = [a(_as_u8_hwc(x).to(device)) for a, x in zip(aug, batch)] + list(batch[images:])
             return train(trainer)(*batch)
+        step.augmenters = aug or ()       # (--state-dir saves their counts)
         return step
     return stepper
 
@@ -311,7 +312,10 @@ def main(what):
     the parser to the teardown: the recorded routes under the config's `data_dir` are read by lav_amd.data (every rank its own shard of
     each epoch), one optimiser step per batch, checkpoints every --num-per-save epochs, one JSON summary line.  What this build adds to
     the reference's flags: --synthetic / --steps-per-epoch (seeded synthetic batches instead of a data set), --save-dir, and what the
-    trainer's description (_lav, _SEG, _BRA) names, and --log-dir (a picture of sample 0 per logged iteration)."""
+    trainer's description (_lav, _SEG, _BRA) names, --log-dir (a picture of sample 0 per logged iteration), --fused-optim /
+    --max-grad-norm / --max-skipped-steps (lav_amd.train.optim.FusedAdam: a step with a NaN / Inf gradient is skipped, a run that keeps
+    skipping ends) and --state-dir / --resume (lav_amd.train.state: everything a run needs to go on from an epoch boundary).  Without
+    these flags nothing changes, files written included."""
     t = {"seg": _SEG, "bra": _BRA}.get(what) or _lav(what)
     ap = argparse.ArgumentParser()
     for flag, kw in (
@@ -329,12 +333,35 @@ def main(what):
             ("--save-dir", dict(default="checkpoints")),
             ("--log-dir", dict(default=None, metavar="DIR",
                                help="write the reference's visual log of sample 0 (lav/utils/logger.py) as DIR/{what}_{iteration:07d}.png at every "
-                                    "--num-per-log-th iteration, composed on the device (lav_amd.train.log_view).  Default: none, nothing changes"))):
+                                    "--num-per-log-th iteration, composed on the device (lav_amd.train.log_view).  Default: none, nothing changes")),
+            ("--fused-optim", dict(action="store_true",
+                                   help="lav_amd.train.optim.FusedAdam where torch.optim.Adam stands: one read of all gradients decides whether the step "
+                                        "is applied (a NaN / Inf in any gradient skips it: parameters and moments keep every bit), one launch updates all "
+                                        "parameters; the log lines gain grad_norm and skipped_steps")),
+            ("--max-grad-norm", dict(type=float, default=None, metavar="X", help="clip the global gradient norm to X inside the fused step "
+                                                                                 "(clip_grad_norm_'s factor); implies --fused-optim")),
+            ("--max-skipped-steps", dict(type=int, default=10, metavar="N",
+                                         help="--fused-optim: end the run (non-zero exit) when more than N steps were skipped between two log "
+                                              "iterations, or when a BatchNorm running statistic is not finite")),
+            ("--state-dir", dict(default=None, metavar="DIR",
+                                 help="whenever checkpoints are written, also write DIR/state_{epoch}.th: models, optimiser, scheduler, iteration "
+                                      "counters, augmenter counts, random generators of every rank (the two newest are kept).  State is taken at epoch "
+                                      "boundaries only: resuming inside an epoch of a shuffled loader is out of scope")),
+            ("--resume", dict(default=None, metavar="PATH",
+                              help="continue from a state file at its epoch + 1, with its iteration count; 'auto': the newest of --state-dir, or a "
+                                   "fresh start when there is none (a job script that is simply re-submitted).  Other defining arguments "
+                                   "(batch size, seed, lr ...) than the state's are refused"))):
         for f, k in [(flag, kw)] + t.flags.get(flag, []):
             ap.add_argument(f, **k)
     args = ap.parse_args()
     if getattr(args, "deterministic", False):
         set_deterministic(True)
+    if args.max_grad_norm is not None:
+        if not args.max_grad_norm > 0:
+            raise SystemExit(f"--max-grad-norm {args.max_grad_norm}: a positive norm")
+        args.fused_optim = True
+    if args.resume == "auto" and not args.state_dir:
+        raise SystemExit("--resume auto looks into --state-dir")
     # without a default (bev / lidar) the file named must exist, open() says so; a default that is not there (seg / bra) is no config
     named = t.config_path is None
     have_cfg = bool(args.config_path) and (named or os.path.isfile(args.config_path))
@@ -344,7 +371,8 @@ def main(what):
     rank, world, device = setup_distributed()
     if args.device == "cpu":
         device = torch.device("cpu")
-    cfg = load_config(args.config_path if have_cfg else None, lr=args.lr, seed=args.seed, **t.overrides(args))
+    cfg = load_config(args.config_path if have_cfg else None, lr=args.lr, seed=args.seed, fused_optim=args.fused_optim,
+                      max_grad_norm=args.max_grad_norm, **t.overrides(args))
     if args.batch_size % world:
         raise SystemExit(f"global batch {args.batch_size} is not divisible by {world} ranks")
     per_rank = args.batch_size // world
@@ -370,8 +398,18 @@ def main(what):
     # --log-dir, rank 0: the logged steps also return their "view"; its frame is composed where the tensors are and handed to the writer,
     # which encodes it when the next one arrives (and at the end) - the step never waits for its own picture
     writer = log_view.FrameWriter(args.log_dir, what) if args.log_dir and rank == 0 else None
-    global_it, t0 = 0, time.perf_counter()
-    for epoch in range(args.num_epoch):
+    global_it, first_epoch = 0, 0
+    resume = run_state.newest(args.state_dir) if args.resume == "auto" else args.resume      # (auto without a file: a fresh start)
+    if resume:
+        first_epoch, global_it = run_state.restore(run_state.load(resume), trainer, what, args, getattr(step, "augmenters", ()), rank, world)
+        if rank == 0:
+            print(f"resumed from {resume}: epoch {first_epoch}, iteration {global_it}", flush=True)
+    optimizer = getattr(trainer, f"{what}_optim")
+    skipped_seen = health = None
+    if args.fused_optim:
+        skipped_seen = optimizer.health()["skipped"]
+    t0, it0 = time.perf_counter(), global_it
+    for epoch in range(first_epoch, args.num_epoch):
         for batch in batches(epoch):
             drawn = writer is not None and global_it % args.num_per_log == 0
             trainer.log_view = drawn
@@ -379,8 +417,18 @@ def main(what):
             if drawn:
                 trainer.log_view = False
                 writer.add(log_view.render(log_view.build_frame(what, info.pop("view"), cfg)), global_it)
-            if global_it % args.num_per_log == 0 and rank == 0:
-                print(global_it, t.log(info), flush=True)
+            if global_it % args.num_per_log == 0:
+                shown = t.log(info) if rank == 0 else None
+                if args.fused_optim:
+                    # every rank reads its own words and takes the decision alone: under data parallel all of them stepped on the same
+                    # all-reduced gradients, so they all see the same counts - no collective is needed to agree on the end of the run
+                    health = optimizer.health()
+                    if rank == 0:
+                        shown = dict(shown, grad_norm=round(health["grad_norm"], 4), skipped_steps=health["skipped"])
+                if rank == 0:
+                    print(global_it, shown, flush=True)
+                if args.fused_optim:
+                    skipped_seen = run_state.check_health(health, skipped_seen, args.max_skipped_steps, args.state_dir)
             global_it += 1
         if scheduler is not None:
             scheduler.step()       # once per epoch (train_full_v2.py:33)
@@ -390,12 +438,16 @@ def main(what):
                 path = os.path.join(args.save_dir, f"{name}_{epoch + 1}.th")
                 torch.save(trainer.state_dict(name), path)
                 print(f"saved to {path}", flush=True)
+        if (epoch + 1) % args.num_per_save == 0 and args.state_dir:     # every rank: the ranks' generator states are gathered
+            st = run_state.capture(trainer, what, args, epoch + 1, global_it, getattr(step, "augmenters", ()), rank, world)
+            if rank == 0:
+                print(f"state in {run_state.write(st, args.state_dir)}", flush=True)
     if writer is not None:
         writer.close()
     if device.type == "cuda":
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    summary = dict(what=what, samples_per_s=round(args.batch_size * global_it / (max(dt, 1e-9) if t.guard_dt else dt), 2), n_gpus=world)
+    summary = dict(what=what, samples_per_s=round(args.batch_size * (global_it - it0) / (max(dt, 1e-9) if t.guard_dt else dt), 2), n_gpus=world)
     if t.replicas:
         summary["replicas_in_sync"] = None
         if world > 1:   # data parallel keeps the replicas identical: compare a checksum of every trained parameter across the ranks
@@ -409,6 +461,9 @@ def main(what):
                    lr=getattr(trainer, f"{what}_optim").param_groups[0]["lr"])
     if scheduler is not None:
         summary["scheduler_epochs"] = scheduler.last_epoch
+    if args.fused_optim:
+        health = optimizer.health()
+        summary.update(fused_optim=True, skipped_steps=health["skipped"], last_grad_norm=health["grad_norm"])
     if rank == 0:
         print(json.dumps(summary))
     if world > 1:
