@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 46
+#define LAV_ABI_VERSION 47
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -701,6 +701,7 @@ int lav_conv3x3_run_f16(int channels, int h, int w, int nlayers, const float *x,
                         const float *const *shift, float *out, const float *amax_in, int amax_in_count, float *amax_out, void *workspace,
                         size_t workspace_bytes, void *stream);
 int lav_conv3x3_run_f16_status(const void *workspace, int *h_timeouts_launches2, void *stream);
+
 /*
  * lav_conv3x3_tile_f16 (ABI 40): a run of nlayers (<= 3) of the same layers at 64 channels as ONE launch without any hand-off between
  * workgroups - stage s1 of the BEV backbone behind its stride-2 layer.  A workgroup owns an 8 x 16 output tile for all layers: it stages
@@ -724,6 +725,18 @@ int lav_conv1d_pair(int batch, int channels, int h, int w, int d_a, int d_b, con
  * x [batch][channels][h][w] (h, w even); y [batch][out_c_total][h/2][w/2]. */
 int lav_pool_affine(const float *x, int batch, int channels, int h, int w, const float *scale, const float *shift, int relu,
                     float *y, int out_c_total, int out_c_offset, void *stream);
+
+/* ERFNet's two entry DownsamplerBlocks (3 -> 16 -> 64 channels) as one launch (ABI 47; csrc/erfnet_edge.hip):
+ *     y = block2(block1(x)),   block(x) = relu(bn(cat(conv3x3/s2(x), maxpool2x2(x))))
+ * x [batch][3][h][w] raw input (h, w multiples of 4); y [batch][64][h/4][w/4].  Block 1 as DownsamplerBlock.engine folds it:
+ * w1 [13][3][3][3] and b1 [13] with the input affine folded in, pad_value what out-of-image taps of block 1 read (-t/s; 0 without
+ * an input affine), scale1 / shift1 [16]: the BatchNorm affine of the 13 convolution channels, then that of the 3 pooled
+ * channels with the input affine folded in.  Block 2: w2 [48][16][3][3] (16-byte aligned), b2 [48], scale2 / shift2 [64]
+ * (48 convolution channels, then 16 pooled).  Both convolutions are fp32 FMA chains (block 2 on v_mfma_f32_16x16x4_f32): the
+ * result does not depend on LAV_CONV_PRECISION.  No workspace. */
+int lav_erfnet_entry(const float *x, int batch, int h, int w, const float *w1, const float *b1, float pad_value, const float *scale1,
+                     const float *shift1, const float *w2, const float *b2, const float *scale2, const float *shift2, float *y,
+                     void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Train mode of ERFNet's factorised convolution pairs (ABI 29; csrc/conv_pair_train.hip): one pair of a non_bottleneck_1d is

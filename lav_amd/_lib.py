@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LAV_AMD_LIB") or os.path.join(HERE, "liblav_amd.so")   # LAV_AMD_LIB: A/B a second build
 
-ABI_VERSION = 46
+ABI_VERSION = 47
 MAX_CAM = 4
 MAX_CAM_F64 = 8
 
@@ -153,6 +153,7 @@ SIGNATURES = {
     "lav_stage_many_block": (_I, [_I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_I), C.POINTER(C.c_long), C.POINTER(_I), _P, _I, _P, _P]),
     "lav_batch_limit": (_I, [_P]),
     "lav_pool_affine": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _I, _P]),
+    "lav_erfnet_entry": (_I, [_P, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lav_merge_ticks": (_I, [_P, _P, _I, _I, _P, _P]),
     "lav_stack_sweeps": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "lav_extract_peaks_workspace_bytes": (_Z, [_I, _I, _I]),

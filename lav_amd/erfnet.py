@@ -2,7 +2,8 @@
 (lav/models/erfnet.py).  In eval mode on the GPU every convolution - 3x3/s2 downsamplers, the factorised
 3x1 / 1x3 (dilated) pairs, the 3x3/s2 and 2x2/s2 transposed convolutions - is one lav_conv2d launch with its
 bias, BatchNorm affine, residual add and ReLU fused into the epilogue (the reference issues ~6 kernels per
-non_bottleneck_1d convolution pair; MIOpen falls back to naive kernels for the dilated asymmetric shapes).
+non_bottleneck_1d convolution pair; MIOpen falls back to naive kernels for the dilated asymmetric shapes); the two downsamplers at the
+entry are one launch together (lav_erfnet_entry), the runs of non_bottleneck_1d blocks one persistent launch each.
 The torch forward below is kept for training mode, where every non_bottleneck_1d on the GPU goes through
 lav_amd.train.hipnn.nb1d_train (its pairs on lav_pair_train_*, its BatchNorms on lav_bn_train_*; the downsamplers, upsamplers
 and the output transposed convolution stay torch ops).
@@ -19,6 +20,7 @@ from . import ops
 from .engine import Engine
 from .ops import Conv1dPair, Conv1dPairChain, ConvLayer, GroupedDeconv, infer_precision
 
+ERFNET_ENTRY_DEFAULT = "1"
 _USE_PAIRS = os.environ.get("LAV_ERFNET_PAIRS", "1") != "0"   # A/B switch: 0 = four lav_conv2d launches per block
 
 
@@ -37,15 +39,10 @@ class DownsamplerBlock(nn.Module):
     def forward(self, x):
         return F.relu(self.bn(torch.cat([self.conv(x), self.pool(x)], 1)))
 
-    def engine(self, device, input_affine=None):
-        """Two launches: the convolution branch (bias, BatchNorm slice, ReLU fused) and lav_pool_affine for the pooled
-        branch, each writing its channel window of the output.  input_affine=(s, t): the block sees RAW input x while the
-        reference feeds x' = s*x + t (s > 0): the affine is folded into the convolution (W*s, b + t*sum(W), out-of-image
-        taps read -t/s, the pre-image of the reference's zero padding) and into the pooled branch's BatchNorm
-        (max commutes with an increasing map)."""
-        from . import ops
-        nconv = self.conv.out_channels
-        cout = self.bn.num_features
+    def _folded(self, input_affine=None):
+        """(w, b, pad, ps, pt): the convolution's weights and bias with input_affine folded in, the value its out-of-image taps
+        read, and the pooled channels' BatchNorm affine with input_affine folded in (engine's docstring)."""
+        nconv, cout = self.conv.out_channels, self.bn.num_features
         w, b, pad = self.conv.weight.detach(), self.conv.bias.detach(), 0.0
         s_in, t_in = (1.0, 0.0) if input_affine is None else input_affine
         if input_affine is not None:
@@ -54,18 +51,52 @@ class DownsamplerBlock(nn.Module):
             b = (b.double() + t_in * w.double().sum(dim=(1, 2, 3))).float()
             w = (w.double() * s_in).float()
             pad = -t_in / s_in
+        ps, pt = _affine(self.bn, slice(nconv, cout))
+        ps, pt = ps.reshape(-1).double(), pt.reshape(-1).double()
+        return w, b, pad, (ps * s_in).float(), (pt + ps * t_in).float()
+
+    def engine(self, device, input_affine=None):
+        """Two launches: the convolution branch (bias, BatchNorm slice, ReLU fused) and lav_pool_affine for the pooled
+        branch, each writing its channel window of the output.  input_affine=(s, t): the block sees RAW input x while the
+        reference feeds x' = s*x + t (s > 0): the affine is folded into the convolution (W*s, b + t*sum(W), out-of-image
+        taps read -t/s, the pre-image of the reference's zero padding) and into the pooled branch's BatchNorm
+        (max commutes with an increasing map)."""
+        nconv = self.conv.out_channels
+        cout = self.bn.num_features
+        w, b, pad, ps, pt = self._folded(input_affine)
         sl = slice(0, nconv)
         bn = tuple(t[sl] for t in (self.bn.running_mean, self.bn.running_var, self.bn.weight, self.bn.bias))
         conv = ConvLayer(w, stride=2, padding=(1, 1), bias=b, bn=bn, bn_eps=self.bn.eps, relu_post=True, out_c_total=cout,
                          pad_value=pad, device=device)
-        ps, pt = _affine(self.bn, slice(nconv, cout))
-        ps, pt = ps.reshape(-1).double(), pt.reshape(-1).double()
-        ps, pt = (ps * s_in).float().to(device), (pt + ps * t_in).float().to(device)
+        ps, pt = ps.to(device), pt.to(device)
 
         def run(x):
             out = conv(x)                                                    # channels [0, nconv): conv+bias -> BN -> ReLU
             return ops.pool_affine(x, ps, pt, out, nconv, relu=True)         # channels [nconv, cout): pool -> BN -> ReLU
         return run
+
+
+def _entry_stage(b1, b2, device, input_affine, first, second):
+    """encoder.initial_block + encoder.layers[0] as ONE launch (lav_erfnet_entry: both blocks' convolutions as fp32 FMA chains, right
+    in every precision mode) for the inputs the kernel takes as they lie in memory; `first`, `second` - the blocks' own engines -
+    serve the others."""
+    def vectors(m, ps, pt):
+        nconv = m.conv.out_channels
+        s, t = ops.bn_fold(*[v.detach().cpu()[:nconv] for v in (m.bn.running_mean, m.bn.running_var, m.bn.weight, m.bn.bias)], m.bn.eps)
+        return torch.cat([s.float(), ps.cpu()]).to(device), torch.cat([t.float(), pt.cpu()]).to(device)
+    w1, bias1, pad, ps1, pt1 = b1._folded(input_affine)
+    w2, bias2, _, ps2, pt2 = b2._folded()
+    s1, t1 = vectors(b1, ps1, pt1)
+    s2, t2 = vectors(b2, ps2, pt2)
+    w1, bias1, w2, bias2 = (v.to(device, torch.float32).contiguous() for v in (w1, bias1, w2, bias2))
+
+    def run(x):
+        if ops.erfnet_entry_takes(x):
+            return ops.erfnet_entry(x, w1, bias1, pad, s1, t1, w2, bias2, s2, t2)
+        return second(first(x))
+    run.fused_entry = True
+    run.args = (w1, bias1, pad, s1, t1, w2, bias2, s2, t2)     # (lav_erfnet_entry's parameters, for a caller with a buffer of its own)
+    return run
 
 
 class non_bottleneck_1d(nn.Module):  # name kept: it is part of pickled/traced checkpoints' qualified names
@@ -203,6 +234,11 @@ class ERFNet(Engine):
         def build():
             stages = [self.encoder.initial_block.engine(device, input_affine)]
             stages += [m.engine(device) for m in self.encoder.layers]
+            # the two entry downsamplers as one launch (LAV_ERFNET_ENTRY=0: their own four launches; profiles/erfnet_edge_ab.txt)
+            ib, l0 = self.encoder.initial_block, self.encoder.layers[0]
+            if (os.environ.get("LAV_ERFNET_ENTRY", ERFNET_ENTRY_DEFAULT) != "0" and isinstance(l0, DownsamplerBlock)
+                    and (ib.conv.in_channels, ib.bn.num_features, l0.bn.num_features) == (3, 16, 64)):
+                stages[:2] = [_entry_stage(ib, l0, device, input_affine, stages[0], stages[1])]
             stages += [m.engine(device) for m in self.decoder.layers]
             stages = _chain_blocks(stages)
             stages.append(GroupedDeconv([self.decoder.output_conv], softmax=softmax, device=device))   # 16 -> classes, k2 s2: memory bound

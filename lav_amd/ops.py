@@ -1903,6 +1903,34 @@ def pool_affine(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, out: 
     return out
 
 
+def erfnet_entry_takes(x: torch.Tensor) -> bool:
+    """Whether lav_erfnet_entry serves x as it lies in memory: (B, 3, H, W) float32, contiguous, H and W multiples of 4."""
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == 3 and 1 <= x.shape[0] <= 65535
+            and x.shape[2] >= 4 and x.shape[3] >= 4 and x.shape[2] % 4 == 0 and x.shape[3] % 4 == 0 and x.shape[2] <= 8 * 4 * 65535)
+
+
+def erfnet_entry(x: torch.Tensor, w1, b1, pad_value: float, scale1, shift1, w2, b2, scale2, shift2, out: Optional[torch.Tensor] = None):
+    """ERFNet's two entry DownsamplerBlocks on the raw input x (B,3,H,W) as one launch -> (B,64,H/4,W/4); the parameters as
+    include/lav_amd.h describes them (lav_erfnet_entry)."""
+    if not erfnet_entry_takes(x):
+        raise RuntimeError(f"erfnet_entry: input {tuple(x.shape)} is not served (contiguous float32 (B,3,H,W) with H, W multiples of 4)")
+    B, _, H, W = x.shape
+    if out is None:
+        out = torch.empty((B, 64, H // 4, W // 4), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, 64, H // 4, W // 4) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise RuntimeError("erfnet_entry: output buffer does not match")
+    vec = [("w1", w1, 13 * 27), ("b1", b1, 13), ("scale1", scale1, 16), ("shift1", shift1, 16), ("w2", w2, 48 * 144), ("b2", b2, 48),
+           ("scale2", scale2, 64), ("shift2", shift2, 64)]
+    ptrs = {}
+    for name, t, n in vec:
+        if t.numel() != n or t.device != x.device:
+            raise RuntimeError(f"erfnet_entry: {name} must hold {n} floats on {x.device}")
+        ptrs[name] = _ptr(_f32c(t, name))
+    check(_lib.load().lav_erfnet_entry(_ptr(x), B, H, W, ptrs["w1"], ptrs["b1"], float(pad_value), ptrs["scale1"], ptrs["shift1"], ptrs["w2"],
+                                       ptrs["b2"], ptrs["scale2"], ptrs["shift2"], _ptr(out), _stream()), "lav_erfnet_entry")
+    return out
+
+
 def crop_rotate(features: torch.Tensor, locs: torch.Tensor, oris: torch.Tensor, pixels_per_meter: float, crop: int,
                 offset_x: float, offset_y: float) -> torch.Tensor:
     """features (1 or N, C, H, W), locs (N,2), oris (N,) in HBM -> (N, C, crop, crop)."""
