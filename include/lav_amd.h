@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 47
+#define LAV_ABI_VERSION 48
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -1231,6 +1231,20 @@ int lav_optim_grad_stats(const lav_optim_tensor *table, int ntensors, int total_
 int lav_optim_adam_step(const lav_optim_tensor *table, int ntensors, int total_chunks, const lav_optim_watch *watch, int nwatch,
                         int watch_chunks, lav_optim_state *state, lav_optim_global *global, double max_norm, void *workspace,
                         size_t workspace_bytes, void *stream);
+
+/* lav_optim_adam_ema_step (ABI 48; FusedAdam(ema_decay=...), the trainers' --ema): lav_optim_adam_step, and the update launch also keeps
+ * an exponential moving average of every tensor of the table.  shadow: a DEVICE array of ntensors float pointers, row-parallel to `table`
+ * (shadow[r] belongs to table[r]): float32, dense, numel elements, 4-byte aligned, overlapping none of p, g, m, v.  ema_decay: 0 < decay < 1,
+ * anything else is refused.  With the tensor's words advanced to the step count k >= 1, once per workgroup in float64
+ *     d_k = min(ema_decay, (1 + k) / (10 + k));  omd = float32(1 - d_k)
+ * and per element in float32, every operation rounded on its own, with p the parameter the launch has just computed:
+ *     e = e + omd (p - e)
+ * With apply clear e keeps every bit, as p, m and v do.  Same three launches, same workspace, same structs; p, m, v, the words and `global`
+ * get the bits lav_optim_adam_step gives them.  16-byte accesses where p, m, v and e share a misalignment, 4-byte accesses otherwise.
+ * Specification: lav_amd.train.optim.fused_adam_numpy(..., ema_decay=), equal in every stored bit. */
+int lav_optim_adam_ema_step(const lav_optim_tensor *table, int ntensors, int total_chunks, const lav_optim_watch *watch, int nwatch,
+                            int watch_chunks, lav_optim_state *state, lav_optim_global *global, double max_norm, float *const *shadow,
+                            double ema_decay, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LAV_AMD_LIB") or os.path.join(HERE, "liblav_amd.so")   # LAV_AMD_LIB: A/B a second build
 
-ABI_VERSION = 47
+ABI_VERSION = 48
 MAX_CAM = 4
 MAX_CAM_F64 = 8
 
@@ -185,6 +185,7 @@ SIGNATURES = {
     "lav_optim_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
     "lav_optim_grad_stats": (_I, [_P, _I, _I, _P, _I, _I, _P, C.c_double, _P, _Z, _P]),
     "lav_optim_adam_step": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, C.c_double, _P, _Z, _P]),
+    "lav_optim_adam_ema_step": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, C.c_double, _P, C.c_double, _P, _Z, _P]),
 }
 
 _lib = None

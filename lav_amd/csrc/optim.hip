@@ -1,6 +1,7 @@
-// Multi-tensor gradient statistics and a guarded Adam step (ABI 46): the device half of lav_amd.train.optim.FusedAdam.  The
-// specification is lav_amd.train.optim.fused_adam_numpy and the two agree in every stored bit (tests/test_gpu_optim.py); the sum of
-// squares alone is pinned by a bound, n * 2^-53 relative, because its order of summation is this file's business.
+// Multi-tensor gradient statistics and a guarded Adam step (ABI 46), which can keep a moving average of the weights (ABI 48): the
+// device half of lav_amd.train.optim.FusedAdam.  The specification is lav_amd.train.optim.fused_adam_numpy and the two agree in every
+// stored bit (tests/test_gpu_optim.py, tests/test_gpu_ema.py); the sum of squares alone is pinned by a bound, n * 2^-53 relative,
+// because its order of summation is this file's business.
 //
 // The work is cut into chunks of OPTIM_CHUNK elements, one workgroup per chunk; a row of the descriptor table carries the index of its
 // tensor's first chunk, so a workgroup finds its tensor by a binary search over the rows.  Three launches, and every dependency between
@@ -11,8 +12,11 @@
 //                     applying, one thread per tensor advances its step count and running powers and leaves the two float32 factors.
 //   k_optim_update    per chunk, when apply is set: the Adam update in float32, every operation rounded on its own (this file is compiled
 //                     with contraction off and correctly rounded division and square root).  When skipping it stores nothing.
-// Pointers are 4-byte aligned only: a chunk runs on 16-byte accesses where p, m and v share a misalignment (g too, or g on 4-byte loads
-// beside them), heads and tails on 4-byte accesses; otherwise on 4-byte accesses throughout.
+//                     Its <true> instantiation (lav_optim_adam_ema_step) also moves a shadow e of every tensor towards the parameter it
+//                     has just computed and still holds in registers: e = e + omd * (p - e), omd = float32(1 - min(decay, (1 + k) /
+//                     (10 + k))) from the tensor's step count k in float64, once per workgroup.  One load and one store more per element.
+// Pointers are 4-byte aligned only: a chunk runs on 16-byte accesses where p, m and v (and e) share a misalignment (g too, or g on
+// 4-byte loads beside them), heads and tails on 4-byte accesses; otherwise on 4-byte accesses throughout.
 #include "common.hpp"
 
 namespace {
@@ -149,6 +153,7 @@ __global__ __launch_bounds__(THREADS) void k_optim_finalise(const lav_optim_tens
 
 struct Coef {
     float clip, beta1, beta2, om1, om2, step_size, inv, eps;
+    float omd;      // EMA alone: 1 - d_k
 };
 
 __device__ __forceinline__ void adam1(float g, float &p, float &m, float &v, const Coef &c) {
@@ -158,19 +163,31 @@ __device__ __forceinline__ void adam1(float g, float &p, float &m, float &v, con
     p = p - c.step_size * (m / (sqrtf(v) * c.inv + c.eps));
 }
 
+__device__ __forceinline__ void ema1(float p, float &e, const Coef &c) { e = e + c.omd * (p - e); }
+
+template <bool EMA>
 __device__ __forceinline__ void adam_scalar(const float *__restrict__ g, float *__restrict__ p, float *__restrict__ m, float *__restrict__ v,
-                                            int i, const Coef &c) {
+                                            float *__restrict__ e, int i, const Coef &c) {
     float pi = p[i], mi = m[i], vi = v[i];
     adam1(g[i], pi, mi, vi, c);
     p[i] = pi; m[i] = mi; v[i] = vi;
+    if constexpr (EMA) {
+        float ei = e[i];
+        ema1(pi, ei, c);
+        e[i] = ei;
+    }
 }
 
+// EMA: `shadow` holds one pointer per row of the table, to the tensor's moving average e
+template <bool EMA>
 __global__ __launch_bounds__(THREADS) void k_optim_update(const lav_optim_tensor *__restrict__ table, int ntensors,
                                                           const lav_optim_state *__restrict__ state,
-                                                          const lav_optim_global *__restrict__ global) {
+                                                          const lav_optim_global *__restrict__ global, float *const *__restrict__ shadow,
+                                                          double ema_decay) {
     if (!global->apply) return;
     const int tid = threadIdx.x, chunk = blockIdx.x;
-    const lav_optim_tensor &row = table[find_row(table, ntensors, chunk)];
+    const int r = find_row(table, ntensors, chunk);
+    const lav_optim_tensor &row = table[r];
     const long long first = (long long)(chunk - row.chunk0) * OPTIM_CHUNK, left = row.numel - first;
     const int n = left <= 0 ? 0 : (int)(left < OPTIM_CHUNK ? left : OPTIM_CHUNK);
     const lav_optim_state &st = state[row.state];
@@ -179,16 +196,25 @@ __global__ __launch_bounds__(THREADS) void k_optim_update(const lav_optim_tensor
     c.beta1 = (float)row.beta1; c.beta2 = (float)row.beta2;
     c.om1 = (float)(1.0 - row.beta1); c.om2 = (float)(1.0 - row.beta2);      // constants: float64, rounded once
     c.step_size = st.step_size; c.inv = st.inv_sqrt_bc2; c.eps = (float)row.eps;
+    c.omd = 0.0f;
     const float *__restrict__ g = row.g + first;
     float *__restrict__ p = row.p + first, *__restrict__ m = row.m + first, *__restrict__ v = row.v + first;
+    float *__restrict__ e = nullptr;
+    if constexpr (EMA) {
+        const double k = (double)st.step;           // (advanced by k_optim_finalise: >= 1)
+        c.omd = (float)(1.0 - fmin(ema_decay, (1.0 + k) / (10.0 + k)));
+        e = shadow[r] + first;
+    }
     const uintptr_t ap = reinterpret_cast<uintptr_t>(p) & 15;
-    if (ap != (reinterpret_cast<uintptr_t>(m) & 15) || ap != (reinterpret_cast<uintptr_t>(v) & 15)) {
-        for (int i = tid; i < n; i += THREADS) adam_scalar(g, p, m, v, i, c);
+    bool same = ap == (reinterpret_cast<uintptr_t>(m) & 15) && ap == (reinterpret_cast<uintptr_t>(v) & 15);
+    if constexpr (EMA) same = same && ap == (reinterpret_cast<uintptr_t>(e) & 15);
+    if (!same) {
+        for (int i = tid; i < n; i += THREADS) adam_scalar<EMA>(g, p, m, v, e, i, c);
         return;
     }
     const bool g16 = (reinterpret_cast<uintptr_t>(g) & 15) == ap;     // a gradient that is a view into a bucket is often not
     const int head = head_of(p, n), nv = (n - head) >> 2, tail = head + 4 * nv;
-    if (tid < head) adam_scalar(g, p, m, v, tid, c);
+    if (tid < head) adam_scalar<EMA>(g, p, m, v, e, tid, c);
     float4 *p4 = reinterpret_cast<float4 *>(p + head), *m4 = reinterpret_cast<float4 *>(m + head), *v4 = reinterpret_cast<float4 *>(v + head);
     for (int k = tid; k < nv; k += THREADS) {
         float4 gg;
@@ -204,8 +230,14 @@ __global__ __launch_bounds__(THREADS) void k_optim_update(const lav_optim_tensor
         adam1(gg.z, pp.z, mm.z, vv.z, c);
         adam1(gg.w, pp.w, mm.w, vv.w, c);
         p4[k] = pp; m4[k] = mm; v4[k] = vv;
+        if constexpr (EMA) {
+            float4 *e4 = reinterpret_cast<float4 *>(e + head);
+            float4 ee = e4[k];
+            ema1(pp.x, ee.x, c); ema1(pp.y, ee.y, c); ema1(pp.z, ee.z, c); ema1(pp.w, ee.w, c);
+            e4[k] = ee;
+        }
     }
-    if (tail + tid < n) adam_scalar(g, p, m, v, tail + tid, c);
+    if (tail + tid < n) adam_scalar<EMA>(g, p, m, v, e, tail + tid, c);
 }
 
 int check_args(const void *table, int ntensors, int total_chunks, const void *watch, int nwatch, int watch_chunks, const void *global,
@@ -222,7 +254,8 @@ int check_args(const void *table, int ntensors, int total_chunks, const void *wa
 }
 
 int run(const lav_optim_tensor *table, int ntensors, int total_chunks, const lav_optim_watch *watch, int nwatch, int watch_chunks,
-        lav_optim_state *state, lav_optim_global *global, double max_norm, int advance, void *workspace, size_t workspace_bytes, void *stream) {
+        lav_optim_state *state, lav_optim_global *global, double max_norm, int advance, float *const *shadow, double ema_decay,
+        void *workspace, size_t workspace_bytes, void *stream) {
     if (int rc = check_args(table, ntensors, total_chunks, watch, nwatch, watch_chunks, global, workspace, workspace_bytes)) return rc;
     LAV_REQUIRE(!advance || ntensors == 0 || state, "lav_optim_adam_step: null state words");
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -238,7 +271,10 @@ int run(const lav_optim_tensor *table, int ntensors, int total_chunks, const lav
     LAV_LAUNCH_CHECK();
     if (advance && total_chunks > 0) {
         const int tok = timer_begin("optim_update", st);
-        hipLaunchKernelGGL(k_optim_update, dim3(total_chunks), dim3(THREADS), 0, st, table, ntensors, state, global);
+        if (shadow)
+            hipLaunchKernelGGL(k_optim_update<true>, dim3(total_chunks), dim3(THREADS), 0, st, table, ntensors, state, global, shadow, ema_decay);
+        else
+            hipLaunchKernelGGL(k_optim_update<false>, dim3(total_chunks), dim3(THREADS), 0, st, table, ntensors, state, global, shadow, 0.0);
         timer_end(tok, st);
         LAV_LAUNCH_CHECK();
     }
@@ -257,11 +293,20 @@ extern "C" size_t lav_optim_workspace_bytes(long long total_chunks, long long wa
 extern "C" int lav_optim_grad_stats(const lav_optim_tensor *table, int ntensors, int total_chunks, const lav_optim_watch *watch, int nwatch,
                                     int watch_chunks, lav_optim_global *global, double max_norm, void *workspace, size_t workspace_bytes,
                                     void *stream) {
-    return run(table, ntensors, total_chunks, watch, nwatch, watch_chunks, nullptr, global, max_norm, 0, workspace, workspace_bytes, stream);
+    return run(table, ntensors, total_chunks, watch, nwatch, watch_chunks, nullptr, global, max_norm, 0, nullptr, 0.0, workspace, workspace_bytes, stream);
 }
 
 extern "C" int lav_optim_adam_step(const lav_optim_tensor *table, int ntensors, int total_chunks, const lav_optim_watch *watch, int nwatch,
                                    int watch_chunks, lav_optim_state *state, lav_optim_global *global, double max_norm, void *workspace,
                                    size_t workspace_bytes, void *stream) {
-    return run(table, ntensors, total_chunks, watch, nwatch, watch_chunks, state, global, max_norm, 1, workspace, workspace_bytes, stream);
+    return run(table, ntensors, total_chunks, watch, nwatch, watch_chunks, state, global, max_norm, 1, nullptr, 0.0, workspace, workspace_bytes, stream);
+}
+
+extern "C" int lav_optim_adam_ema_step(const lav_optim_tensor *table, int ntensors, int total_chunks, const lav_optim_watch *watch, int nwatch,
+                                       int watch_chunks, lav_optim_state *state, lav_optim_global *global, double max_norm,
+                                       float *const *shadow, double ema_decay, void *workspace, size_t workspace_bytes, void *stream) {
+    LAV_REQUIRE(ema_decay > 0.0 && ema_decay < 1.0, "lav_optim_adam_ema_step: ema_decay %g (0 < decay < 1)", ema_decay);
+    LAV_REQUIRE(ntensors <= 0 || shadow, "lav_optim_adam_ema_step: null shadow pointers");
+    return run(table, ntensors, total_chunks, watch, nwatch, watch_chunks, state, global, max_norm, 1, shadow, ema_decay, workspace, workspace_bytes,
+               stream);
 }

@@ -146,8 +146,10 @@ class ConvBackbone(Engine):
 
 
 class Head(Engine):
-    def __init__(self, num_input, num_output, num_hidden=64, norm_cfg=None, output_activation=nn.Identity()):
+    def __init__(self, num_input, num_output, num_hidden=64, norm_cfg=None, output_activation=None):
         super().__init__()
+        if output_activation is None:       # one nn.Identity per head: a default shared by every head of the process would carry one
+            output_activation = nn.Identity()       # model's .eval() into the others (a trainer beside its own validation)
         self.net = nn.Sequential(
             nn.Conv2d(num_input, num_hidden, 3, 1, 1, bias=False),
             nn.ReLU(inplace=True),

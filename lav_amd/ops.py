@@ -1816,6 +1816,19 @@ def optim_adam_step(table, ntensors, chunks, watch, nwatch, watch_chunks, state,
                                   float(max_norm or 0.0), _ptr(ws), nbytes, _stream()), "lav_optim_adam_step")
 
 
+def optim_adam_ema_step(table, ntensors, chunks, watch, nwatch, watch_chunks, state, glob, shadow, ema_decay, max_norm=None) -> None:
+    """optim_adam_step whose update launch also moves a shadow of every tensor towards its new parameter (lav_optim_adam_ema_step: the
+    same three launches).  shadow: a uint8 tensor in HBM holding `ntensors` device pointers (little-endian uint64), row-parallel to
+    `table`, to dense float32 tensors of the rows' sizes; ema_decay: 0 < decay < 1.  Equal to fused_adam_numpy(..., ema_decay=) in every
+    bit; p, m, v and the words get optim_adam_step's bits."""
+    lib, ws, nbytes = _optim_args("optim_adam_ema_step", table, ntensors, chunks, watch, nwatch, watch_chunks, dict(state=state, **{"global": glob}))
+    if not (isinstance(shadow, torch.Tensor) and shadow.is_cuda and shadow.device == glob.device and shadow.dtype == torch.uint8
+            and shadow.is_contiguous() and shadow.numel() >= 8 * int(ntensors) and (shadow.numel() == 0 or shadow.data_ptr() % 8 == 0)):
+        raise ValueError(f"optim_adam_ema_step: shadow must be a contiguous, 8-byte aligned uint8 tensor of at least {8 * int(ntensors)} bytes in HBM")
+    check(lib.lav_optim_adam_ema_step(_ptr(table), int(ntensors), int(chunks), _ptr(watch), int(nwatch), int(watch_chunks), _ptr(state), _ptr(glob),
+                                      float(max_norm or 0.0), _ptr(shadow), float(ema_decay), _ptr(ws), nbytes, _stream()), "lav_optim_adam_ema_step")
+
+
 def copy_many(pairs, block=None) -> None:
     """[(dst, src), ...] device tensors of equal shape into their destinations in at most two launches: contiguous same-dtype
     16-byte-aligned pairs through lav_copy_many (16-byte words), strided / uint8 sources of up to four dimensions into contiguous

@@ -10,4 +10,4 @@ from .losses import DetLoss, build_seg_mask, bev_losses, lidar_losses  # noqa: F
 from .lav import LAV, TrainConfig  # noqa: F401
 from .synthetic import synthetic_bev_batch, synthetic_bra_batch, synthetic_lidar_batch  # noqa: F401
 from .brake import BrakeTrainer  # noqa: F401
-from .optim import FusedAdam, fused_adam_numpy  # noqa: F401
+from .optim import FusedAdam, ema_state_dict, fused_adam_numpy  # noqa: F401

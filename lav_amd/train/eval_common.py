@@ -254,7 +254,15 @@ def parser(tool) -> argparse.ArgumentParser:
     return ap
 
 
-def run_cli(tool, argv=None):
+def held_out_units(tool, config_path, data_dir, seed=2021):
+    """How many of the tool's units (frames / images) its loader finds under `data_dir`, with the loaders' keys of `config_path`: what the
+    trainers' --val-data-dir asks before the first step."""
+    from .run import load_config
+    args = argparse.Namespace(synthetic=False, config_path=config_path, data_dir=data_dir, seed=seed)
+    return len(tool["batches"](args, load_config(config_path, seed=seed)))
+
+
+def run_cli(tool, argv=None, optional=(), echo=True):
     """One evaluation tool's main: one JSON line per precision - the tool's summary, the raw counters and the frames (images) per
     second of the evaluation, the whole run's, engine build and loader start-up included.  Single process, no augmentation, the
     loader in order and to its last sample.  `tool` describes what is the tool's own:
@@ -263,7 +271,9 @@ def run_cli(tool, argv=None):
         that was already in force)
         build(args, cfg, device) -> the model(s), from the checkpoint paths (or None: seeded weights) the driver left in args
         batches(args, cfg) -> the recorded dataset, or under --synthetic an iterator of batches
-        make_evaluator(model, name, args), line(ev, acc, args, cfg) -> the tool's own keys of the line."""
+        make_evaluator(model, name, args), line(ev, acc, args, cfg) -> the tool's own keys of the line.
+    optional: checkpoint flags that stay None when they are not given, the config is not asked (the trainers' validation: the teacher
+    rides in uniplanner_*.th); echo False: the lines are returned and not printed."""
     from .run import load_config
     args = parser(tool).parse_args(argv)
     name, unit = tool["name"], tool["unit"]
@@ -272,6 +282,8 @@ def run_cli(tool, argv=None):
     if args.batch_size < 1:
         raise SystemExit(f"--batch-size {args.batch_size}")
     for flag, key in tool["checkpoints"].items():
+        if flag in optional and not getattr(args, flag):
+            continue
         setattr(args, flag, config_checkpoint(args.config_path, key, flag, getattr(args, flag), args.synthetic,
                                               f"for seeded random weights on {tool['synthetic']}"))
     if not torch.cuda.is_available():
@@ -304,7 +316,8 @@ def run_cli(tool, argv=None):
                 f"{unit}_per_s": round(n / max(dt, 1e-9), 2), "counters": ev.layout.named(acc), **tool["line"](ev, acc, args, cfg)}
         line = {k: have[k] for k in tool["keys"]}
         lines.append(line)
-        print(json.dumps(line), flush=True)
+        if echo:
+            print(json.dumps(line), flush=True)
     if args.out:
         with open(args.out, "w") as f:
             f.writelines(json.dumps(one) + "\n" for one in lines)

@@ -305,7 +305,7 @@ def held_out_frames(config_path, data_dir=None, seed=2021):
 def _build(args, cfg, device):
     from .lav import LAV
     ck = {k: torch.load(getattr(args, k), map_location="cpu") for k in TOOL["checkpoints"] if getattr(args, k)}
-    lav = LAV(cfg, device, what="lidar", checkpoints=ck)
+    lav = LAV(cfg, device, what="lidar", checkpoints=ck, distributed=False)       # (an evaluation is one process's own: no collective)
     lav.student.eval()
     return lav
 

@@ -250,7 +250,8 @@ def held_out_bev_frames(config_path, data_dir=None, seed=2021):
 
 def _build(args, cfg, device):
     from .lav import LAV
-    return LAV(cfg, device, what="bev", checkpoints={"bev": torch.load(args.bev, map_location="cpu")} if args.bev else {})
+    return LAV(cfg, device, what="bev", checkpoints={"bev": torch.load(args.bev, map_location="cpu")} if args.bev else {},
+               distributed=False)       # (an evaluation is one process's own: no collective, also inside a trainer's process group)
 
 
 def _batches(args, cfg):

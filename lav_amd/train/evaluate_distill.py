@@ -368,7 +368,7 @@ class DistillEvaluator(EvaluatorBase):
 def _build(args, cfg, device):
     from .lav import LAV
     ck = {k: torch.load(getattr(args, k), map_location="cpu") for k in ("lidar", "uniplanner") if getattr(args, k)}
-    lav = LAV(cfg, device, what="lidar", checkpoints=ck)
+    lav = LAV(cfg, device, what="lidar", checkpoints=ck, distributed=False)
     lav.student.eval()
     if args.bev:           # another teacher than the one the uniplanner checkpoint carries
         if not os.path.isfile(args.bev):

@@ -18,7 +18,15 @@ APPLIED, clipped to `max_norm` by clip_grad_norm_'s factor when one is set:
 
 Running products stand where torch has beta ** step, so that host and device agree bit for bit; steps are counted per tensor, as torch
 counts them (a parameter without a gradient is left out of that step and keeps its own count).  The words are laid out as the C ABI
-lays them out (TENSOR_DTYPE ... GLOBAL_DTYPE = lav_optim_tensor ... lav_optim_global)."""
+lays them out (TENSOR_DTYPE ... GLOBAL_DTYPE = lav_optim_tensor ... lav_optim_global).
+
+With an `ema_decay` (0 < decay < 1; FusedAdam(ema_decay=), the trainers' --ema) an applied step also moves a shadow e of every tensor it
+updates towards the parameter it has just computed (lav_optim_adam_ema_step: inside the update launch, which still holds p):
+
+    per tensor, float64, k = its step count after this step:  d_k = min(ema_decay, (1 + k) / (10 + k));  omd = float32(1 - d_k)
+    per element, float32, every operation rounded on its own:  e = e + omd * (p - e)
+
+The warm-up keeps the first steps from being dominated by where the shadow started; a skipped step leaves e alone, as it leaves p."""
 from __future__ import annotations
 
 import math
@@ -62,11 +70,14 @@ def fill_chunks(rows, chunk):
     return total
 
 
-def fused_adam_numpy(tensors, state, glob, max_norm=None, watch=(), sumsq=None):
+def fused_adam_numpy(tensors, state, glob, max_norm=None, watch=(), sumsq=None, ema_decay=None):
     """The specification of one step (see the module's text).  tensors: one dict per tensor of the step with p, g, m, v (1-D float32
     arrays; p, m, v are updated in place), lr, beta1, beta2, eps and `state`, its index in `state` (a STATE_DTYPE array, updated in
     place); glob: a GLOBAL_DTYPE array of one element; watch: float32 arrays that are only scanned; sumsq: taken in place of this
-    function's own float64 sum of squares (whose order is NumPy's) - for a comparison in which the clip factor is in play."""
+    function's own float64 sum of squares (whose order is NumPy's) - for a comparison in which the clip factor is in play.
+    ema_decay: a row that carries `e` (a float32 array like p) has it moved towards the new p, in place."""
+    if ema_decay is not None and not 0.0 < ema_decay < 1.0:
+        raise ValueError(f"fused_adam_numpy: ema_decay {ema_decay} (0 < decay < 1, or None)")
     g_all = [np.asarray(t["g"]) for t in tensors]
     if any(g.dtype != np.float32 for g in g_all):
         raise TypeError("fused_adam_numpy: float32 gradients")
@@ -105,6 +116,16 @@ def fused_adam_numpy(tensors, state, glob, max_norm=None, watch=(), sumsq=None):
             m[...] = beta1 * m + om1 * gs
             v[...] = beta2 * v + (om2 * gs) * gs
             p[...] = p - step_size * (m / (np.sqrt(v) * inv + eps))
+            e = t.get("e") if ema_decay is not None else None
+            if e is not None:
+                omd = np.float32(one - ema_decay_at(ema_decay, st["step"][0]))
+                e[...] = e + omd * (p - e)
+
+
+def ema_decay_at(ema_decay, k):
+    """d_k, float64: the decay of the step that brings a tensor's count to k >= 1."""
+    k = np.float64(k)
+    return min(np.float64(ema_decay), (np.float64(1) + k) / (np.float64(10) + k))
 
 
 _ADAM_DEFAULTS = dict(weight_decay=0.0, amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
@@ -118,17 +139,23 @@ class FusedAdam(Optimizer):
     by the same launch (BatchNorm's running statistics).  step() never waits for the device; health() does, for six words.
     state_dict() has torch.optim.Adam's layout (step, exp_avg, exp_avg_sq per parameter) plus beta1_power / beta2_power, Python floats
     (float64: load_state_dict casts tensors to the parameter's dtype, and leaves numbers alone); a torch.optim.Adam state loads into it
-    (a missing power is beta ** step) and its state loads into torch.optim.Adam."""
+    (a missing power is beta ** step) and its state loads into torch.optim.Adam.
+    ema_decay: keep state[p]["ema"], an exponential moving average of p (the module's text), beside exp_avg: a clone of p taken before
+    the parameter's first update here - also where a loaded state has none (a torch.optim.Adam state, a run started without it; the
+    warm-up then goes on from the loaded step count).  It travels in state_dict(); torch.optim.Adam ignores the key and keeps it."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, maximize=False, max_grad_norm=None,
-                 watch=()):
+                 watch=(), ema_decay=None):
         if not 0.0 <= lr or not 0.0 <= eps or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"FusedAdam: lr {lr}, eps {eps}, betas {betas}")
         if max_grad_norm is not None and not max_grad_norm > 0:
             raise ValueError(f"FusedAdam: max_grad_norm {max_grad_norm} (a positive norm, or None)")
+        if ema_decay is not None and not 0.0 < ema_decay < 1.0:
+            raise ValueError(f"FusedAdam: ema_decay {ema_decay} (0 < decay < 1, or None)")
         defaults = dict(_ADAM_DEFAULTS, lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize)
         super().__init__(params, defaults)
         self.max_grad_norm = max_grad_norm
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.watch = tuple(watch)
         for b in self.watch:
             if not (isinstance(b, torch.Tensor) and b.dtype == torch.float32 and b.layout == torch.strided and b.is_contiguous()):
@@ -136,7 +163,7 @@ class FusedAdam(Optimizer):
         self._check()
         self._words = None          # STATE_DTYPE rows, one per parameter in group order: a uint8 tensor on the parameters' device
         self._global = None         # GLOBAL_DTYPE, there too
-        self._key = self._table = self._watch_table = self._host = None
+        self._key = self._table = self._watch_table = self._shadow_table = self._host = None
         self._counts = (0, 0, 0, 0)
 
     # ------------------------------------------------------------------------------------------------------------
@@ -239,7 +266,7 @@ class FusedAdam(Optimizer):
                 loss = closure()
         device = self._check()
         self._ensure_words(device)
-        used, grads, key, i = [], [], [], 0
+        used, grads, key, shadows, i = [], [], [], [], 0
         for group in self.param_groups:
             lr, (beta1, beta2), eps = float(group["lr"]), group["betas"], float(group["eps"])
             for p in group["params"]:
@@ -255,14 +282,20 @@ class FusedAdam(Optimizer):
                         st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                         st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                     m, v = st["exp_avg"], st["exp_avg_sq"]
+                    if self.ema_decay is not None:
+                        e = st.get("ema")
+                        if e is None:           # before the update: the first step here, or a loaded state without a shadow
+                            e = st["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
+                        shadows.append(e)       # (checked where a table is built from them: the walk stays cheap)
                     used.append(p)
                     grads.append(g)         # (alive until the launches are enqueued)
                     key.append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, float(beta1), float(beta2), eps, i))
                 i += 1
         key = [row for row in key if row[4] > 0]
         wkey = [(b.data_ptr(), b.numel()) for b in self.watch if b.numel() > 0]
+        shadows = [e for e in shadows if e.numel() > 0]
         if device.type == "cuda":
-            self._step_device(device, key, wkey)
+            self._step_device(device, key, wkey, shadows)
         else:
             self._step_host(used, grads, key)
         if used:    # a write through a raw pointer moves no version counter, and caches are keyed on it (lav_amd.rgb)
@@ -280,14 +313,27 @@ class FusedAdam(Optimizer):
             _, _, _, _, _, lr, beta1, beta2, eps, i = key[len(tensors)]
             tensors.append(dict(p=p.detach().view(-1).numpy(), g=g.detach().view(-1).numpy(), m=st["exp_avg"].view(-1).numpy(),
                                 v=st["exp_avg_sq"].view(-1).numpy(), lr=lr, beta1=beta1, beta2=beta2, eps=eps, state=i))
-        fused_adam_numpy(tensors, rows, glob, self.max_grad_norm, [b.detach().view(-1).numpy() for b in self.watch if b.numel() > 0])
+            if self.ema_decay is not None:
+                self._check_shadows([p], [st["ema"]])
+                tensors[-1]["e"] = st["ema"].view(-1).numpy()
+        fused_adam_numpy(tensors, rows, glob, self.max_grad_norm, [b.detach().view(-1).numpy() for b in self.watch if b.numel() > 0],
+                         ema_decay=self.ema_decay)
 
-    def _step_device(self, device, key, wkey):
+    def _check_shadows(self, used, shadows):
+        for p, e in zip(used, shadows):
+            if e.dtype != torch.float32 or e.device != p.device or e.shape != p.shape or not e.is_contiguous():
+                raise ValueError("FusedAdam: state['ema'] must be a dense float32 tensor of the parameter's shape, on its device")
+
+    def _step_device(self, device, key, wkey, shadows=()):
         from .. import ops
-        full = (tuple(key), tuple(wkey))
+        shadows = [e.data_ptr() for e in shadows]
+        full = (tuple(key), tuple(wkey), tuple(shadows))
         if full != self._key:
             # a fresh pinned buffer and a fresh device table per change: the copy is ordered on the stream behind the launches that
             # read the table it replaces, and a source is never rewritten
+            if shadows:
+                by_index = self._params()
+                self._check_shadows([by_index[row[9]] for row in key], [self.state[by_index[row[9]]]["ema"] for row in key])
             chunk = chunk_length()
             table = np.zeros(len(key), TENSOR_DTYPE)
             for r, row in enumerate(key):
@@ -296,21 +342,27 @@ class FusedAdam(Optimizer):
             for r, (ptr, n) in enumerate(wkey):
                 watch[r] = (ptr, n, 0, 0)
             chunks, wchunks = fill_chunks(table, chunk), fill_chunks(watch, chunk)
-            blob = np.concatenate([table.view(np.uint8), watch.view(np.uint8), np.zeros(16, np.uint8)])
+            ptrs = np.asarray(shadows, "<u8")       # (the EMA entry's pointer array, row-parallel to the table; 8-byte aligned behind 80 / 24)
+            blob = np.concatenate([table.view(np.uint8), watch.view(np.uint8), ptrs.view(np.uint8), np.zeros(16, np.uint8)])
             self._host = torch.from_numpy(blob).pin_memory()
             dev = self._host.to(device, non_blocking=True)
             self._table, self._watch_table = dev[:table.nbytes], dev[table.nbytes:table.nbytes + watch.nbytes]
+            self._shadow_table = dev[table.nbytes + watch.nbytes:table.nbytes + watch.nbytes + ptrs.nbytes]
             self._counts = (len(key), chunks, len(wkey), wchunks)
             self._key = full
         n, chunks, nw, wchunks = self._counts
+        if self.ema_decay is not None:
+            ops.optim_adam_ema_step(self._table, n, chunks, self._watch_table, nw, wchunks, self._words, self._global, self._shadow_table,
+                                    self.ema_decay, self.max_grad_norm)
+            return
         ops.optim_adam_step(self._table, n, chunks, self._watch_table, nw, wchunks, self._words, self._global, self.max_grad_norm)
 
 
 def make_adam(params, cfg, modules):
-    """The trainers' optimiser: torch.optim.Adam(params, lr=cfg.lr) as the reference has it, or - cfg.fused_optim, or a cfg.max_grad_norm,
-    which implies it - FusedAdam over the same parameters and lr, watching the float buffers of the trained `modules`."""
+    """The trainers' optimiser: torch.optim.Adam(params, lr=cfg.lr) as the reference has it, or - cfg.fused_optim, or a cfg.max_grad_norm
+    or a cfg.ema_decay, which imply it - FusedAdam over the same parameters and lr, watching the float buffers of the trained `modules`."""
     params = list(params)
-    if not (getattr(cfg, "fused_optim", False) or getattr(cfg, "max_grad_norm", None)):
+    if not (getattr(cfg, "fused_optim", False) or getattr(cfg, "max_grad_norm", None) or getattr(cfg, "ema_decay", None)):
         return torch.optim.Adam(params, lr=cfg.lr)
     seen, watch = set(), []
     for m in modules:
@@ -318,4 +370,17 @@ def make_adam(params, cfg, modules):
             if b.dtype == torch.float32 and id(b) not in seen:
                 seen.add(id(b))
                 watch.append(b)
-    return FusedAdam(params, lr=cfg.lr, max_grad_norm=getattr(cfg, "max_grad_norm", None) or None, watch=watch)
+    return FusedAdam(params, lr=cfg.lr, max_grad_norm=getattr(cfg, "max_grad_norm", None) or None, watch=watch,
+                     ema_decay=getattr(cfg, "ema_decay", None) or None)
+
+
+def ema_state_dict(module, optimizer):
+    """module.state_dict() with every parameter that has a shadow in `optimizer` (FusedAdam(ema_decay=)) replaced by a copy of it.  A
+    parameter without one - frozen, or never stepped - stays live, and so does every buffer (BatchNorm's running statistics and
+    num_batches_tracked are the live model's: "buffers: live")."""
+    sd = module.state_dict()
+    for name, p in module.named_parameters(remove_duplicate=False):
+        e = optimizer.state.get(p, {}).get("ema")
+        if e is not None and name in sd:
+            sd[name] = e.detach().clone().view_as(p)
+    return sd

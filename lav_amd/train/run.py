@@ -14,6 +14,7 @@ import torch.distributed as dist
 from . import log_view, state as run_state
 from .brake import BRA_LABELS, BrakeTrainer
 from .lav import LAV, TrainConfig
+from .optim import ema_state_dict
 from .synthetic import synthetic_bev_batch, synthetic_bra_batch, synthetic_lidar_batch, synthetic_seg_batch
 
 
@@ -307,6 +308,72 @@ _BRA = _Trainer(
     log=lambda info: dict(loss=round(info["loss"], 4), bra=info["bra"], pred_bra=round(info["pred_bra"], 4)), replicas=("bra_model",))
 
 
+def _val_tool(what):
+    """The evaluation tool of a trainer's own checkpoints (eval_common.run_cli's description)."""
+    if what in ("seg", "bra"):
+        from .evaluate_camera import _WHAT
+        return _WHAT[what]
+    if what == "bev":
+        from .evaluate_bev import TOOL
+        return TOOL
+    from .evaluate import TOOL
+    return TOOL
+
+
+def _val_argv(tool, args, paths):
+    """The tool's command line over --val-data-dir: the files just written, the tool's own defaults (the frame's precision) otherwise."""
+    argv = ["--config-path", args.config_path, "--data-dir", args.val_data_dir, "--num-workers", str(max(0, min(args.num_workers, 4)))]
+    for name, path in paths.items():
+        argv += [f"--{name}", path]
+    if args.val_max > 0:
+        argv += [f"--max-{tool['unit']}", str(args.val_max)]
+    return argv
+
+
+def _process_settings():
+    """What a validation must hand back as it found it, besides the generators: backend flags, default dtype, the precision stack."""
+    from .. import ops
+    mi = getattr(torch.backends, "miopen", None)
+    return dict(cudnn=(torch.backends.cudnn.benchmark, torch.backends.cudnn.deterministic, torch.backends.cudnn.allow_tf32, torch.backends.cudnn.enabled),
+                matmul=torch.backends.cuda.matmul.allow_tf32, miopen=getattr(mi, "immediate", None), dtype=torch.get_default_dtype(),
+                deterministic=(torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()),
+                grad=torch.is_grad_enabled(), precision=tuple(getattr(ops._precision_stack, "v", None) or ()))
+
+
+def validate(what, args, trainer, device, epoch, global_it, files):
+    """--val-data-dir, rank 0, right behind an epoch's checkpoint files: each of `files` = (weights, {name: path}) through the trainer's
+    own evaluation tool (eval_common.run_cli, in this process, on inference modules it builds from the files), the tool's JSON line
+    plus epoch / global_it / weights / buffers / checkpoints appended to SAVE_DIR/val.jsonl, one digest line printed.  The run goes on in
+    the bits it would have had: every generator lav_amd.train.state covers is put back (run_cli seeds torch), and a setting or a trainer
+    module's mode that an evaluation left changed ends the run."""
+    from .eval_common import run_cli
+    tool = _val_tool(what)
+
+    def modes():        # every nn.Module the trainer object holds, whatever it is called
+        return {f"{name}.{sub}": m.training for name, top in vars(trainer).items() if isinstance(top, torch.nn.Module)
+                for sub, m in top.named_modules()}
+
+    was = modes()
+    before, rng = _process_settings(), run_state._rng_state(device)
+    try:
+        for weights, paths in files:
+            for line in run_cli(tool, _val_argv(tool, args, paths), optional=("bev",) if what == "lidar" else (), echo=False):
+                line = dict(line, epoch=epoch, global_it=global_it, weights=weights, buffers="live", checkpoints=[paths[k] for k in sorted(paths)])
+                with open(os.path.join(args.save_dir, "val.jsonl"), "a") as f:
+                    f.write(json.dumps(line) + "\n")
+                rate = next((v for k, v in line.items() if k.endswith("_per_s")), None)
+                shown = {k: v for k, v in (line.get("summary") or {}).items() if isinstance(v, (int, float)) or v is None}
+                print(f"val epoch {epoch} it {global_it} weights: {weights} (buffers: live) {line['precision']} {line['data']}, {rate} {tool['unit']}/s: "
+                      + json.dumps(shown), flush=True)
+    finally:
+        run_state._set_rng_state(rng, device)
+    after, now = _process_settings(), modes()
+    if after != before or now != was:
+        moved = sorted(k for k in set(was) | set(now) if was.get(k) != now.get(k))
+        raise SystemExit(f"--val-data-dir: the evaluation left the process changed: settings {before} -> {after}; "
+                         f"modules whose mode moved: {[(k, was.get(k), now.get(k)) for k in moved[:8]]} ({len(moved)})")
+
+
 def main(what):
     """The command line of train_bev_v2.py ("bev"), train_full_v2.py ("lidar"), train_seg.py ("seg") and train_bra_v2.py ("bra"), from
     the parser to the teardown: the recorded routes under the config's `data_dir` are read by lav_amd.data (every rank its own shard of
@@ -314,7 +381,9 @@ def main(what):
     the reference's flags: --synthetic / --steps-per-epoch (seeded synthetic batches instead of a data set), --save-dir, and what the
     trainer's description (_lav, _SEG, _BRA) names, --log-dir (a picture of sample 0 per logged iteration), --fused-optim /
     --max-grad-norm / --max-skipped-steps (lav_amd.train.optim.FusedAdam: a step with a NaN / Inf gradient is skipped, a run that keeps
-    skipping ends) and --state-dir / --resume (lav_amd.train.state: everything a run needs to go on from an epoch boundary).  Without
+    skipping ends), --state-dir / --resume (lav_amd.train.state: everything a run needs to go on from an epoch boundary), --ema DECAY (a
+    moving average of the weights inside the fused step, saved as {name}_ema_{epoch}.th beside {name}_{epoch}.th; buffers: live) and
+    --val-data-dir / --val-max (each file just written through the trainer's own evaluation tool, into SAVE_DIR/val.jsonl).  Without
     these flags nothing changes, files written included."""
     t = {"seg": _SEG, "bra": _BRA}.get(what) or _lav(what)
     ap = argparse.ArgumentParser()
@@ -343,6 +412,19 @@ def main(what):
             ("--max-skipped-steps", dict(type=int, default=10, metavar="N",
                                          help="--fused-optim: end the run (non-zero exit) when more than N steps were skipped between two log "
                                               "iterations, or when a BatchNorm running statistic is not finite")),
+            ("--ema", dict(type=float, default=None, metavar="DECAY",
+                           help="keep an exponential moving average of the trained weights inside the fused step (e += (1 - d) (p - e), d = "
+                                "min(DECAY, (1 + k) / (10 + k)) at the parameter's step count k; a skipped step leaves it alone) and write it as "
+                                "{name}_ema_{epoch}.th wherever {name}_{epoch}.th is written: the same keys, frozen parameters and every buffer "
+                                "(BatchNorm running statistics) at their live values - buffers: live.  0 < DECAY < 1; implies --fused-optim")),
+            ("--val-data-dir", dict(default=None, metavar="DIR",
+                                    help="held-out routes: right after an epoch's checkpoint files are written, rank 0 evaluates them (the _ema_ "
+                                         "files too) with the trainer's own tool (eval_seg / eval_bra_v2 / eval_bev_v2 / eval_full_v2) at the frame's "
+                                         "precision, appends each JSON line with epoch, global_it, weights (raw | ema), buffers and checkpoints to "
+                                         "SAVE_DIR/val.jsonl and prints a digest; the run's bits do not change.  Needs a GPU and --config-path (the "
+                                         "loaders' keys).  The other ranks wait for rank 0's verdict at one collective: keep --val-max below the "
+                                         "process group's timeout")),
+            ("--val-max", dict(type=int, default=1000, metavar="N", help="--val-data-dir: units (frames / images) per evaluation; 0: all")),
             ("--state-dir", dict(default=None, metavar="DIR",
                                  help="whenever checkpoints are written, also write DIR/state_{epoch}.th: models, optimiser, scheduler, iteration "
                                       "counters, augmenter counts, random generators of every rank (the two newest are kept).  State is taken at epoch "
@@ -360,6 +442,17 @@ def main(what):
         if not args.max_grad_norm > 0:
             raise SystemExit(f"--max-grad-norm {args.max_grad_norm}: a positive norm")
         args.fused_optim = True
+    if args.ema is not None:
+        if not 0.0 < args.ema < 1.0:
+            raise SystemExit(f"--ema {args.ema}: a decay, 0 < DECAY < 1")
+        args.fused_optim = True
+    if args.val_data_dir is not None:
+        if args.device == "cpu":
+            ap.error("--val-data-dir with --device cpu: the models have no CPU inference path")
+        if args.val_max < 0:
+            ap.error(f"--val-max {args.val_max}")
+        if not (args.config_path and os.path.isfile(args.config_path)):
+            ap.error("--val-data-dir reads the loaders' keys from --config-path (with --synthetic too)")
     if args.resume == "auto" and not args.state_dir:
         raise SystemExit("--resume auto looks into --state-dir")
     # without a default (bev / lidar) the file named must exist, open() says so; a default that is not there (seg / bra) is no config
@@ -372,7 +465,7 @@ def main(what):
     if args.device == "cpu":
         device = torch.device("cpu")
     cfg = load_config(args.config_path if have_cfg else None, lr=args.lr, seed=args.seed, fused_optim=args.fused_optim,
-                      max_grad_norm=args.max_grad_norm, **t.overrides(args))
+                      max_grad_norm=args.max_grad_norm, ema_decay=args.ema, **t.overrides(args))
     if args.batch_size % world:
         raise SystemExit(f"global batch {args.batch_size} is not divisible by {world} ranks")
     per_rank = args.batch_size // world
@@ -383,6 +476,16 @@ def main(what):
         loader = get_data_loader(t.loader, args, rank=rank, world=world, **t.loader_kwargs(args))
         if len(loader) == 0:
             raise SystemExit(f"{args.config_path}: data_dir holds fewer {t.unit} than one batch of {args.batch_size}")
+    if args.val_data_dir is not None:       # before the first step: a directory without routes ends the run here
+        from .eval_common import held_out_units
+        if not torch.cuda.is_available():
+            raise SystemExit("--val-data-dir: no GPU visible; the models have no CPU inference path")
+        tool = _val_tool(what)
+        rng = run_state._rng_state(device)      # (the loaders seed NumPy where they list their routes)
+        units = held_out_units(tool, args.config_path, args.val_data_dir)
+        run_state._set_rng_state(rng, device)
+        if units == 0:
+            raise SystemExit(f"--val-data-dir {args.val_data_dir}: no recorded {tool['unit']} there")
     step = t.stepper(trainer, args, rank, world, device, loader)
     scheduler = getattr(trainer, f"{what}_scheduler", None)
 
@@ -409,6 +512,7 @@ def main(what):
     if args.fused_optim:
         skipped_seen = optimizer.health()["skipped"]
     t0, it0 = time.perf_counter(), global_it
+    val_failed = None
     for epoch in range(first_epoch, args.num_epoch):
         for batch in batches(epoch):
             drawn = writer is not None and global_it % args.num_per_log == 0
@@ -434,10 +538,30 @@ def main(what):
             scheduler.step()       # once per epoch (train_full_v2.py:33)
         if (epoch + 1) % args.num_per_save == 0 and rank == 0:
             os.makedirs(args.save_dir, exist_ok=True)
+            written = {"raw": {}, "ema": {}}
             for name in t.saves:
                 path = os.path.join(args.save_dir, f"{name}_{epoch + 1}.th")
                 torch.save(trainer.state_dict(name), path)
                 print(f"saved to {path}", flush=True)
+                written["raw"][name] = path
+            if args.ema is not None:
+                for name in t.saves:
+                    path = os.path.join(args.save_dir, f"{name}_ema_{epoch + 1}.th")
+                    torch.save(ema_state_dict(run_state._module(trainer, name), optimizer), path)
+                    print(f"saved to {path}", flush=True)
+                    written["ema"][name] = path
+            if args.val_data_dir is not None:
+                try:
+                    validate(what, args, trainer, device, epoch + 1, global_it, [(w, paths) for w, paths in written.items() if paths])
+                except (SystemExit, Exception) as e:      # (told to the other ranks first: they all end with it, none waits for a timeout)
+                    val_failed = f"validation after epoch {epoch + 1} failed: {e!r}" if not isinstance(e, SystemExit) else str(e.code)
+        if (epoch + 1) % args.num_per_save == 0 and args.val_data_dir is not None:
+            if world > 1:       # rank 0 validates, the others wait here for its verdict
+                verdict = [val_failed]
+                dist.broadcast_object_list(verdict, src=0)
+                val_failed = verdict[0]
+            if val_failed is not None:
+                raise SystemExit(val_failed)
         if (epoch + 1) % args.num_per_save == 0 and args.state_dir:     # every rank: the ranks' generator states are gathered
             st = run_state.capture(trainer, what, args, epoch + 1, global_it, getattr(step, "augmenters", ()), rank, world)
             if rank == 0:
@@ -464,6 +588,8 @@ def main(what):
     if args.fused_optim:
         health = optimizer.health()
         summary.update(fused_optim=True, skipped_steps=health["skipped"], last_grad_norm=health["grad_norm"])
+    if args.ema is not None:
+        summary["ema_decay"] = args.ema
     if rank == 0:
         print(json.dumps(summary))
     if world > 1:

@@ -16,7 +16,7 @@ import torch.distributed as dist
 
 FORMAT = 1
 KEEP = 2                    # state files kept in --state-dir
-_SHARED = ("batch_size", "seed", "lr", "synthetic", "steps_per_epoch", "augment", "fused_optim", "max_grad_norm")
+_SHARED = ("batch_size", "seed", "lr", "synthetic", "steps_per_epoch", "augment", "fused_optim", "max_grad_norm", "ema")
 _OWN = {"bev": ("perceive_only", "motion_only", "max_points", "bev_on_device", "deterministic"), "seg": (), "bra": ()}
 _OWN["lidar"] = _OWN["bev"]
 
