@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 48
+#define LAV_ABI_VERSION 49
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -1245,6 +1245,22 @@ int lav_optim_adam_step(const lav_optim_tensor *table, int ntensors, int total_c
 int lav_optim_adam_ema_step(const lav_optim_tensor *table, int ntensors, int total_chunks, const lav_optim_watch *watch, int nwatch,
                             int watch_chunks, lav_optim_state *state, lav_optim_global *global, double max_norm, float *const *shadow,
                             double ema_decay, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * lav_eval_resample (ABI 49; the eval tools' --bootstrap, lav_amd.ops.eval_resample): block-bootstrap replicates of a table of
+ * accumulator rows.  rows [R][W] int64 in DEVICE memory, one row per block of consecutive frames (EvaluatorBase.resample); out
+ * [B + 1][W] int64 in DEVICE memory, overlapping no row; both 8-byte aligned.
+ *     out[0][w] = sum over r of rows[r][w]                       the identity replicate: no draws, the run's own accumulator
+ *     out[b][w] = sum over j < R of rows[idx(b, j)][w]           b = 1 .. B
+ *     idx(b, j) = (u * R) >> 32 as a 64-bit product, u = word j & 3 of Philox4x32-10 at counter (j >> 2, b, 0x52534D50, 0) and key
+ *                 (seed & 0xffffffff, seed >> 32) - lav_augment_u8's generator
+ * The multiply-high map favours some rows by at most R / 2^32 (below 2.5e-4 at the cap).  Sums are int64 sums modulo 2^64: any
+ * split of the work gives the same bits.  1 <= R <= 2^20, W >= 1, B >= 0, R W 8 <= 4 GiB; anything else is refused before the launch.
+ * One launch on `stream`: a workgroup per replicate and tile of up to 64 columns, which draws the replicate's indices into LDS
+ * lav_eval_resample_chunk() at a time; no atomics, no floating point, no dependency between workgroups, nothing copied to the host.
+ * Specification: lav_amd.train.eval_common.eval_resample_numpy, equal in every word. */
+int lav_eval_resample_chunk(void);
+int lav_eval_resample(const long long *rows, int R, int W, int B, unsigned long long seed, long long *out, void *stream);
 
 #ifdef __cplusplus
 }

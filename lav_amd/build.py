@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblav_amd.so")
-SOURCES = ["misc.hip", "pillar.hip", "paint.hip", "paint_frames.hip", "gru.hip", "gru_seq.hip", "conv.hip", "conv_f16.hip", "conv_pair.hip", "conv_run.hip", "conv_tile.hip", "deconv.hip", "crop.hip", "frame.hip", "heads_peaks.hip", "attn.hip", "bn_train.hip", "conv_wgrad.hip", "upconv.hip", "conv_pair_train.hip", "augment.hip", "bev_stack.hip", "debug_view.hip", "log_view.hip", "eval_metrics.hip", "eval_camera.hip", "eval_plans.hip", "eval_drive.hip", "eval_distill.hip", "eval_det.hip", "jpeg.hip", "optim.hip", "erfnet_edge.hip"]
+SOURCES = ["misc.hip", "pillar.hip", "paint.hip", "paint_frames.hip", "gru.hip", "gru_seq.hip", "conv.hip", "conv_f16.hip", "conv_pair.hip", "conv_run.hip", "conv_tile.hip", "deconv.hip", "crop.hip", "frame.hip", "heads_peaks.hip", "attn.hip", "bn_train.hip", "conv_wgrad.hip", "upconv.hip", "conv_pair_train.hip", "augment.hip", "bev_stack.hip", "debug_view.hip", "log_view.hip", "eval_metrics.hip", "eval_camera.hip", "eval_plans.hip", "eval_drive.hip", "eval_distill.hip", "eval_det.hip", "eval_resample.hip", "jpeg.hip", "optim.hip", "erfnet_edge.hip"]
 # Parity-critical arithmetic (float32 cell ids, decoration, camera projection; bev_stack.hip's float64 inverse maps) must round every multiply and
 # add separately, like the oracle: these translation units are compiled with FMA contraction off (the header
 # helpers __fadd_rn/__fmul_rn are plain operators that clang would otherwise fuse after inlining).

@@ -15,6 +15,7 @@
 // The elastic warp's raw displacement field is such a function too; it is staged in LDS once instead of 25 Philox calls per pixel.
 // The op list is uniform per workgroup: every branch on it is scalar.
 #include "common.hpp"
+#include "philox.hpp"
 
 #pragma clang fp contract(off)
 
@@ -31,16 +32,6 @@ struct Rect {
     __device__ __forceinline__ int count() const { return (x1 - x0) * (y1 - y0); }
 };
 
-__device__ __forceinline__ void philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&o)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
 __device__ __forceinline__ float uniform24(unsigned word) { return (float)(word >> 8) * 5.9604644775390625e-8f; }          // [0, 1)
 __device__ __forceinline__ float uniform24_open(unsigned word) { return (float)((word >> 8) + 1u) * 5.9604644775390625e-8f; }  // (0, 1]
 __device__ __forceinline__ float gauss(unsigned a, unsigned b) {

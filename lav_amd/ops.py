@@ -824,6 +824,37 @@ def eval_det(acc: torch.Tensor, rows: torch.Tensor, locs: torch.Tensor, typs: to
     return acc
 
 
+EVAL_RESAMPLE_MAX_ROWS = 1 << 20          # lav_eval_resample: idx = (u * R) >> 32 favours rows by at most R / 2^32
+EVAL_RESAMPLE_MAX_BYTES = 4 << 30         # of the row table
+
+
+def eval_resample_chunk() -> int:
+    """How many of a replicate's draws lav_eval_resample holds in LDS at a time (lav_eval_resample_chunk; host only, no device needed)."""
+    return int(_lib.load().lav_eval_resample_chunk())
+
+
+def eval_resample(rows: torch.Tensor, B: int, seed: int) -> torch.Tensor:
+    """Block-bootstrap replicates of a row table, one launch on the current stream (lav_eval_resample): rows (R, W) int64 in HBM, read
+    where they are -> (B + 1, W) int64 in HBM.  out[0] = rows.sum(0), the identity replicate; out[b], b = 1 .. B, is the sum of R rows
+    drawn with replacement, idx(b, j) = (u * R) >> 32 with u = word j & 3 of Philox4x32-10 at counter (j >> 2, b, 0x52534D50, 0) and key
+    (seed low word, seed high word).  That map favours some rows by at most R / 2^32, below 2.5e-4 at the cap of 2^20 rows.  Word for
+    word lav_amd.train.eval_common.eval_resample_numpy.  Wrong shapes, dtypes or devices raise ValueError before anything is launched."""
+    if not isinstance(rows, torch.Tensor) or not rows.is_cuda:
+        raise ValueError("eval_resample: rows must be a tensor in HBM (cuda/hip device); lav_amd.ops has no CPU path "
+                         "(lav_amd.train.eval_common.eval_resample_numpy is the CPU specification)")
+    if rows.dtype != torch.int64 or rows.dim() != 2 or not rows.is_contiguous():
+        raise ValueError(f"eval_resample: rows must be a contiguous int64 tensor of shape (R, W), got {rows.dtype} {tuple(rows.shape)}")
+    R, W = rows.shape
+    B = int(B)
+    if not 1 <= R <= EVAL_RESAMPLE_MAX_ROWS or W < 1 or R * W * 8 > EVAL_RESAMPLE_MAX_BYTES:
+        raise ValueError(f"eval_resample: a table of {R} x {W} words (1 .. 2^20 rows, at least one word, at most 4 GiB)")
+    if not 0 <= B < (1 << 31) - 1:
+        raise ValueError(f"eval_resample: {B} replicates")
+    out = torch.empty((B + 1, W), dtype=torch.int64, device=rows.device)
+    check(_lib.load().lav_eval_resample(_ptr(rows), R, W, B, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out), _stream()), "lav_eval_resample")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ GRU decoders
 def gru_cast(embd, w_ih, w_hh, b_ih, b_hh, mlp_w, mlp_b, T: int):
     """embd (B, E); stacked per-command GRU/MLP weights -> (B, num_cmds, T, 2)."""

@@ -243,6 +243,11 @@ class SegEvaluator(EvaluatorBase):
         super().__init__(seg_model, SEG, precision, device)
         self.images_per_call = max(1, int(images_per_call))
         self.images = 0
+        self._ahead = 0
+
+    def units(self) -> int:
+        """The images of the calls before this one (EvaluatorBase.resample's rows: a call's images land in one row)."""
+        return self.images + self._ahead
 
     @torch.no_grad()
     def batch(self, rgb, sem, limit=None):
@@ -257,7 +262,9 @@ class SegEvaluator(EvaluatorBase):
             with ops.precision(self.code):
                 logits = self.model(part)
             self.in_force.add(erfnet_arithmetic(self.model.erfnet, self.code, part.shape))
+            self._ahead = j
             self._add("eval_seg", eval_seg_numpy, "seg", logits, labels[j:j + self.images_per_call], 1)
+        self._ahead = 0
         self.images += x.shape[0]
 
     def run(self, batches, max_images=None) -> int:
@@ -277,6 +284,11 @@ class BrakeEvaluator(EvaluatorBase):
         super().__init__(bra_model, BRA, precision, device)
         self.threshold = float(threshold)
         self.frames = 0
+        self._ahead = 0
+
+    def units(self) -> int:
+        """The frames before the one whose three launches are being added (EvaluatorBase.resample's rows)."""
+        return self.frames + self._ahead
 
     @torch.no_grad()
     def batch(self, rgb, tel_rgb, sem, tel_sem, bra, limit=None):
@@ -296,9 +308,11 @@ class BrakeEvaluator(EvaluatorBase):
             if pred is None:
                 raise RuntimeError("BrakeEvaluator: the brake net has no fused classifier path here (eval mode, in HBM, batch 1)")
             self.in_force.add(trunk_arithmetic(m.conv_backbone, self.code))
+            self._ahead = i
             self._add("eval_seg", eval_seg_numpy, "wide", logit1, sem[i:i + 1], SEG_SCALE)
             self._add("eval_seg", eval_seg_numpy, "tele", logit2, tel_sem[i:i + 1], SEG_SCALE)
             self._add("eval_scores", eval_scores_numpy, SCORES, pred.contiguous(), flags[i:i + 1], self.threshold, self.layout.nbins)
+        self._ahead = 0
         self.frames += wide.shape[0]
 
     def run(self, batches, max_frames=None) -> int:

@@ -447,7 +447,7 @@ TOOL = dict(
            ("--iou", dict(type=float, nargs="+", default=list(IOU_THRESHOLDS), metavar="T", help="up to 3 IoU thresholds (arms 1 ..)")),
            ("--range-edges", dict(type=float, nargs="+", default=list(RANGE_EDGES_M), metavar="M", help="up to 3 range edges from the ego, metres")),
            ("--nbins", dict(type=int, default=NBINS, help="bins of the score histograms"))],
-    build=_build, batches=_batches, make_evaluator=_make, line=_line,
+    build=_build, batches=_batches, make_evaluator=_make, line=_line, contrasts=(("dense", "peaks"),),      # (--bootstrap, --heads both: paired)
     keys=("what", "heads", "measured", "precision", "data", "frames_per_s", "match_radius_m", "iou_thresholds", "range_edges_m", "heading_edges_deg",
           "note", "summary", "counters"))
 

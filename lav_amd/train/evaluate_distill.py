@@ -401,6 +401,7 @@ TOOL = dict(
     build=_build, batches=_batches, make_evaluator=lambda lav, name, args: DistillEvaluator(lav, precision=name, others=args.others),
     line=lambda ev, acc, args, cfg: dict(others=args.others, teacher="--bev " + args.bev if args.bev else "the uniplanner checkpoint's", note=NOTE,
                                          summary=summarise(acc, cfg.num_plan)),
+    contrasts=(("student", "teacher"),),          # (--bootstrap: the paired difference of the two sections' metrics)
     keys=("what", "precision", "asked", "others", "teacher", "note", "data", "batch_size", "frames_per_s", "summary", "counters"))
 
 
