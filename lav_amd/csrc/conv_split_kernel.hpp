@@ -128,6 +128,10 @@ __device__ __forceinline__ void split_body(const SplitArgs &a, unsigned char *sm
     const int ngroups = (nsteps + G - 1) / G;                 // a group = the G taps between two barriers
     const int ngroups_pad = (ngroups + WFM - 1) / WFM * WFM;  // barriers every role executes (the weight waves' loop is unrolled by WFM)
     const int *toff = a.toff + cls * a.taps_per_class;
+    // One step per chunk (a 1x1 layer, the one-tap parity class of a 3x3 stride-2 data gradient): step 1 already belongs to chunk 1, so
+    // chunk 2 is due at the barrier that closes group 0 - and its buffer is chunk 0's, which the compute waves read for step 0 AFTER
+    // the barrier that opens the loop.  Every role then executes one more barrier behind that first fetch (workgroup-uniform).
+    const bool one_step_chunks = ntaps == 1;
 
     if (wid == 4 || wid == 5) {
         // ------------------------------------------------------------------------------ weight waves (2 x 64 threads)
@@ -201,6 +205,7 @@ __device__ __forceinline__ void split_body(const SplitArgs &a, unsigned char *sm
 #pragma unroll
             for (int g = 0; g < G; ++g) request(wreg[f][g]);
         lds_barrier();
+        if (one_step_chunks) lds_barrier();
         // group k: deposit group k+2 (set k % WFM), then request group k+2+WFM into the same set
         for (int k = 0; k < ngroups_pad; k += WFM) {
 #pragma unroll
@@ -280,7 +285,8 @@ __device__ __forceinline__ void split_body(const SplitArgs &a, unsigned char *sm
         // then take the loads of chunk c+3.
         // During group k the compute waves fetch taps kG+1 .. (k+1)G, so the chunks below the one of tap kG+1 are free, and the
         // barrier that closes the group promises the chunks up to tap (k+2)G.  Host: 2G <= taps + 1, i.e. those 2G taps touch
-        // at most two chunks - the two LDS buffers.  A chunk is converted as soon as its buffer is free, from registers whose
+        // at most two chunks - the two LDS buffers.  (Group 0 also fetches tap 0, of chunk 0: with one step per chunk that is the
+        // buffer chunk 2 is due in - one_step_chunks' extra barrier.)  A chunk is converted as soon as its buffer is free, from registers whose
         // loads were issued when the previous chunk was converted (about a chunk of matrix work earlier).
         auto issue_loads = [&](int sc) __attribute__((always_inline)) { issue_loads_to(v, sc); };
         auto convert_store = [&](int sc) __attribute__((always_inline)) { convert_store_from(v, sc); };
@@ -299,6 +305,7 @@ __device__ __forceinline__ void split_body(const SplitArgs &a, unsigned char *sm
         }
         int conv_next = 2;
         lds_barrier();
+        if (one_step_chunks) lds_barrier();   // (chunk 0 has been fetched: group 0 may convert chunk 2 into its buffer)
         int m_c = 0, m_t = 1;   // chunk / tap of micro-step kG+1
         if (m_t >= ntaps) { m_t -= ntaps; ++m_c; }
         for (int k = 0; k < ngroups; ++k) {
@@ -397,6 +404,7 @@ __device__ __forceinline__ void split_body(const SplitArgs &a, unsigned char *sm
         };
         SplitOps<MP, MC, NPC> o0, o1;
         if (nsteps > 0) fetch(o0);
+        if (one_step_chunks) lds_barrier();   // (waits for the fetch: lgkmcnt(0))
         // U taps per iteration (static register sets, a barrier after every G-th).  The operand fetch is unconditional - past
         // the last tap it reads stale LDS that nobody uses - so that fetch and matrix instructions share one basic block, and
         // the LDS reads of the next tap are spread between this tap's matrix instructions (one read per NM / NR of them):

@@ -262,10 +262,10 @@ class _Conv2d(torch.autograd.Function):
         if ctx.needs_input_grad[0] and lav_dgrad:
             kh, kw = w.shape[2], w.shape[3]
             # the adjoint's output_padding = the rows / columns of x the strided forward never reached, PER DIMENSION; the transposed
-            # plan takes one value for both and requires it below the stride - anything else goes to torch
+            # plan takes one value for both, requires it below the stride and has no dilation - anything else goes to torch
             oph = x.shape[2] - ((dy.shape[2] - 1) * stride - 2 * padding[0] + dilation[0] * (kh - 1) + 1)
             opw = x.shape[3] - ((dy.shape[3] - 1) * stride - 2 * padding[1] + dilation[1] * (kw - 1) + 1)
-            if oph == opw and 0 <= oph < max(stride, 1) and dy.numel() > 0:
+            if oph == opw and 0 <= oph < max(stride, 1) and tuple(dilation) == (1, 1) and dy.numel() > 0:
                 dx = _conv_engine("dgrad", w, stride, padding, dilation, True, oph)(dy, amax_in=am_dy)
                 if dx.shape != x.shape:
                     raise RuntimeError(f"convolution data gradient {tuple(dx.shape)} != input {tuple(x.shape)}")

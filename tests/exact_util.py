@@ -663,17 +663,20 @@ class UpconvCase:
 
 
 # ---------------------------------------------------------------------------------------------- weight gradient
-WGRAD_GEOMS = [(2, 64, 64, 20, 32, 1), (2, 64, 128, 20, 24, 2)]             # B, cin, cout, H, W, stride (3x3, pad 1)
+# B, cin, cout, H, W, stride (3x3, pad 1); a seventh entry is the kernel size k (pad k // 2): the 7x7 stride-2 stem, one ky per task
+WGRAD_GEOMS = [(2, 64, 64, 20, 32, 1), (2, 64, 128, 20, 24, 2), (2, 64, 64, 24, 24, 2, 7)]
 
 
 class WgradCase:
     """lav_conv_wgrad (bf16x6) / lav_conv_wgrad_amax (two fp16 pieces): dw = sum over (n, y, x) of dy * x.  Class A: integers on both sides.
-    Class D (bf16 entry) / B (fp16 entry): dy has ONE nonzero element per output channel, +- a power of two, and x carries the pattern."""
+    Class D (bf16 entry) / B (fp16 entry): dy has ONE nonzero element per output channel, +- a power of two, and x carries the pattern.
+    k: the kernel size (k x k, pad k // 2)."""
 
-    def __init__(self, B, cin, cout, H, W, stride, key):
-        self.name = f"wgrad B {B} {cin}->{cout} {H}x{W} s{stride} / class {key}"
-        rng = rng_of("wgrad", B, cin, cout, H, W, stride, key)
+    def __init__(self, B, cin, cout, H, W, stride, key, k=3):
+        self.name = f"wgrad B {B} {cin}->{cout} {H}x{W} s{stride}{'' if k == 3 else f' k{k}'} / class {key}"
         self.geom = (B, cin, cout, H, W, stride)
+        self.k = k
+        rng = rng_of("wgrad", B, cin, cout, H, W, stride, key, *(() if k == 3 else (k,)))
         ys = (B, cout, H // stride, W // stride)
         if key == "A":
             x, dy = integers(rng, (B, cin, H, W), 7), integers(rng, ys, 3)
@@ -684,7 +687,116 @@ class WgradCase:
 
     def forward(self, mul):
         B, cin, cout, H, W, s = self.geom
-        return mul(lambda a, b: torch.nn.grad.conv2d_weight(a, (cout, cin, 3, 3), b, stride=s, padding=1), self.x.double(), self.dy.double())
+        k = self.k
+        return mul(lambda a, b: torch.nn.grad.conv2d_weight(a, (cout, cin, k, k), b, stride=s, padding=k // 2), self.x.double(), self.dy.double())
+
+
+# ---------------------------------------------------------------------------------------------- the training convolution
+# One autograd step of lav_amd.train.hipnn.conv2d: forward (lav_conv2d), data gradient (the transposed lav_conv2d plan over the same
+# weight tensor), weight gradient (lav_conv_wgrad / lav_conv_wgrad_amax).  dgrad / wgrad: who must take the leg - "lib" or "torch" -
+# by the conditions of _Conv2d.backward and _wgrad_hip with LAV_TRAIN_WGRAD_MINPIX=1 (None: the leg is not asked for).
+TrainGeom = namedtuple("TrainGeom", "name B cin cout kh kw stride ph pw dh dw H W x_grad env dgrad wgrad")
+
+
+def _tg(name, B, cin, cout, k, s, p, H, W, dgrad, wgrad, d=(1, 1), x_grad=True, env=()):
+    return TrainGeom(name, B, cin, cout, *k, s, *p, *d, H, W, x_grad, tuple(env), dgrad if x_grad else None, wgrad)
+
+
+TRAIN_CONV_GEOMS = [
+    _tg("a 3x3 s1 p1 64->64 12x16", 2, 64, 64, (3, 3), 1, (1, 1), 12, 16, "lib", "lib"),
+    _tg("b 3x3 s2 p1 64->128 20x24 op1", 2, 64, 128, (3, 3), 2, (1, 1), 20, 24, "lib", "lib"),
+    _tg("c 3x3 s2 p1 64->128 21x25 op0", 2, 64, 128, (3, 3), 2, (1, 1), 21, 25, "lib", "torch"),
+    _tg("d 3x3 s2 p1 128->64 21x24 oph0 opw1", 1, 128, 64, (3, 3), 2, (1, 1), 21, 24, "torch", "torch"),
+    _tg("e 3x3 s2 p1 128->64 20x24 strided dgrad on torch", 1, 128, 64, (3, 3), 2, (1, 1), 20, 24, "torch", "lib",
+        env=(("LAV_TRAIN_DGRAD_STRIDED", "torch"),)),
+    _tg("f 7x7 s2 p3 64->64 24x24", 2, 64, 64, (7, 7), 2, (3, 3), 24, 24, "lib", "lib"),
+    _tg("g 7x7 s2 p3 64->64 25x27", 2, 64, 64, (7, 7), 2, (3, 3), 25, 27, "lib", "torch"),
+    _tg("h 7x7 s2 p3 3->64 24x32 x without gradient", 2, 3, 64, (7, 7), 2, (3, 3), 24, 32, "lib", "torch", x_grad=False),
+    _tg("h 7x7 s2 p3 3->64 24x32", 2, 3, 64, (7, 7), 2, (3, 3), 24, 32, "lib", "torch"),
+    _tg("i 3x1 p(1,0) 64->64 12x16", 2, 64, 64, (3, 1), 1, (1, 0), 12, 16, "lib", "torch"),
+    _tg("j 3x3 s1 p0 64->64 10x14", 2, 64, 64, (3, 3), 1, (0, 0), 10, 14, "lib", "torch"),
+    _tg("k 3x3 dilation 2 p2 16->16 12x16", 2, 16, 16, (3, 3), 1, (2, 2), 12, 16, "torch", "torch", d=(2, 2)),
+    _tg("l 3x3 s1 p1 48->40 13x17", 2, 48, 40, (3, 3), 1, (1, 1), 13, 17, "lib", "torch"),
+    _tg("m 7x7 s2 p3 384->64 24x24", 1, 384, 64, (7, 7), 2, (3, 3), 24, 24, "lib", "lib"),
+]
+
+
+class _Leg:
+    """One product of a TrainConvCase as a case of its own (`preconditions` and the host checks take one result)."""
+
+    def __init__(self, case, n):
+        self.case, self.n = case, n
+        self.name = f"{case.name} / {('y', 'dx', 'dw')[n]}"
+
+    def forward(self, mul):
+        return self.case.product(n=self.n, mul=mul)
+
+
+class TrainConvCase:
+    """One autograd step of hipnn.conv2d at geometry g on class A: x in [-7, 7], w and dy in [-3, 3] ([-2, 2] on every side for
+    K = cin kh kw > 4608, ConvLayerCase's rule - x and w ARE a ConvLayerCase's).  Three bilinear products: F.conv2d, its data gradient
+    written as F.conv_transpose2d with the output padding of each dimension, torch.nn.grad.conv2d_weight."""
+
+    def __init__(self, g: TrainGeom, key: str = "A"):
+        assert key == "A", "the three legs share their operands: integers only"
+        self.g, self.key = g, key
+        self.name = f"train conv {g.name} / class {key}"
+        self.fwd = ConvLayerCase(ConvGeom(g.name, g.B, g.cin, g.cout, g.kh, g.kw, g.stride, g.ph, g.pw, g.dh, g.dw, False, 0, g.H, g.W, "", ()), key)
+        self.x, self.w = self.fwd.x, self.fwd.w
+        oh, ow = self.fwd.out_hw()
+        rng = rng_of("train conv", tuple(g[1:13]), key)
+        self.dy = integers(rng, (g.B, g.cout, oh, ow), 3 if g.cin * g.kh * g.kw <= 4608 else 2).float()
+        # the rows / columns of x the strided forward never reached
+        self.out_pad = (g.H - ((oh - 1) * g.stride - 2 * g.ph + g.dh * (g.kh - 1) + 1), g.W - ((ow - 1) * g.stride - 2 * g.pw + g.dw * (g.kw - 1) + 1))
+
+    def product(self, n, mul):
+        g = self.g
+        s, p, d = g.stride, (g.ph, g.pw), (g.dh, g.dw)
+        x, w, dy = self.x.double(), self.w.double(), self.dy.double()
+        if n == 0:
+            return mul(self.fwd.op, x, w)
+        if n == 1:
+            return mul(lambda a, b: F.conv_transpose2d(a, b, None, s, p, self.out_pad, 1, d), dy, w)
+        return mul(lambda a, b: torch.nn.grad.conv2d_weight(a, tuple(w.shape), b, stride=s, padding=p, dilation=d), x, dy)
+
+    def legs(self):
+        return [_Leg(self, n) for n in range(3)]
+
+    def forward(self, mul):
+        """(y, dx, dw) in float64 (dx also where the step does not ask for it)."""
+        return tuple(self.product(n, mul) for n in range(3))
+
+
+# One step per 16-channel chunk on the split kernel (a 1x1 layer; the one-tap parity class of b and c above is the other instance):
+# the third chunk is staged into the first one's buffer while the first tap is still being fetched unless the kernel waits.
+ONE_STEP_GEOM = ConvGeom("1x1 s1 128->128 24x24 (one step per chunk)", 2, 128, 128, 1, 1, 1, 0, 0, 1, 1, False, 0, 24, 24, "", ())
+
+TRAIN_CONVT_GEOMS = [(2, 128, 128, 4, 2, 1, 0, 10, 12), (2, 128, 64, 4, 4, 0, 0, 5, 6), (2, 64, 128, 3, 2, 1, 1, 8, 8)]   # B, cin, cout, k, stride, pad, out_pad, H, W
+
+
+class TrainConvTCase(TrainConvCase):
+    """One autograd step of hipnn._ConvT2d (LAV_TRAIN_CONVT=hip) on class A: forward on the transposed plan (x and w ARE a transposed
+    ConvLayerCase's), data gradient = the ordinary convolution of dy with the same tensor; the weight gradient is torch's."""
+
+    def __init__(self, B, cin, cout, k, stride, pad, out_pad, H, W):
+        self.geom = (B, cin, cout, k, stride, pad, out_pad, H, W)
+        self.name = f"train convT {k}x{k} s{stride} p{pad} op{out_pad} {cin}->{cout} {H}x{W} / class A"
+        self.fwd = ConvLayerCase(ConvGeom(self.name, B, cin, cout, k, k, stride, pad, pad, 1, 1, True, out_pad, H, W, "", ()), "A")
+        self.x, self.w = self.fwd.x, self.fwd.w
+        self.dy = integers(rng_of("train convT", self.geom), (B, cout, *self.fwd.out_hw()), 3).float()
+
+    def product(self, n, mul):
+        B, cin, cout, k, s, p, op, H, W = self.geom
+        if n == 0:
+            return mul(self.fwd.op, self.x.double(), self.w.double())
+        return mul(lambda a, b: F.conv2d(a, b, None, s, p), self.dy.double(), self.w.double())
+
+    def legs(self):
+        return [_Leg(self, n) for n in range(2)]
+
+    def forward(self, mul):
+        """(y, dx) in float64."""
+        return tuple(self.product(n, mul) for n in range(2))
 
 
 # ---------------------------------------------------------------------------------------------- the BEV backbone

@@ -88,7 +88,7 @@ def test_conv_geometries_cover_the_lists_of_test_gpu_conv():
     assert all(g.B == 2 for g in GEOMS)
 
 
-@pytest.mark.parametrize("g", [g for g in GEOMS if (g.kh, g.stride) == (7, 2) and g.cin >= 32 and g.H <= 50], ids=lambda g: g.name)
+@pytest.mark.parametrize("g", [g for g in GEOMS if (g.kh, g.stride) == (7, 2) and not g.transposed and g.cin >= 32 and g.H <= 50], ids=lambda g: g.name)
 def test_stem_case_past_the_batch_limit(g):
     check_case(E.ConvLayerCase(g, "A", batch=5), PRECISIONS)
 
@@ -140,13 +140,72 @@ def test_deconv_and_upconv_cases(key):
 
 @pytest.mark.parametrize("geom", E.WGRAD_GEOMS)
 def test_wgrad_cases(geom):
-    case = E.WgradCase(*geom, "A")
+    case = E.WgradCase(*geom[:6], "A", *geom[6:])
     ref = check_case(case, (BF16X6, F16X3))
     indexing_faults_change(case, ref)
     for key, p in (("D", BF16X6), ("B", F16X3)):
-        case = E.WgradCase(*geom, key)
+        case = E.WgradCase(*geom[:6], key, *geom[6:])
         ref = check_case(case, (p,))
         dropped_products_change(case, (p,), ref, side=0)
+
+
+@pytest.mark.parametrize("g", E.TRAIN_CONV_GEOMS, ids=lambda g: g.name)
+def test_train_conv_cases(g):
+    """One step of hipnn.conv2d: every one of the three products (forward, data gradient, weight gradient) is exactly representable at
+    both training precisions, and a shifted tap, a dropped k-block and a zeroed halo column each change dx."""
+    case = E.TrainConvCase(g)
+    y, dx, dw = case.legs()
+    refs = [check_case(leg, (BF16X6, F16X3)) for leg in (y, dx, dw)]
+    assert all(torch.equal(a, b) for a, b in zip(case.forward(E.Plain()), refs))
+    assert tuple(refs[0].shape) == tuple(case.dy.shape) and tuple(refs[1].shape) == tuple(case.x.shape) and tuple(refs[2].shape) == tuple(case.w.shape)
+    indexing_faults_change(dx, refs[1])
+    # the reference IS autograd's: the three products are the step's y and its two gradients
+    xr, wr = case.x.double().requires_grad_(True), case.w.double().requires_grad_(True)
+    yr = torch.nn.functional.conv2d(xr, wr, None, g.stride, (g.ph, g.pw), (g.dh, g.dw))
+    gx, gw = torch.autograd.grad(yr, (xr, wr), case.dy.double())
+    assert torch.equal(yr.detach(), refs[0]) and torch.equal(gx, refs[1]) and torch.equal(gw, refs[2])
+
+
+def test_one_step_chunk_case():
+    case = E.ConvLayerCase(E.ONE_STEP_GEOM, "A")
+    ref = check_case(case, (BF16X6, F16X3))
+    must_change(case, E.FaultLastKBlock(), ref, "the last k-block dropped")
+    # what the race this case is for does: the third chunk where the first one belongs
+    a = case.x.double().clone()
+    a[:, :16] = a[:, 32:48]
+    assert not torch.equal(case.op(a, case.w.double()), ref)
+
+
+@pytest.mark.parametrize("geom", E.TRAIN_CONVT_GEOMS)
+def test_train_conv_transpose_cases(geom):
+    case = E.TrainConvTCase(*geom)
+    y, dx = case.legs()
+    refs = [check_case(leg, (BF16X6, F16X3)) for leg in (y, dx)]
+    assert tuple(refs[1].shape) == tuple(case.x.shape)
+    indexing_faults_change(y, refs[0])
+    indexing_faults_change(dx, refs[1])
+    B, cin, cout, k, s, p, op, H, W = geom
+    xr = case.x.double().requires_grad_(True)
+    yr = torch.nn.functional.conv_transpose2d(xr, case.w.double(), None, s, p, op)
+    assert torch.equal(yr.detach(), refs[0]) and torch.equal(torch.autograd.grad(yr, xr, case.dy.double())[0], refs[1])
+
+
+def test_train_conv_geometries_name_who_takes_each_leg():
+    """The table's last two columns restate the conditions of hipnn._Conv2d.backward and hipnn._wgrad_hip (LAV_TRAIN_WGRAD_MINPIX=1)."""
+    for g in E.TRAIN_CONV_GEOMS:
+        case = E.TrainConvCase(g)
+        oph, opw = case.out_pad
+        oh, ow = case.fwd.out_hw()
+        strided_off = dict(g.env).get("LAV_TRAIN_DGRAD_STRIDED") == "torch" and g.stride != 1
+        dgrad = "lib" if (oph == opw and 0 <= oph < g.stride and (g.dh, g.dw) == (1, 1) and not strided_off) else "torch"
+        assert g.dgrad == (dgrad if g.x_grad else None), g.name
+        wgrad = (g.kh == g.kw and ((g.kh == 3 and g.stride in (1, 2)) or (g.kh == 7 and g.stride == 2)) and (g.ph, g.pw) == (g.kh // 2, g.kh // 2)
+                 and (g.dh, g.dw) == (1, 1) and g.W % (4 * g.stride) == 0 and g.H % g.stride == 0 and g.cin % 64 == 0 and g.cout % 64 == 0
+                 and (oh, ow) == (g.H // g.stride, g.W // g.stride))
+        assert g.wgrad == ("lib" if wgrad else "torch"), g.name
+    took = lambda leg, who: sorted({g.name[0] for g in E.TRAIN_CONV_GEOMS if getattr(g, leg) == who})
+    assert took("dgrad", "lib") == list("abcfghijlm") and took("dgrad", "torch") == list("dek")
+    assert took("wgrad", "lib") == list("abefm") and took("wgrad", "torch") == list("cdghijkl")
 
 
 @pytest.mark.parametrize("H,W,B", [(H, W, 1) for H, W in E.BACKBONE_CANVASES] + [E.BACKBONE_CANVASES[0] + (2,)])

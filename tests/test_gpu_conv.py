@@ -37,6 +37,15 @@ CASES = [
     ("3x3 s2 256->512 on 6x6 (split-K)", 256, 512, (3, 3), 2, (1, 1), (1, 1), False, 0, 6, 6),
     ("1x1 s2 256->512 downsample", 256, 512, (1, 1), 2, (0, 0), (1, 1), False, 0, 6, 6),
     ("7x7 s2 p3 384->64 batch crop", 384, 64, (7, 7), 2, (3, 3), (1, 1), False, 0, 96, 96),
+    # the transposed plans train.hipnn._Conv2d.backward builds for its data gradients (3x3 s1, 3x3 s2 and 7x7 s2 with output padding
+    # 0 / 1), and the ordinary convolutions _ConvT2d.backward builds for the up-convolutions'
+    ("3x3 convT s1 p1 64->64 (dgrad)", 64, 64, (3, 3), 1, (1, 1), (1, 1), True, 0, 12, 16),
+    ("3x3 convT s2 p1 op1 128->64 (dgrad)", 128, 64, (3, 3), 2, (1, 1), (1, 1), True, 1, 10, 12),
+    ("3x3 convT s2 p1 op0 128->64 (dgrad)", 128, 64, (3, 3), 2, (1, 1), (1, 1), True, 0, 11, 13),
+    ("7x7 convT s2 p3 op1 64->64 (dgrad)", 64, 64, (7, 7), 2, (3, 3), (1, 1), True, 1, 12, 12),
+    ("7x7 convT s2 p3 op0 64->3 (dgrad)", 64, 3, (7, 7), 2, (3, 3), (1, 1), True, 0, 13, 11),
+    ("4x4 s2 p1 128->128 (convT dgrad)", 128, 128, (4, 4), 2, (1, 1), (1, 1), False, 0, 24, 20),
+    ("4x4 s4 p0 64->128 (convT dgrad)", 64, 128, (4, 4), 4, (0, 0), (1, 1), False, 0, 24, 20),
 ]
 
 

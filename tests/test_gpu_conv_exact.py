@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
 PREC = {F32: _lib.CONV_F32, BF16X6: _lib.CONV_BF16X6, F16X3: _lib.CONV_F16X3}
 GEOMS = E.conv_geometries() + E.conv_geometries(own_batch=True)
-STEMS = [g for g in GEOMS if (g.kh, g.stride) == (7, 2) and g.cin >= 32 and g.H <= 50]
+STEMS = [g for g in GEOMS if (g.kh, g.stride) == (7, 2) and not g.transposed and g.cin >= 32 and g.H <= 50]      # (the stems: not the 7x7 data-gradient plans)
 _cases: dict = {}
 
 
@@ -256,26 +256,28 @@ def test_pointwise_upconv_is_exact(cin, cout, k, pad, opad, H, W, key):
     assert bool((out[:, :off] == -7).all()) and bool((out[:, off + cout:] == -7).all()), "wrote outside its channel slice"
 
 
-@pytest.mark.parametrize("B,cin,cout,H,W,S", E.WGRAD_GEOMS)
-def test_conv_wgrad_is_exact(B, cin, cout, H, W, S):
-    """lav_conv_wgrad (bf16x6: classes A and D) and lav_conv_wgrad_amax (two fp16 pieces per operand, scales from measured maxima: A and B)."""
+@pytest.mark.parametrize("geom", E.WGRAD_GEOMS, ids=lambda g: "-".join(str(v) for v in g))
+def test_conv_wgrad_is_exact(geom):
+    """lav_conv_wgrad (bf16x6: classes A and D) and lav_conv_wgrad_amax (two fp16 pieces per operand, scales from measured maxima: A and B),
+    3x3 at strides 1 and 2 and the 7x7 stride-2 stem (one ky per task)."""
     from lav_amd.ops import _ptr, _stream, _workspace, check
     lib = _lib.load()
-    nbytes = lib.lav_conv_wgrad_workspace_bytes(B, cin, cout, H, W, 3, S)
+    (B, cin, cout, H, W, S), k = geom[:6], (geom[6] if len(geom) > 6 else 3)
+    nbytes = lib.lav_conv_wgrad_workspace_bytes(B, cin, cout, H, W, k, S)
     assert nbytes > 0
     ws = _workspace("conv_wgrad_exact", nbytes, DEV)
     for key, f16 in (("A", False), ("D", False), ("A", True), ("B", True)):
-        case = E.WgradCase(B, cin, cout, H, W, S, key)
+        case = E.WgradCase(B, cin, cout, H, W, S, key, k)
         x, dy = case.x.to(DEV), case.dy.to(DEV)
-        dw = torch.full((cout, cin, 3, 3), float("nan"), device=DEV)
+        dw = torch.full((cout, cin, k, k), float("nan"), device=DEV)
         if f16:
             ax, ay = torch.zeros(512, device=DEV), torch.zeros(512, device=DEV)
             check(lib.lav_absmax_parts(_ptr(x), x.numel(), _ptr(ax), _stream()), "lav_absmax_parts")
             check(lib.lav_absmax_parts(_ptr(dy), dy.numel(), _ptr(ay), _stream()), "lav_absmax_parts")
-            check(lib.lav_conv_wgrad_amax(_ptr(x), _ptr(dy), B, cin, cout, H, W, 3, S, _ptr(dw), _ptr(ws), ws.numel(), _ptr(ax), 512, _ptr(ay), 512,
+            check(lib.lav_conv_wgrad_amax(_ptr(x), _ptr(dy), B, cin, cout, H, W, k, S, _ptr(dw), _ptr(ws), ws.numel(), _ptr(ax), 512, _ptr(ay), 512,
                                           _stream()), "lav_conv_wgrad_amax")
         else:
-            check(lib.lav_conv_wgrad(_ptr(x), _ptr(dy), B, cin, cout, H, W, 3, S, _ptr(dw), _ptr(ws), ws.numel(), _stream()), "lav_conv_wgrad")
+            check(lib.lav_conv_wgrad(_ptr(x), _ptr(dy), B, cin, cout, H, W, k, S, _ptr(dw), _ptr(ws), ws.numel(), _stream()), "lav_conv_wgrad")
         assert_exact(dw, case.forward(E.Plain()), case.name + (" on fp16 pieces" if f16 else " on bf16 pieces"))
 
 
