@@ -39,19 +39,6 @@ __device__ __forceinline__ void lds_commit() { asm volatile("s_waitcnt lgkmcnt(0
 template <class T>
 __device__ __forceinline__ void lds_keep(T &v) { asm volatile("" : "+v"(v)); }
 
-// LDS claims (round 4's fence, an opt-in since round 5): LAV_LDS_EXCLUSIVE=1 makes the split-operand convolutions and the ERFNet pair
-// kernels ask for all of their CU's LDS (half each where two workgroups share a CU), so that no kernel that uses LDS runs beside them;
-// 2: the whole CU also for kernels that could run two per CU; default 0: exact sizes.  needs_two_per_cu: a persistent launch whose
-// workgroups must all be resident at once and outnumber the CUs keeps the half claim in every mode.
-inline size_t lds_claim(size_t need, size_t static_bytes = 0, bool needs_two_per_cu = false) {
-    static const int mode = [] { const char *e = getenv("LAV_LDS_EXCLUSIVE"); return e ? atoi(e) : 0; }();
-    const size_t total = 160 * 1024;
-    if (mode == 0) return need;
-    if (need + static_bytes > total / 2 || (mode == 2 && !needs_two_per_cu && need + static_bytes > total / 3)) return (total - static_bytes) / 16 * 16;   // one workgroup per CU
-    if (need + static_bytes > total / 3) return (total / 2 - static_bytes) / 16 * 16;   // two
-    return need;                                                                          // three or more: left alone
-}
-
 // ---- LAV_CONV_F16X3's scale hand-off (conv_f16.hip, conv_wgrad.hip): maxima of the finite |values| of a tensor, in parts
 // the largest finite |v| of the wave's lanes, in every lane
 __device__ __forceinline__ float wave_finite_absmax(float m) {

@@ -491,9 +491,8 @@ int choose_tile(const lav_conv &c, const Plan &p, ConvArgs &a, int &MP, int &MC,
         const long pad = ((long)g.ROWS * g.Wst + 63) / 64 * 64;
         auto bytes_with = [&](int tg) { return (size_t)(g.in_bufs * (size_t)CK * pad + 2 * (size_t)tg * CK * CO_T) * 4; };
         // weight slab: all taps of a class, one kernel row, or a single tap (tg_opt 0 / 1 / 2)
-        static const int force_tg = [] { const char *e = getenv("LAV_CONV_FORCE_TG"); return e ? atoi(e) : 0; }();   // experiments
         const int opts[3] = {p.taps_per_class, p.nclasses == 1 ? c.kw : 1, 1};
-        g.tap_group = force_tg ? force_tg : opts[tg_opt];
+        g.tap_group = opts[tg_opt];
         if (g.tap_group < 1 || g.tap_group > TAP_GROUP || bytes_with(g.tap_group) > LDS_MAX) g.tap_group = 0;
         g.plane_pad = (int)pad;
         g.lds = bytes_with(std::max(g.tap_group, 1));
@@ -537,18 +536,13 @@ int choose_tile(const lav_conv &c, const Plan &p, ConvArgs &a, int &MP, int &MC,
             // when a layer is several rounds deep (BEV-size layers measured no gain).
             const bool deep = g.nwg * std::max(1, std::min(16, nchunks / 2)) >= 3 * ncu && g.nwg >= ncu;
             if (per_cu >= 2 && deep) unit *= g.in_bufs == 1 ? 0.85 / 1.2 : 0.85;
-            static const int force_ks = [] { const char *e = getenv("LAV_CONV_FORCE_KS"); return e ? atoi(e) : 0; }();   // experiments
-            static const int force_mode = [] { const char *e = getenv("LAV_CONV_FORCE_MODE"); return e ? atoi(e) : -1; }();
-            static const int force_tile = [] { const char *e = getenv("LAV_CONV_FORCE_TILE"); return e ? atoi(e) : 0; }();
-            if (force_mode >= 0 && mode != force_mode) continue;
-            if (force_tile && cd[0] * 10 + cd[1] != force_tile) continue;
-            const int ks_max = force_ks ? force_ks : (nchunks >= 4 ? std::min(16, nchunks / 2) : 1);
+            const int ks_max = nchunks >= 4 ? std::min(16, nchunks / 2) : 1;
             // partial sums: ks slabs of the output written by the tiles and read back by the reduce launch (~4 TB/s)
             const double slab_us = (double)c.batch * c.cout * p.OH * p.OW * 4.0 * 2.0 / 4e6;
             // what a split costs besides its partial-sum traffic: the reduce launch.  6 us was calibrated on stand-alone layers; LAV_CONV_KS_COST
             // re-prices it (round 6: inside the frame the extra launch and its workgroups also cost the other streams - tools/frame_ab.py)
             static const double ks_cost = [] { const char *e = getenv("LAV_CONV_KS_COST"); return e ? atof(e) : 6.0; }();
-            for (int ks = force_ks ? force_ks : 1; ks <= ks_max; ++ks) {
+            for (int ks = 1; ks <= ks_max; ++ks) {
                 const long wgs = g.nwg * ks;
                 const double t = (double)((wgs + ncu - 1) / ncu) * ((nchunks + ks - 1) / ks) * unit +
                                  (double)((wgs + ncu * per_cu - 1) / (ncu * per_cu)) * 5.0 + (ks > 1 ? ks_cost + ks * slab_us : 0.0);
@@ -777,35 +771,29 @@ struct DirectPlan { bool ok; int waves, ksplit, cw; double cost; long tiles; int
 
 DirectPlan choose_direct(const lav_conv &c, const Plan &p) {
     DirectPlan d{false, 0, 1, 0, 1e30, 0, 1};
-    // experiments (read per call so that a probe can sweep them): LAV_CONV_DIRECT 0 never / 1 by cost / 2 whenever possible,
-    // LAV_CONV_DIRECT_WAVES and LAV_CONV_DIRECT_KS pin the workgroup size and the split
-    auto env_int = [](const char *k, int dflt) { const char *e = getenv(k); return e ? atoi(e) : dflt; };
-    const int mode = env_int("LAV_CONV_DIRECT", 1), force_w = env_int("LAV_CONV_DIRECT_WAVES", 0), force_k = env_int("LAV_CONV_DIRECT_KS", 0);
-    if (!mode || c.cin % 16 != 0 || (c.transposed && !env_int("LAV_CONV_DIRECT_TR", 1))) return d;
+    if (c.cin % 16 != 0) return d;
     const long M = (long)c.batch * p.QH * p.QW;   // per class
     // the kernel addresses activations with 32-bit BYTE offsets from the tensor base
     if (M * c.cout >= (1l << 31) || (long)c.batch * c.in_c_total * c.h * c.w >= (1l << 30)) return d;
     const int taps = p.taps_per_class;   // the largest class
-    if (taps > 9 && mode != 2) return d;   // 7x7 stems re-read too much without an LDS tile (measured 93 vs 86 us, 475 vs 416)
+    if (taps > 9) return d;   // 7x7 stems re-read too much without an LDS tile (measured 93 vs 86 us, 475 vs 416)
     const double slab_us = (double)c.batch * c.cout * p.OH * p.OW * 4.0 * 2.0 / 4e6;
-    const int force_mc = env_int("LAV_CONV_DIRECT_MC", 0);
     for (int mc = 1; mc <= 2; ++mc) {
-        if ((mc == 2 && c.cout < 64) || (force_mc && mc != force_mc)) continue;
+        if (mc == 2 && c.cout < 64) continue;
         // transposed: measured a gain only for 4-tap classes with >= 128 couts (4x4 s2 up-convolution 53.7 -> 49.8 us)
-        if (mc == 2 && !force_mc && c.transposed && (p.taps_per_class < 4 || c.cout < 128)) continue;
+        if (mc == 2 && c.transposed && (p.taps_per_class < 4 || c.cout < 128)) continue;
         const long tiles = (M + 31) / 32 * ((c.cout + 32 * mc - 1) / (32 * mc)) * p.nclasses;
         if (tiles > 8192) continue;
         // sharing a gather between two cout blocks pays once the layer is a few workgroups per CU deep (measured: 8-12 % at
         // >= 400 tiles, a loss on the small ResNet maps)
-        if (mc == 2 && !force_mc && (M + 31) / 32 * ((c.cout + 31) / 32) * p.nclasses < 512) continue;
+        if (mc == 2 && (M + 31) / 32 * ((c.cout + 31) / 32) * p.nclasses < 512) continue;
         for (int ks = 1; ks <= 16; ks *= 2) {
             if (c.cin % (ks * 8) != 0) break;
-            if (force_k && ks != force_k) continue;
             const int cks = c.cin / ks;
-            if (ks > 1 && cks < 32 && !force_k) break;   // keep at least 4 waves x 8 channels per slice
+            if (ks > 1 && cks < 32) break;   // keep at least 4 waves x 8 channels per slice
             for (int waves : {1, 2, 4, 8, 16}) {
-                if (cks % (8 * waves) != 0 || (force_w && waves != force_w) || (mc == 2 && waves > 8)) continue;
-                if (waves < 4 && cks % 32 == 0 && !force_w) continue;   // 1-2 waves only for 16-channel inputs
+                if (cks % (8 * waves) != 0 || (mc == 2 && waves > 8)) continue;
+                if (waves < 4 && cks % 32 == 0) continue;   // 1-2 waves only for 16-channel inputs
                 const int cw = cks / waves;
                 // calibrated on MI355X (tools/direct_probe.py): ~6.5 us of launch + prologue + LDS reduction + epilogue, the
                 // MFMAs of the waves that share a SIMD at ~2/3 of the pipe's rate (gather bound; two cout blocks per
@@ -828,7 +816,6 @@ DirectPlan choose_direct(const lav_conv &c, const Plan &p) {
             }
         }
     }
-    if (mode == 2 && d.ok) d.cost = 0.0;
     return d;
 }
 // precision of a layer: LAV_CONV_F32 (exact fp32 MFMA kernels only) or LAV_CONV_BF16X6 (the split kernel where its plan

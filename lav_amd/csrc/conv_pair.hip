@@ -1273,7 +1273,7 @@ int pair_launch(int ks, int ring, int rows, size_t lds, hipStream_t st, const ty
     static constexpr int (*table[2][3])(dim3, dim3, size_t, hipStream_t, int, const A &) = {   // [KS - 1][R = 1, 2, 4]
         {&launch_lds<F::template kernel<1, 1>, A>, &launch_lds<F::template kernel<1, 2>, A>, &launch_lds<F::template kernel<1, 4>, A>},
         {&launch_lds<F::template kernel<2, 1>, A>, &launch_lds<F::template kernel<2, 2>, A>, &launch_lds<F::template kernel<2, 4>, A>}};
-    return table[ks - 1][ring >> 1](dim3(rows), dim3(256 * ks), lav::lds_claim(lds), st, 160 * 1024, a);
+    return table[ks - 1][ring >> 1](dim3(rows), dim3(256 * ks), lds, st, 160 * 1024, a);
 }
 }  // namespace
 
@@ -1376,8 +1376,7 @@ extern "C" int lav_conv1d_pair(int batch, int channels, int h, int w, int d_a, i
     const int tok = timer_begin("conv1d_pair", st);
     // rows are few (one workgroup each, at most one per CU for ERFNet's shapes): put 8 waves on the channel loop when it
     // is long enough to halve (the partial sums need 16 KB of the staging area)
-    static const bool no_split = getenv("LAV_PAIR_KSPLIT") && getenv("LAV_PAIR_KSPLIT")[0] == '0';
-    const int ks = (channels >= 64 && (channels / 16) % 2 == 0 && !no_split && (size_t)channels * 3 * w * sizeof(float) >= 16 * 1024) ? 2 : 1;
+    const int ks = (channels >= 64 && (channels / 16) % 2 == 0 && (size_t)channels * 3 * w * sizeof(float) >= 16 * 1024) ? 2 : 1;
     const int nch = channels / 16 / ks;              // chunks per wave
     const int ring = nch % 4 == 0 ? 4 : nch % 2 == 0 ? 2 : 1;
     const int rc = pair_launch<PairExact>(ks, ring, batch * h, lds, st, a);
@@ -1416,22 +1415,22 @@ inline size_t chain_cap_rows(size_t workspace_bytes) { return workspace_bytes > 
 
 constexpr int CHAIN_TRACE_ROWS = 512;   // workgroups the trace buffer holds
 
-// One run of family F: a workgroup of 256 * KS threads per row.  `want` bytes of dynamic LDS: what the run needs, or its claim of the
-// CU (lds_claim); the kernel also holds F::STATIC_LDS bytes of static LDS, so the dynamic part may reach 160 KB minus that.
-// trace (LAV_PAIR_CHAIN_TRACE, built for KS = R = 2 only): the exact size `need`, and a.trace is set.
+// One run of family F: a workgroup of 256 * KS threads per row and `lds` bytes of dynamic LDS; the kernel also holds F::STATIC_LDS
+// bytes of static LDS, so the dynamic part may reach 160 KB minus that.
+// trace (LAV_PAIR_CHAIN_TRACE, built for KS = R = 2 only): a.trace is set.
 template <class F>
-int chain_launch(int ks, int ring, bool trace, int rows, size_t need, size_t want, hipStream_t st, const typename F::Args &a) {
+int chain_launch(int ks, int ring, bool trace, int rows, size_t lds, hipStream_t st, const typename F::Args &a) {
     using A = typename F::Args;
     const dim3 grid(rows), block(256 * ks);
-    if (trace) return launch_lds<F::template kernel<2, 2, true>>(grid, block, need, st, 152 * 1024, a);
+    if (trace) return launch_lds<F::template kernel<2, 2, true>>(grid, block, lds, st, 152 * 1024, a);
     static constexpr int (*table[2][2])(dim3, dim3, size_t, hipStream_t, size_t, size_t *, const A &) = {   // [KS - 1][R - 1]
         {&launch_lds_capped<F::template kernel<1, 1, false>, A>, &launch_lds_capped<F::template kernel<1, 2, false>, A>},
         {&launch_lds_capped<F::template kernel<2, 1, false>, A>, &launch_lds_capped<F::template kernel<2, 2, false>, A>}};
     size_t cap = 0;
-    const int rc = table[ks - 1][ring - 1](grid, block, want, st, F::STATIC_LDS, &cap, a);
+    const int rc = table[ks - 1][ring - 1](grid, block, lds, st, F::STATIC_LDS, &cap, a);
     static bool said[2][2] = {};
     if (!said[ks - 1][ring - 1] && getenv("LAV_PAIR_CHAIN_DEBUG"))
-        fprintf(stderr, "[%s] dynamic LDS cap %zu bytes, this launch %zu\n", F::label[0], cap, std::min(cap, want));
+        fprintf(stderr, "[%s] dynamic LDS cap %zu bytes, this launch %zu\n", F::label[0], cap, std::min(cap, lds));
     said[ks - 1][ring - 1] = true;
     return rc;
 }
@@ -1540,10 +1539,9 @@ static int pair_chain_launch(bool f16, int batch, int channels, int h, int w, in
         a.trace = d_trace;
     }
     const int tok = timer_begin("conv1d_pair", st);
-    // (the residency rule above was checked with the bf16 run's LDS size: the fp16 run, which needs less, claims what THAT one would, so
+    // (the residency rule above was checked with the bf16 run's LDS size, and the fp16 run, which needs less, asks for that size too:
     // the same rows per CU)
-    const size_t want = lav::lds_claim(lds, f16 ? ChainF16::STATIC_LDS : ChainBf16::STATIC_LDS, rows > cus);
-    const int rc = f16 ? chain_launch<ChainF16>(ks2, ring2, trace, rows, lds, want, st, fa) : chain_launch<ChainBf16>(ks2, ring2, trace, rows, lds, want, st, a);
+    const int rc = f16 ? chain_launch<ChainF16>(ks2, ring2, trace, rows, lds, st, fa) : chain_launch<ChainBf16>(ks2, ring2, trace, rows, lds, st, a);
     if (!rc && trace) chain_trace_report(d_trace, f16 ? ChainF16::label : ChainBf16::label, channels, w, rows, npairs, st);
     timer_end(tok, st);
     return rc;

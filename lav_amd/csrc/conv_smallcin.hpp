@@ -176,10 +176,8 @@ __global__ __launch_bounds__(128 * CS) void k_conv_smallcin(SmallCinArgs a) {
     }
 }
 
-// Which layers the kernel is built for (LAV_CONV_SMALLCIN=0 switches it off)
+// Which layers the kernel is built for
 inline bool smallcin_applies(const lav_conv &c) {
-    const char *e = getenv("LAV_CONV_SMALLCIN");
-    if (e && atoi(e) == 0) return false;
     if (c.transposed || c.dil_h != 1 || c.dil_w != 1 || c.kh != c.kw || c.stride != 2) return false;
     // (ERFNet's second downsampler, 16 -> 48 with K = 144, was tried on an instance <16, 3, 2, 48, 4, 1> of this kernel: 33.3 us against 25.4 us
     // on the split kernel - the 37 KB patch per 4 x 32 tile costs more than the matrix kernel's prologue; not kept.)

@@ -52,12 +52,8 @@ inline size_t split_weight_bytes_f16(const Plan &p) {
     return taps * (size_t)(p.cout_pad / 32) * (p.cin_pad / 16) * 2 * 1024;
 }
 // The layers the mode takes (round 6: whatever the split kernel takes - any stride, tile, tap group, split-K, tap pairs, the parity
-// classes of a transposed convolution).  LAV_F16X3_LAYERS=head restores round 5's rule (stride-1 single-class layers of >= 64 -> >= 128 channels).
-inline bool f16x3_layer(const lav_conv &c, const Plan &p) {
-    static const bool head_only = [] { const char *e = getenv("LAV_F16X3_LAYERS"); return e && !strcmp(e, "head"); }();
-    if (head_only) return !c.transposed && p.nclasses == 1 && c.stride == 1 && c.cin % 16 == 0 && c.cin >= 64 && c.cout >= 128;
-    return c.cin >= 16;
-}
+// classes of a transposed convolution).
+inline bool f16x3_layer(const lav_conv &c, const Plan &) { return c.cin >= 16; }
 inline void split_pack_weights_f16(const lav_conv &c, const Plan &p, const float *h_weight, unsigned char *out) {
     const int nblk = p.cout_pad / 32, nchunks = p.cin_pad / 16;
     const size_t nw = (size_t)c.cout * c.cin * c.kh * c.kw;
@@ -135,9 +131,8 @@ inline SplitPlan choose_split(const lav_conv &c, const Plan &p) {
     best.ok = false; best.cost = 1e30;
     int f_mp = 0, f_mc = 0, f_wpx = 0, f_tw = -1, f_tg = 0, f_ks = 0, f_wring = 0, f_tp = -1;
     if (const char *e = getenv("LAV_SPLIT_FORCE")) sscanf(e, "%d,%d,%d,%d,%d,%d,%d,%d", &f_mp, &f_mc, &f_wpx, &f_tw, &f_tg, &f_ks, &f_wring, &f_tp);
-    // tap pairs (see the kernel): deep many-tap stems only - LAV_SPLIT_TP=0 switches the mode off
-    static const bool tp_on = [] { const char *e = getenv("LAV_SPLIT_TP"); return !e || atoi(e) != 0; }();
-    const bool tp_can = tp_on && !c.transposed && p.nclasses == 1 && p.taps_per_class >= 25 && p.taps_per_class <= 63 && c.cin % 16 == 0;
+    // tap pairs (see the kernel): deep many-tap stems only
+    const bool tp_can = !c.transposed && p.nclasses == 1 && p.taps_per_class >= 25 && p.taps_per_class <= 63 && c.cin % 16 == 0;
     static const double c_fixed = [] { const char *e = getenv("LAV_SPLIT_C_FIXED"); return e ? atof(e) : 11.0; }();
     static const double c_mma = [] { const char *e = getenv("LAV_SPLIT_C_MMA"); return e ? atof(e) : 0.105; }();
     static const double c_stage = [] { const char *e = getenv("LAV_SPLIT_C_STAGE"); return e ? atof(e) : 0.18; }();
@@ -183,9 +178,8 @@ inline SplitPlan choose_split(const lav_conv &c, const Plan &p) {
             if (plane > SPLIT_LOADERS * (tp ? SPLIT_NT_TP : SPLIT_NT)) continue;
             {
                 // LDS: two activation chunk buffers + a ring of three groups of G taps of weights
-                static const int g_max = [] { const char *e = getenv("LAV_SPLIT_GMAX"); return e ? atoi(e) : 4; }();
                 for (int G : {4, 2, 1}) {
-                    if (G > g_max || (f_tg && G != f_tg)) continue;
+                    if (f_tg && G != f_tg) continue;
                     if (G == 4 && MP * MC > 2 && !f_tg) continue;   // 2x2 tiles have 24 matrix instructions per tap: a barrier every 2 taps is amortised
                     if (tp && G != (MP * MC == 2 ? 4 : 1)) continue;   // built: 1x2 tiles with G = 4, 2x2 tiles with G = 1 (their 256-pixel patch leaves LDS for a 3-slot ring)
                     const int steps_per_chunk = tp ? (min_taps + 1) / 2 : min_taps;
@@ -219,17 +213,10 @@ inline SplitPlan choose_split(const lav_conv &c, const Plan &p) {
 
 template <int MP, int MC, int WPX, int NT, int G, bool TP = false>
 int launch_split_g(const SplitArgs &sa, dim3 grid, size_t lds, hipStream_t st) {
-    // Round 4 made this workgroup take the CU's whole LDS whatever its tiles need, to keep LDS-using kernels off its CUs: the
-    // finite-but-wrong results beside it were taken for an LDS effect.  Round 5 found the cause - packed fp32 instructions with an
-    // op_sel bit in the VICTIMS (common.hpp) - and removed those instructions from the library, so the launch asks for what it needs
-    // again (+0.5 % frames/s: the side streams' kernels overlap with it once more).  LAV_LDS_EXCLUSIVE=1 / LAV_SPLIT_LDS_EXCLUSIVE=1
-    // bring the claim back (tools/coresidency.py measures both settings).
-    static const bool exclusive = [] {
-        const char *e = getenv("LAV_SPLIT_LDS_EXCLUSIVE"), *g = getenv("LAV_LDS_EXCLUSIVE");
-        return (e && atoi(e) != 0) || (g && atoi(g) != 0);
-    }();
+    // The launch asks for the LDS its tiles need, not for the CU's whole LDS: the side streams' kernels overlap with it (+0.5 % frames/s),
+    // and the finite-but-wrong results once seen in such neighbours were packed fp32 instructions with an op_sel bit (common.hpp), not LDS.
     // (+ 16: the two sync words, SplitArgs::sync_off)
-    return launch_lds<k_conv_split<MP, MC, WPX, NT, G, TP>>(grid, dim3(512), exclusive ? (size_t)160 * 1024 : (lds + 15) / 16 * 16 + 16, st, 160 * 1024, sa);
+    return launch_lds<k_conv_split<MP, MC, WPX, NT, G, TP>>(grid, dim3(512), (lds + 15) / 16 * 16 + 16, st, 160 * 1024, sa);
 }
 template <int MP, int MC, int WPX>
 int launch_split_t(const SplitArgs &sa, dim3 grid, size_t lds, hipStream_t st) {
@@ -336,15 +323,14 @@ inline int launch_split(const lav_conv &c, const Plan &p, const SplitPlan &sp, c
             s.f16_parts = io.scratch; s.f16_nparts = F16_PARTS;
         }
         // taps per barrier: a tap is half the matrix instructions of the bf16 kernel, so the barrier's share doubles - four taps per
-        // barrier wherever the two-piece ring of 3 x 4 taps fits beside the activation buffers and 2G steps stay within two chunks
-        // (LAV_F16_TAP_GROUP=2 caps it); the tap-pair kernels exist for their bf16 tap groups only
-        static const int g_env = [] { const char *e = getenv("LAV_F16_TAP_GROUP"); return e ? atoi(e) : 4; }();
+        // barrier wherever the two-piece ring of 3 x 4 taps fits beside the activation buffers and 2G steps stay within two chunks;
+        // the tap-pair kernels exist for their bf16 tap groups only
         const size_t lds_in16 = (size_t)2 * (sp.tp ? 2 : 4) * sp.plane * 16;
         int G16 = sp.tap_group;
         if (!sp.tp) {
             G16 = 1;
             for (int g : {2, 4})
-                if (g <= g_env && 2 * g <= min_taps + 1 && lds_in16 + (size_t)3 * g * NBLK * 2 * 1024 + 16 <= 160 * 1024) G16 = g;
+                if (2 * g <= min_taps + 1 && lds_in16 + (size_t)3 * g * NBLK * 2 * 1024 + 16 <= 160 * 1024) G16 = g;
             if (G16 < sp.tap_group) G16 = sp.tap_group;   // (never fewer taps per barrier than the bf16 plan, which holds 3/2 of the bytes)
         }
         s.tap_group = G16; s.wring = 3 * G16;

@@ -257,8 +257,7 @@ struct TileConfig { int th, tw, tiles_x, tiles; size_t lds; };
 // how a run of this geometry is cut, or false: not served (the caller keeps one launch per layer)
 bool tile_config(int channels, int h, int w, int nlayers, TileConfig &c) {
     if (channels != TILE_C || nlayers < 1 || nlayers > TILE_MAX_L || h < 1 || w < 1 || h > 32768 || w > 32768) return false;
-    static const bool tall = [] { const char *e = getenv("LAV_BEV_TILE_SHAPE"); return e && !strcmp(e, "16x8"); }();
-    c.th = tall ? 16 : 8; c.tw = tall ? 8 : 16;
+    c.th = 8; c.tw = 16;
     c.tiles_x = (w + c.tw - 1) / c.tw;
     const long tiles = (long)c.tiles_x * ((h + c.th - 1) / c.th);
     if (tiles > TILE_MAX_WG) return false;
@@ -303,9 +302,7 @@ extern "C" int lav_conv3x3_tile_f16(int channels, int h, int w, int nlayers, con
     a.H = h; a.W = w; a.tiles_x = c.tiles_x;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int tok = timer_begin("conv3x3_tile", st);
-    int rc;
-    if (c.th == 8) rc = nlayers == 1 ? tile_launch<8, 16, 1>(a, c, st) : nlayers == 2 ? tile_launch<8, 16, 2>(a, c, st) : tile_launch<8, 16, 3>(a, c, st);
-    else rc = nlayers == 1 ? tile_launch<16, 8, 1>(a, c, st) : nlayers == 2 ? tile_launch<16, 8, 2>(a, c, st) : tile_launch<16, 8, 3>(a, c, st);
+    const int rc = nlayers == 1 ? tile_launch<8, 16, 1>(a, c, st) : nlayers == 2 ? tile_launch<8, 16, 2>(a, c, st) : tile_launch<8, 16, 3>(a, c, st);
     timer_end(tok, st);   // (also when the launch failed: the slot that timer_begin opened is closed on every path)
     return rc;
 }

@@ -295,11 +295,8 @@ void launch(const DeconvArgs &a, int groups, hipStream_t st) {
         }
     }
     const long nq = (long)a.B * a.QH * a.QW;
-    static const int unroll = [] { const char *e = getenv("LAV_DECONV_UNROLL"); return e ? atoi(e) : 8; }();
     const dim3 grid((unsigned)((nq + 255) / 256), groups);
-    if (unroll >= 8) hipLaunchKernelGGL((k_deconv_grouped<K, S, NC, 8>), grid, dim3(256), 0, st, a);
-    else if (unroll >= 4) hipLaunchKernelGGL((k_deconv_grouped<K, S, NC, 4>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_deconv_grouped<K, S, NC, 2>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_deconv_grouped<K, S, NC, 8>), grid, dim3(256), 0, st, a);
 }
 }  // namespace
 

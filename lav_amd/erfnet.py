@@ -21,7 +21,6 @@ from .engine import Engine
 from .ops import Conv1dPair, Conv1dPairChain, ConvLayer, GroupedDeconv, infer_precision
 
 ERFNET_ENTRY_DEFAULT = "1"
-_USE_PAIRS = os.environ.get("LAV_ERFNET_PAIRS", "1") != "0"   # A/B switch: 0 = four lav_conv2d launches per block
 
 
 def _affine(bn, sl):
@@ -134,7 +133,7 @@ class non_bottleneck_1d(nn.Module):  # name kept: it is part of pickled/traced c
         p2 = Conv1dPair(self.conv3x1_2, self.conv1x3_2, self.bn2, device=device)
 
         def run(x):
-            if _USE_PAIRS and p1.supported(x) and p2.supported(x):
+            if p1.supported(x) and p2.supported(x):
                 return p2(p1(x), residual=x)
             return d(c(b(a(x))), residual=x)
         run.pairs = (p1, p2)     # (ERFNet._engine chains the pairs of consecutive blocks into one persistent launch)
@@ -152,7 +151,7 @@ def _chain_blocks(stages):
             return
         blocks = list(run)
         run.clear()
-        if len(blocks) == 1 or not _USE_PAIRS:
+        if len(blocks) == 1:
             out.extend(blocks)
             return
         pairs = [p for b in blocks for p in b.pairs]

@@ -21,10 +21,8 @@ from . import ops
 from .model_inference import InferModel
 
 GAP = 5  # NUM_REPEAT + 1 (lav_agent_fast.py:32-33)
-_COPY_STREAM = os.environ.get("LAV_COPY_STREAM", "0") == "1"   # the frame's device-to-host copies on a stream of their own: measured 0.10 ms SLOWER with the side streams on (round 6, profiles/r06_frame_experiments.txt); off
 _DET_REPORT = os.environ.get("LAV_DET_REPORT", "1") != "0"   # round 6: lav_det_decode writes the peak rows + count into pinned host memory itself and bumps a sequence word the host polls (no device->host copies, no event between the heads and the others graph)
 _POSE_BLOCK = os.environ.get("LAV_POSE_BLOCK", "1") != "0"   # round 6: the 176-byte pose block rides in the staging launch's kernel arguments (no upload of its own in front of the lidar graph)
-_BRAKE_AFTER = os.environ.get("LAV_BRAKE_AFTER", "in")       # "in": the brake graph starts with the frame (beside ERFNet + backbone); "feat": behind the lidar graph (beside heads / others / ego)
 _BRAKE_SPLIT = os.environ.get("LAV_BRAKE_SPLIT", "wide")    # "wide" (round 6 default) | "tele": the brake net as two graphs on its stream - that image's trunk with the frame, the other's + poolings + classifier behind the lidar graph; "0": one graph with the frame
 if _BRAKE_SPLIT in ("0", "off", "none"):
     _BRAKE_SPLIT = ""
@@ -70,7 +68,7 @@ class FramePipeline:
         # conv_split.hpp) by writing a flag onto the LiDARModel; round 6 runs EVERY split-kernel layer of the frame that way (the scale
         # handed from layer to layer, lav_conv2d_amax) and asks for it through ops.precision around the pipeline's own calls: the
         # engines are cached per precision on their modules, a model that a trainer owns keeps its default engines.
-        # LAV_INFER_PRECISION=bf16x6 (or round 5's LAV_HEADS_PRECISION=bf16x6) switches the mode off; LAV_CONV_PRECISION=f32 too.
+        # LAV_INFER_PRECISION=bf16x6 switches the mode off; LAV_CONV_PRECISION=f32 too.
         self.precision = ops.frame_precision()
         self.infer_model = InferModel(lidar_model, uniplanner, camera_x, camera_z, device=device, precision=self.precision,
                                       heads_at_peaks=_HEADS_AT_PEAKS)
@@ -167,7 +165,7 @@ class GraphedFramePipeline(FramePipeline):
 
     def __init__(self, *a, points_per_tick: int = 32768, device_others: bool = True, **k):
         super().__init__(*a, **k)
-        self.device_others = device_others and os.environ.get("LAV_DEVICE_OTHERS", "1") != "0"
+        self.device_others = device_others
         dev, P = self.device, points_per_tick
         self.P = P
         f = dict(dtype=torch.float32, device=dev)
@@ -204,17 +202,14 @@ class GraphedFramePipeline(FramePipeline):
         self.b_zero = torch.zeros((1, 4), **f)   # the ego vehicle's own (loc, ori)
         # capture streams double as workspace keys (lav_amd.ops._workspace): graphs that run concurrently must not
         # share split-K scratch, graphs of one stream may
-        # (LAV_BRAKE_PRIORITY / LAV_EGO_PRIORITY: HIP stream priority of the side streams, e.g. 1 = low; default 0.  tools/frame_ab.py)
         self.s_cap = torch.cuda.Stream(dev)
-        self.s_bra = torch.cuda.Stream(dev, priority=int(os.environ.get("LAV_BRAKE_PRIORITY", "0")))
-        self.s_ego = torch.cuda.Stream(dev, priority=int(os.environ.get("LAV_EGO_PRIORITY", "0")))
-        self.ev_in, self.ev_feat, self.ev_heads = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
-        self.s_copy = torch.cuda.Stream(dev)   # the frame's device-to-host copies (peak rows, vehicle count)
-        # the brake net runs beside the LiDAR chain: its layers are planned for part of the chip so that both fit
-        side = int(os.environ.get("LAV_BRAKE_CUS", "128"))
+        self.s_bra = torch.cuda.Stream(dev)
+        self.s_ego = torch.cuda.Stream(dev)
+        self.ev_in, self.ev_feat = torch.cuda.Event(), torch.cuda.Event()
+        # the brake net runs beside the LiDAR chain: its layers are planned for half of the chip so that both fit
         trunk = getattr(self.bra_model, "conv_backbone", None)
-        if side and trunk is not None:
-            object.__setattr__(trunk, "target_cus", side)
+        if trunk is not None:
+            object.__setattr__(trunk, "target_cus", 128)
             trunk._drop()
         self.graphs, self.outs = {}, {}
         self.frame_no = 0
@@ -445,30 +440,23 @@ class GraphedFramePipeline(FramePipeline):
             self.b_tick[n:].fill_(float("nan"))
         cmd_value = int(cmd_value)
         main = torch.cuda.current_stream()
-        brake_late = _BRAKE_AFTER == "feat"
-        if not brake_late:
-            self.ev_in.record(main)                                    # inputs are in their static buffers
+        self.ev_in.record(main)                                        # inputs are in their static buffers
         self._stamp("inputs enqueued")
         o_lidar = self._replay("lidar", self._g_lidar, self.s_cap)
         self._stamp("lidar graph launched")
-        if not brake_late:
-            self.s_bra.wait_event(self.ev_in)
-            with torch.cuda.stream(self.s_bra):
-                if _BRAKE_SPLIT:
-                    self._replay("brake_a", self._g_brake_a, self.s_bra, _skip="brake" in _DIAG_SKIP and "brake_a" in self.graphs)
-                else:
-                    o_bra = self._replay("brake", self._g_brake, self.s_bra, _skip="brake" in _DIAG_SKIP and "brake" in self.graphs)
+        self.s_bra.wait_event(self.ev_in)
+        with torch.cuda.stream(self.s_bra):
+            if _BRAKE_SPLIT:
+                self._replay("brake_a", self._g_brake_a, self.s_bra, _skip="brake" in _DIAG_SKIP and "brake_a" in self.graphs)
+            else:
+                o_bra = self._replay("brake", self._g_brake, self.s_bra, _skip="brake" in _DIAG_SKIP and "brake" in self.graphs)
         self.ev_feat.record(main)                                      # feature map complete
-        if _BRAKE_SPLIT and not brake_late:
+        if _BRAKE_SPLIT:
             skip_b = "brake" in _DIAG_SKIP and "brake_b" in self.graphs
             if not skip_b:
                 self.s_bra.wait_event(self.ev_feat)
             with torch.cuda.stream(self.s_bra):
                 o_bra = self._replay("brake_b", self._g_brake_b, self.s_bra, _skip=skip_b)
-        if brake_late:
-            self.s_bra.wait_event(self.ev_feat)
-            with torch.cuda.stream(self.s_bra):
-                o_bra = self._replay("brake", self._g_brake, self.s_bra, _skip="brake" in _DIAG_SKIP and "brake" in self.graphs)
         self.s_ego.wait_event(self.ev_feat)
         with torch.cuda.stream(self.s_ego):
             o_ego = self._replay(("ego", cmd_value), self._g_ego, self.s_ego, cmd_value,
@@ -481,26 +469,16 @@ class GraphedFramePipeline(FramePipeline):
         if self.device_others:
             # peaks and count travel up while the GPU goes straight on with the others branch; the host reads them (and rebuilds
             # the detection lists of the API) while that branch runs - nothing on the GPU waits for it
-            # (round 6: on a copy stream of their own - issued on the main stream the two copies sat between the heads graph and the
-            # others graph, 25 us of the critical chain in the kernel trace)
-            if _COPY_STREAM:
-                self.ev_heads.record(main)
-                self.s_copy.wait_event(self.ev_heads)
-                with torch.cuda.stream(self.s_copy):
-                    self.h_det.copy_(o_heads["det_raw"], non_blocking=True)
-                    self.h_n.copy_(self.d_n, non_blocking=True)
-                    self.ev_det.record(self.s_copy)
-            elif not _DET_REPORT:
+            # (LAV_DET_REPORT=0: the two copies sit between the heads graph and the others graph, 25 us of the critical chain)
+            if not _DET_REPORT:
                 self.h_det.copy_(o_heads["det_raw"], non_blocking=True)
                 self.h_n.copy_(self.d_n, non_blocking=True)
                 self.ev_det.record(main)
             ob = self._replay("others_cap", self._g_others_cap, self.s_cap)
             main.wait_stream(self.s_ego)      # also keeps the next frame's input copies behind this frame's readers
             main.wait_stream(self.s_bra)
-            if _COPY_STREAM:
-                main.wait_stream(self.s_copy)     # (the next frame's heads graph rewrites the rows being copied)
             self._stamp("others graph launched")
-            if _DET_REPORT and not _COPY_STREAM:
+            if _DET_REPORT:
                 self._wait_report(seq0)
             else:
                 self.ev_det.synchronize()

@@ -1044,10 +1044,10 @@ def frame_heads_at_peaks() -> bool:
 
 def frame_precision() -> int:
     """What the inference pipelines run at: LAV_CONV_F16X3 unless LAV_CONV_PRECISION asks for the exact-fp32 kernels or
-    LAV_INFER_PRECISION / LAV_HEADS_PRECISION (round 5's knob) say bf16x6."""
+    LAV_INFER_PRECISION says bf16x6."""
     if _os.environ.get("LAV_CONV_PRECISION", "") in ("f32", "fp32"):
         return 0
-    want = _os.environ.get("LAV_INFER_PRECISION", _os.environ.get("LAV_HEADS_PRECISION", "f16x3"))
+    want = _os.environ.get("LAV_INFER_PRECISION", "f16x3")
     return _lib.CONV_F16X3 if want == "f16x3" else 0
 
 
@@ -1477,8 +1477,8 @@ class Conv1dPairChain:
         self.pairs, self.residual = list(pairs), [int(bool(r)) for r in residual]
         self._bufs = {}
         # round 6: engines built for LAV_CONV_F16X3 (the inference pipelines' default) run on two fp16 pieces per operand
-        # (lav_conv1d_pair_chain_f16); LAV_ERFNET_F16=0 keeps the bf16x6 run
-        self.f16 = infer_precision() == _lib.CONV_F16X3 and _os.environ.get("LAV_ERFNET_F16", "1") != "0"
+        # (lav_conv1d_pair_chain_f16); every other precision keeps the bf16x6 run
+        self.f16 = infer_precision() == _lib.CONV_F16X3
 
     def supported(self, x: torch.Tensor) -> bool:
         lib = _lib.load()
@@ -1878,7 +1878,7 @@ def copy_many(pairs, block=None) -> None:
         else:
             dst.copy_(src, non_blocking=True)
     lib = _lib.load()
-    if _os.environ.get("LAV_COPY_MERGE", "1") != "0" and stage and plain and len(stage) + len(plain) <= 8 and all(d.dtype == torch.float32 for d, _ in plain):
+    if stage and plain and len(stage) + len(plain) <= 8 and all(d.dtype == torch.float32 for d, _ in plain):
         # (round 6) one launch instead of two: the few contiguous float32 pairs of a frame (LiDAR rows, next waypoint) ride with the
         # strided ones - every launch on the frame's critical chain costs ~4.5 us whatever it moves
         stage = [(d.reshape(-1), s_.reshape(-1)) for d, s_ in plain] + stage

@@ -1,6 +1,6 @@
 """Per-tick deviations of the HIP-graph agent from the reference agent's recorded run (tests/golden/agent_fast.npz): steer,
 EKF pose handed to the stacking, stacked xyz, ego plan / cast waypoints.  Diagnosis companion of
-tests/test_gpu_agent.py::test_agent_vs_reference_agent_golden.    [LAV_SPLIT_TP=0] python tools/agent_dev.py"""
+tests/test_gpu_agent.py::test_agent_vs_reference_agent_golden.    python tools/agent_dev.py"""
 import os
 import pathlib
 import sys

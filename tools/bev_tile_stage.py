@@ -2,8 +2,7 @@
 against lav_conv3x3_tile_f16 (ops.ConvTileRun) and against two layers fused + one per-layer launch, back to back from a HIP graph of 20
 copies each, the variants alternated `--rounds` times in one process.  Prints us per stage.
 
-    python tools/bev_tile_stage.py [--rounds 5] [--reps 50]
-    LAV_BEV_TILE_SHAPE=16x8 python tools/bev_tile_stage.py      (the tile shape is read once per process)"""
+    python tools/bev_tile_stage.py [--rounds 5] [--reps 50]"""
 import argparse
 import json
 import os
@@ -78,5 +77,5 @@ for _ in range(a.rounds):
         e1.record()
         torch.cuda.synchronize()
         res[name].append(round(e0.elapsed_time(e1) * 1e3 / (a.reps * IN_GRAPH), 2))
-print(json.dumps(dict(shape=os.environ.get("LAV_BEV_TILE_SHAPE", "8x16"), us_per_stage=res, best={n: min(r) for n, r in res.items()},
+print(json.dumps(dict(us_per_stage=res, best={n: min(r) for n, r in res.items()},
                       max_abs_diff_to_per_layer=diff, out_absmax=want.abs().max().item())))

@@ -3,13 +3,12 @@
 Every kernel of the frame that uses LDS ("victim") is launched N times on one stream while a second stream loops one of the
 kernels known or suspected to disturb LDS-dependent results of waves sharing their CUs ("aggressor"); every launch is compared bit
 for bit with the same launch on a quiet chip.  Two alternating inputs per victim, so that a value left over from the previous
-launch would show.  One process = one setting of the aggressors' LDS claims (lav::lds_claim reads LAV_LDS_EXCLUSIVE once):
+launch would show.  Every kernel asks for the LDS it needs (round 4's claims of a CU's whole LDS are gone from the library; the runs
+with and without them are profiles/r05_coresidency.md):
 
-    python tools/coresidency.py [launches]                        # exact LDS sizes (the library's default since round 5)
-    LAV_LDS_EXCLUSIVE=1 python tools/coresidency.py [launches]    # round 4's claims: the aggressors take their CU's LDS
-    LAV_LDS_EXCLUSIVE=2 ...                                       # every claiming kernel takes the CU's whole LDS (also the two-per-CU ones)
+    python tools/coresidency.py [launches]
 
-Output: one line per (victim, aggressor): wrong / launches; profiles/r05_coresidency.md is assembled from the two runs.
+Output: one line per (victim, aggressor): wrong / launches.
 """
 import ctypes
 import os
@@ -150,7 +149,7 @@ aggressors["lds_hog mode 1 (matrix + LDS, 150 KB: 10 KB left per CU)"] = _synth
 
 # ------------------------------------------------------------------------------------------------------------------ run
 s_hog, s_vic = torch.cuda.Stream(), torch.cuda.Stream()
-print(f"# {torch.cuda.get_device_name(0)}  LAV_LDS_EXCLUSIVE={os.environ.get('LAV_LDS_EXCLUSIVE', '(default: 0 = exact LDS sizes)')}  launches per cell {N}", flush=True)
+print(f"# {torch.cuda.get_device_name(0)}  launches per cell {N}", flush=True)
 for vname, vic in victims.items():
     if ONLY_V and not any(k in vname for k in ONLY_V):
         continue

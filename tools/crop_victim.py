@@ -41,7 +41,7 @@ for i in range(N):
         outs.append(crop().clone())
 torch.cuda.synchronize()
 bad = [i for i, o in enumerate(outs) if not torch.equal(o, want)]
-print(f"{torch.cuda.get_device_name(0)}  LAV_CROP_FWD_GENERAL={os.environ.get('LAV_CROP_FWD_GENERAL', '0')}  LAV_LDS_EXCLUSIVE={os.environ.get('LAV_LDS_EXCLUSIVE', '1')}: "
+print(f"{torch.cuda.get_device_name(0)}  LAV_CROP_FWD_GENERAL={os.environ.get('LAV_CROP_FWD_GENERAL', '0')}: "
       f"wrong launches {len(bad)} / {N}")
 kinds = {"stale (same pixel, 8 channels earlier)": 0, "stale (same pixel, 8 channels later)": 0, "other pixel of the channel's crop": 0, "zero": 0, "other": 0}
 nel = []

@@ -1,5 +1,5 @@
 """Time of the heads' pieces in isolation (library HIP events, back-to-back launches): fused first convolution, grouped
-deconvolution, peak extraction.  LAV_DECONV_UNROLL=2|4|8 python tools/heads_probe.py
+deconvolution, peak extraction.  python tools/heads_probe.py
 
 Then the stage of the frame, LiDARModel.detect (heads + peaks -> the (2, 15, 7) rows), from a replayed HIP graph of 10 copies: the dense
 four-head path and the heads-at-peaks path alternated in one process, --rounds rounds (default 6) of 50 replays each; us per stage."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Pillar kernel timings (library HIP events, back-to-back launches) for several clouds + memset/copy references.
-    LAV_PILLAR_TW=<w> python tools/pillar_probe.py"""
+    python tools/pillar_probe.py [substring of a cloud's label]"""
 import ctypes
 import os
 import sys
@@ -87,7 +87,7 @@ probe("uniform 196608", uni)
 probe("uniform 32768", uni[:32768])
 for B in (2, 4, 8, 16, 32):
     probe_batch("lidar-like 3x10923", [synth.stacked_lidar(10923, seed=100 + b) if "seed" in synth.stacked_lidar.__code__.co_varnames else synth.stacked_lidar(10923) for b in range(B)])
-if "LAV_PILLAR_TW" not in os.environ and len(sys.argv) == 1:
+if len(sys.argv) == 1:
     canvas = torch.empty((1, 64, 320, 320), device=dev)
     src = torch.randn((1, 64, 320, 320), device=dev)
     print(f"torch zero_ 26 MB   {ev_time(lambda: canvas.zero_()):6.1f} us (back-to-back incl. launch gaps)")
