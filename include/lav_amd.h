@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LAV_ABI_VERSION 49
+#define LAV_ABI_VERSION 50
 
 #define LAV_OK 0
 #define LAV_EINVAL (-1)    /* bad argument / unsupported shape */
@@ -1245,6 +1245,69 @@ int lav_optim_adam_step(const lav_optim_tensor *table, int ntensors, int total_c
 int lav_optim_adam_ema_step(const lav_optim_tensor *table, int ntensors, int total_chunks, const lav_optim_watch *watch, int nwatch,
                             int watch_chunks, lav_optim_state *state, lav_optim_global *global, double max_norm, float *const *shadow,
                             double ema_decay, void *workspace, size_t workspace_bytes, void *stream);
+
+/* lav_optim_tensor_stats (ABI 50; FusedAdam.tensor_stats(), the trainers' --tensor-stats N): the per-tensor view of a step, over the
+ * step's own table, watch rows and state words.  It reads g, p, m, v of every tensor once and stores nothing into them, into `state` or
+ * into any global word.  rows_out [ntensors] and watch_out [nwatch] in DEVICE memory, 8-byte aligned, row-parallel to the tables:
+ *   gradient g   g_nonfinite (NaN, +-Inf), g_zeros (+-0), g_sumsq (float64, of the finite elements), g_maxabs (the largest finite |g|),
+ *                hist[64]: a finite element with biased exponent field e counts in bin clamp(e - 86, 0, 63) - bin 0: zeros, denormals and
+ *                everything below 2^-40; bin k (1 .. 62): [2^(k-41), 2^(k-40)); bin 63: finite values >= 2^22.  Elements that are not
+ *                finite count in g_nonfinite alone.
+ *   parameter p  p_nonfinite, p_sumsq, p_maxabs, as for g.
+ *   update u     u_sumsq, u_maxabs over the finite elements of u = step_size * (m / (sqrtf(v) * inv_sqrt_bc2 + eps)) in float32, every
+ *                operation rounded on its own, from the tensor's state words and m, v as they stand: after an applied step the value the
+ *                update launch subtracted, in every bit; after a skipped one the previous applied update.  A tensor at step 0 gives 0.
+ *   watched      nonfinite, maxabs.
+ * Integers, bins and the bit patterns of the maxima are exact; a sum of squares is within numel * 2^-53 relative of any other order.
+ * Two launches on `stream`: a workgroup per chunk leaves its partials (per-chunk bins are 16-bit) in the workspace, then a wave per
+ * tensor reduces them in chunk order.  No float atomic, no dependency between workgroups of one launch: identical inputs give identical
+ * bits.  workspace: DEVICE, 256-byte aligned, lav_optim_tensor_stats_workspace_bytes(total_chunks, watch_chunks) bytes (0 for counts the
+ * call would refuse); needs no initialisation.  Specification: lav_amd.train.optim.tensor_stats_numpy.
+ *
+ * lav_optim_blame (ABI 50): who caused a skipped step.  One workgroup behind a lav_optim_adam_step / lav_optim_adam_ema_step on the same
+ * stream, with the same tables, `global` and workspace: it reads the per-chunk counts that step left in the workspace, the tables and
+ * `global`.  With global->apply == 0 one thread appends, in table order, the first (at most) LAV_OPTIM_BLAME_PER_STEP tensors whose
+ * gradient holds elements that are not finite to ring[0], and the first (at most) as many watched buffers with such elements to ring[1]:
+ * record k of a ring (counted from 0 since the caller zeroed the block) lies in slot k % LAV_OPTIM_BLAME_RING, written[] counts the
+ * records ever appended.  A record: step = applied + skipped (the ordinal of the skipped step), index = the row's `state` (for a
+ * buffer: its row in `watch`), nonfinite = its count.  With apply == 1 nothing is written.
+ * Specification: lav_amd.train.optim.blame_numpy. */
+#define LAV_OPTIM_HIST_BINS 64
+#define LAV_OPTIM_BLAME_RING 16
+#define LAV_OPTIM_BLAME_PER_STEP 4
+
+typedef struct lav_optim_tensor_row {
+    double g_sumsq, p_sumsq, u_sumsq;
+    long long g_nonfinite, g_zeros, p_nonfinite;
+    float g_maxabs, p_maxabs, u_maxabs;
+    int reserved;
+    long long hist[LAV_OPTIM_HIST_BINS];
+} lav_optim_tensor_row;
+
+typedef struct lav_optim_watch_row {
+    long long nonfinite;
+    float maxabs;
+    int reserved;
+} lav_optim_watch_row;
+
+typedef struct lav_optim_blame_record {
+    long long step, nonfinite;
+    int index;
+    int reserved;
+} lav_optim_blame_record;
+
+typedef struct lav_optim_blame_block {
+    long long written[2];                                       /* [0] tensors, [1] watched buffers */
+    lav_optim_blame_record ring[2][LAV_OPTIM_BLAME_RING];
+} lav_optim_blame_block;
+
+size_t lav_optim_tensor_stats_workspace_bytes(long long total_chunks, long long watch_chunks);
+int lav_optim_tensor_stats(const lav_optim_tensor *table, int ntensors, int total_chunks, const lav_optim_watch *watch, int nwatch,
+                           int watch_chunks, const lav_optim_state *state, lav_optim_tensor_row *rows_out, lav_optim_watch_row *watch_out,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int lav_optim_blame(const lav_optim_tensor *table, int ntensors, int total_chunks, const lav_optim_watch *watch, int nwatch,
+                    int watch_chunks, const lav_optim_global *global, lav_optim_blame_block *blame, const void *workspace,
+                    size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * lav_eval_resample (ABI 49; the eval tools' --bootstrap, lav_amd.ops.eval_resample): block-bootstrap replicates of a table of

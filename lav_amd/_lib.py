@@ -12,7 +12,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LAV_AMD_LIB") or os.path.join(HERE, "liblav_amd.so")   # LAV_AMD_LIB: A/B a second build
 
-ABI_VERSION = 49
+ABI_VERSION = 50
 MAX_CAM = 4
 MAX_CAM_F64 = 8
 
@@ -186,6 +186,9 @@ SIGNATURES = {
     "lav_optim_grad_stats": (_I, [_P, _I, _I, _P, _I, _I, _P, C.c_double, _P, _Z, _P]),
     "lav_optim_adam_step": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, C.c_double, _P, _Z, _P]),
     "lav_optim_adam_ema_step": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, C.c_double, _P, C.c_double, _P, _Z, _P]),
+    "lav_optim_tensor_stats_workspace_bytes": (_Z, [C.c_longlong, C.c_longlong]),
+    "lav_optim_tensor_stats": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "lav_optim_blame": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _Z, _P]),
     "lav_eval_resample_chunk": (_I, []),
     "lav_eval_resample": (_I, [_P, _I, _I, _I, C.c_ulonglong, _P, _P]),
 }

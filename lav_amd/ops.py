@@ -1860,6 +1860,44 @@ def optim_adam_ema_step(table, ntensors, chunks, watch, nwatch, watch_chunks, st
                                       float(max_norm or 0.0), _ptr(shadow), float(ema_decay), _ptr(ws), nbytes, _stream()), "lav_optim_adam_ema_step")
 
 
+def optim_tensor_stats(table, ntensors, chunks, watch, nwatch, watch_chunks, state, rows_out, watch_out) -> None:
+    """The per-tensor view of a step (lav_optim_tensor_stats: two launches on the current stream, no synchronisation) over the tables
+    and state words an optim_adam_step ran on: rows_out / watch_out, uint8 tensors in HBM, receive one lav_amd.train.optim
+    TENSOR_ROW_DTYPE row per tensor and one WATCH_ROW_DTYPE row per watched buffer.  Reads g, p, m, v and the words; stores into none
+    of them.  Equal to tensor_stats_numpy in every integer, bin and maximum; the sums of squares within numel * 2^-53 relative."""
+    from .train import optim as O
+    dev = rows_out.device
+    for t, nbytes, name in ((table, ntensors * O.TENSOR_DTYPE.itemsize, "table"), (watch, nwatch * O.WATCH_DTYPE.itemsize, "watch"),
+                            (state, ntensors * O.STATE_DTYPE.itemsize, "state"), (rows_out, ntensors * O.TENSOR_ROW_DTYPE.itemsize, "rows_out"),
+                            (watch_out, nwatch * O.WATCH_ROW_DTYPE.itemsize, "watch_out")):
+        if t is None and nbytes == 0:
+            continue
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == torch.uint8 and t.is_contiguous() and t.numel() >= nbytes
+                and (t.numel() == 0 or t.data_ptr() % 8 == 0)):
+            raise ValueError(f"optim_tensor_stats: {name} must be a contiguous, 8-byte aligned uint8 tensor of at least {nbytes} bytes in HBM, on one device")
+    lib = _lib.load()
+    nbytes = int(lib.lav_optim_tensor_stats_workspace_bytes(int(chunks), int(watch_chunks)))
+    if nbytes == 0:
+        raise ValueError(f"optim_tensor_stats: {chunks} + {watch_chunks} chunks")
+    ws = _workspace(("optim_tensor_stats",), nbytes, dev)
+    check(lib.lav_optim_tensor_stats(_ptr(table), int(ntensors), int(chunks), _ptr(watch), int(nwatch), int(watch_chunks), _ptr(state),
+                                     _ptr(rows_out), _ptr(watch_out), _ptr(ws), nbytes, _stream()), "lav_optim_tensor_stats")
+
+
+def optim_blame(table, ntensors, chunks, watch, nwatch, watch_chunks, glob, blame) -> None:
+    """Who caused a skipped step (lav_optim_blame: one workgroup on the current stream, behind the optim_adam_step / optim_adam_ema_step
+    with these tables whose per-chunk counts it reads in their workspace).  blame: a uint8 tensor in HBM holding one
+    lav_amd.train.optim BLAME_DTYPE block, zeroed by the caller once.  When that step was applied nothing is written.  Equal to
+    blame_numpy in every word."""
+    from .train import optim as O
+    lib, ws, nbytes = _optim_args("optim_blame", table, ntensors, chunks, watch, nwatch, watch_chunks, dict(**{"global": glob}))
+    if not (isinstance(blame, torch.Tensor) and blame.is_cuda and blame.device == glob.device and blame.dtype == torch.uint8 and blame.is_contiguous()
+            and blame.numel() >= O.BLAME_DTYPE.itemsize and blame.data_ptr() % 8 == 0):
+        raise ValueError(f"optim_blame: blame must be a contiguous, 8-byte aligned uint8 tensor of at least {O.BLAME_DTYPE.itemsize} bytes in HBM")
+    check(lib.lav_optim_blame(_ptr(table), int(ntensors), int(chunks), _ptr(watch), int(nwatch), int(watch_chunks), _ptr(glob), _ptr(blame),
+                              _ptr(ws), nbytes, _stream()), "lav_optim_blame")
+
+
 def copy_many(pairs, block=None) -> None:
     """[(dst, src), ...] device tensors of equal shape into their destinations in at most two launches: contiguous same-dtype
     16-byte-aligned pairs through lav_copy_many (16-byte words), strided / uint8 sources of up to four dimensions into contiguous

@@ -86,7 +86,7 @@ class BrakeTrainer:
         # becoming ready (Adam skips a parameter without a gradient either way: the steps are the reference's)
         for p in self.bra_model.conv_backbone.fc.parameters():
             p.requires_grad_(False)
-        self.bra_optim = make_adam(self.bra_model.parameters(), cfg, [self.bra_model])     # lav_privileged_v2.py:46 (Adam), no scheduler
+        self.bra_optim = make_adam(self.bra_model.parameters(), cfg, [self.bra_model], saved={"bra": self.bra_model})     # lav_privileged_v2.py:46 (Adam), no scheduler
         self.bra_ddp = _ddp(_BrakeStep(self.bra_model), self.device)
 
     def state_dict(self, model_name="bra"):

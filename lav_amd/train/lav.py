@@ -60,6 +60,7 @@ class TrainConfig:
     fused_optim: bool = False      # --fused-optim: lav_amd.train.optim.FusedAdam (guarded, one update launch) where optim.Adam stands
     max_grad_norm: float = 0.0     # --max-grad-norm X > 0: clip the global gradient norm inside that step (implies fused_optim)
     ema_decay: float = 0.0         # --ema DECAY in (0, 1): a moving average of the weights inside that step (implies fused_optim)
+    tensor_stats: int = 0          # --tensor-stats N > 0: the optimiser carries names and records who made a step skip (implies fused_optim)
 
 
 class _Student(nn.Module):
@@ -113,7 +114,7 @@ class LAV:
             self.seg_model = RGBSegmentationModel(cfg.seg_channels)
             self.seg_model.load_state_dict(ck.get("seg") or synth.seeded_state_dict(self.seg_model, prefix="seg."))
             self.seg_model.to(self.device).train()
-            self.seg_optim = make_adam(self.seg_model.parameters(), cfg, [self.seg_model])
+            self.seg_optim = make_adam(self.seg_model.parameters(), cfg, [self.seg_model], saved={"seg": self.seg_model})
             self.seg_ddp = _ddp(self.seg_model, self.device, distributed=distributed)
             return
         y_off = 1 + cfg.min_x / ((cfg.max_x - cfg.min_x) / 2)
@@ -133,7 +134,7 @@ class LAV:
             p.requires_grad_(False)
         if what == "bev":
             self.bev_planner.train()
-            self.bev_optim = make_adam([p for p in self.bev_planner.parameters() if p.requires_grad], cfg, [self.bev_planner])
+            self.bev_optim = make_adam([p for p in self.bev_planner.parameters() if p.requires_grad], cfg, [self.bev_planner], saved={"bev": self.bev_planner})
             self.bev_scheduler = StepLR(self.bev_optim, step_size=32, gamma=0.5)
             self.bev_ddp = _ddp(self.bev_planner, self.device, distributed=distributed)
             return
@@ -169,7 +170,8 @@ class LAV:
             params += list(self.lidar_model.parameters())
         self.student = _Student(self.lidar_model, self.uniplanner).to(self.device).train()
         self.bev_planner.eval()
-        self.lidar_optim = make_adam(params, cfg, trainable + ([] if cfg.motion_only else [self.lidar_model]))
+        self.lidar_optim = make_adam(params, cfg, trainable + ([] if cfg.motion_only else [self.lidar_model]),
+                                     saved={"lidar": self.lidar_model, "uniplanner": self.uniplanner})
         self.lidar_scheduler = StepLR(self.lidar_optim, step_size=4, gamma=0.5)
         self.det_criterion = DetLoss()
         self.seg_mask = build_seg_mask(h=H, w=W, cx=self.bev_center[0], cy=self.bev_center[1]).to(self.device)

@@ -26,7 +26,16 @@ updates towards the parameter it has just computed (lav_optim_adam_ema_step: ins
     per tensor, float64, k = its step count after this step:  d_k = min(ema_decay, (1 + k) / (10 + k));  omd = float32(1 - d_k)
     per element, float32, every operation rounded on its own:  e = e + omd * (p - e)
 
-The warm-up keeps the first steps from being dominated by where the shadow started; a skipped step leaves e alone, as it leaves p."""
+The warm-up keeps the first steps from being dominated by where the shadow started; a skipped step leaves e alone, as it leaves p.
+
+The per-tensor view (FusedAdam.tensor_stats(), the trainers' --tensor-stats N; lav_optim_tensor_stats) says WHERE a run goes wrong:
+`tensor_stats_numpy` is its specification, one TENSOR_ROW_DTYPE row per tensor of the step and one WATCH_ROW_DTYPE row per watched
+buffer.  The histogram of a gradient is a pure function of the float32 bit pattern, exact and free of any order: with e the biased
+exponent field, a finite element counts in bin clamp(e - 86, 0, 63) - bin 0 holds zeros, denormals and everything below 2^-40, bin k
+(1 .. 62) holds [2^(k-41), 2^(k-40)), bin 63 holds finite values >= 2^22; elements that are not finite count in g_nonfinite alone.
+This differs from the reference's wandb.watch (lav/utils/logger.py:32) on purpose: wandb draws 64 LINEAR bins between the minimum and the
+maximum, which needs two passes over the data and resolves nothing across a gradient's dynamic range - one outlier puts every other
+element into bin 0.  `blame_numpy` is the specification of lav_optim_blame: the ring that names the tensors of a skipped step."""
 from __future__ import annotations
 
 import math
@@ -42,6 +51,14 @@ STATE_DTYPE = np.dtype([("step", "<i8"), ("beta1_power", "<f8"), ("beta2_power",
 GLOBAL_DTYPE = np.dtype([("applied", "<i8"), ("skipped", "<i8"), ("nonfinite", "<i8"), ("sumsq", "<f8"), ("clip", "<f4"), ("apply", "<i4"),
                          ("watch_nonfinite", "<i8")])
 assert (TENSOR_DTYPE.itemsize, WATCH_DTYPE.itemsize, STATE_DTYPE.itemsize, GLOBAL_DTYPE.itemsize) == (80, 24, 32, 48)
+HIST_BINS, BLAME_RING, BLAME_PER_STEP = 64, 16, 4      # LAV_OPTIM_HIST_BINS, LAV_OPTIM_BLAME_RING, LAV_OPTIM_BLAME_PER_STEP
+TENSOR_ROW_DTYPE = np.dtype([("g_sumsq", "<f8"), ("p_sumsq", "<f8"), ("u_sumsq", "<f8"), ("g_nonfinite", "<i8"), ("g_zeros", "<i8"),
+                             ("p_nonfinite", "<i8"), ("g_maxabs", "<f4"), ("p_maxabs", "<f4"), ("u_maxabs", "<f4"), ("reserved", "<i4"),
+                             ("hist", "<i8", (HIST_BINS,))])
+WATCH_ROW_DTYPE = np.dtype([("nonfinite", "<i8"), ("maxabs", "<f4"), ("reserved", "<i4")])
+BLAME_RECORD_DTYPE = np.dtype([("step", "<i8"), ("nonfinite", "<i8"), ("index", "<i4"), ("reserved", "<i4")])
+BLAME_DTYPE = np.dtype([("written", "<i8", (2,)), ("ring", BLAME_RECORD_DTYPE, (2, BLAME_RING))])      # [0] tensors, [1] watched buffers
+assert (TENSOR_ROW_DTYPE.itemsize, WATCH_ROW_DTYPE.itemsize, BLAME_RECORD_DTYPE.itemsize, BLAME_DTYPE.itemsize) == (576, 16, 24, 784)
 
 
 def new_state(n):
@@ -128,6 +145,86 @@ def ema_decay_at(ema_decay, k):
     return min(np.float64(ema_decay), (np.float64(1) + k) / (np.float64(10) + k))
 
 
+def _finite_view(x):
+    """(finite elements as float32, their count of the others, the largest finite |x| as a float32): maxima on the values, which for
+    finite floats order as the bit patterns of |x| do."""
+    x = np.asarray(x, np.float32).reshape(-1)
+    fin = x[np.isfinite(x)]
+    return fin, int(x.size - fin.size), (np.float32(np.abs(fin).max()) if fin.size else np.float32(0))
+
+
+def _sumsq(fin):
+    return float(np.sum(np.square(fin.astype(np.float64)), dtype=np.float64))
+
+
+def update_term_numpy(t, st):
+    """u = step_size * (m / (sqrt(v) * inv_sqrt_bc2 + eps)) of one row in float32, every operation rounded on its own, from the tensor's
+    stored words `st` and m, v as they stand: what the last applied step subtracted from p.  A tensor at step 0 gives 0."""
+    m, v = np.asarray(t["m"], np.float32).reshape(-1), np.asarray(t["v"], np.float32).reshape(-1)
+    if int(st["step"]) <= 0:
+        return np.zeros_like(m)
+    with np.errstate(all="ignore"):
+        return np.float32(st["step_size"]) * (m / (np.sqrt(v) * np.float32(st["inv_sqrt_bc2"]) + np.float32(t["eps"])))
+
+
+def tensor_stats_numpy(tensors, state, watch=()):
+    """The specification of lav_optim_tensor_stats (the module's text): tensors and state as fused_adam_numpy takes them (nothing is
+    changed), watch: float32 arrays.  Returns (TENSOR_ROW_DTYPE rows, WATCH_ROW_DTYPE rows)."""
+    rows, wrows = np.zeros(len(tensors), TENSOR_ROW_DTYPE), np.zeros(len(watch), WATCH_ROW_DTYPE)
+    for r, t in enumerate(tensors):
+        g, bad, mx = _finite_view(t["g"])
+        bits = g.view(np.uint32) & np.uint32(0x7FFFFFFF)
+        bins = np.clip((bits >> np.uint32(23)).astype(np.int64) - 86, 0, HIST_BINS - 1)
+        rows[r]["g_nonfinite"], rows[r]["g_zeros"], rows[r]["g_sumsq"], rows[r]["g_maxabs"] = bad, int(np.count_nonzero(bits == 0)), _sumsq(g), mx
+        rows[r]["hist"] = np.bincount(bins, minlength=HIST_BINS)
+        p, bad, mx = _finite_view(t["p"])
+        rows[r]["p_nonfinite"], rows[r]["p_sumsq"], rows[r]["p_maxabs"] = bad, _sumsq(p), mx
+        u, _, mx = _finite_view(update_term_numpy(t, state[t["state"]]))
+        rows[r]["u_sumsq"], rows[r]["u_maxabs"] = _sumsq(u), mx
+    for r, b in enumerate(watch):
+        _, wrows[r]["nonfinite"], wrows[r]["maxabs"] = _finite_view(b)
+    return rows, wrows
+
+
+def blame_numpy(tensors, glob, blame, watch=()):
+    """The specification of lav_optim_blame, called behind fused_adam_numpy with the same tensors, words and watched arrays: when that
+    step was skipped (glob apply == 0) the first BLAME_PER_STEP tensors, in table order, whose gradient holds elements that are not
+    finite are appended to ring 0 of `blame` (a BLAME_DTYPE array of one element, changed in place) as (step = applied + skipped, the
+    count, the row's `state`), and the first BLAME_PER_STEP watched arrays with such elements to ring 1, index = their position in
+    `watch`.  Record k of a ring lies in slot k % BLAME_RING; written counts the records ever appended.  An applied step writes nothing."""
+    w = glob[0] if getattr(glob, "ndim", 0) else glob
+    if int(w["apply"]):
+        return
+    b = blame[0] if getattr(blame, "ndim", 0) else blame
+    step = int(w["applied"]) + int(w["skipped"])
+    for k, rows in enumerate(([(t["state"], t["g"]) for t in tensors], list(enumerate(watch)))):
+        found = 0
+        for index, x in rows:
+            bad = _finite_view(x)[1]
+            if bad and found < BLAME_PER_STEP:
+                b["ring"][k][int(b["written"][k]) % BLAME_RING] = (step, bad, index, 0)
+                b["written"][k] += 1
+                found += 1
+
+
+def blame_records(blame, names=None):
+    """The records a BLAME_DTYPE block still holds, oldest first: ([tensors], [watched buffers]) of dicts step, index, nonfinite, ordinal
+    (the record's number since the block was zeroed) and, with names = (parameter names, buffer names), name."""
+    b = blame[0] if getattr(blame, "ndim", 0) else blame
+    out = []
+    for k in range(2):
+        written = int(b["written"][k])
+        recs = []
+        for o in range(max(0, written - BLAME_RING), written):
+            rec = b["ring"][k][o % BLAME_RING]
+            d = dict(step=int(rec["step"]), index=int(rec["index"]), nonfinite=int(rec["nonfinite"]), ordinal=o)
+            if names is not None:
+                d["name"] = names[k][d["index"]]
+            recs.append(d)
+        out.append(recs)
+    return tuple(out)
+
+
 _ADAM_DEFAULTS = dict(weight_decay=0.0, amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
                       decoupled_weight_decay=False)      # torch.optim.Adam's other group keys: a state_dict moves between the two classes
 
@@ -142,10 +239,13 @@ class FusedAdam(Optimizer):
     (a missing power is beta ** step) and its state loads into torch.optim.Adam.
     ema_decay: keep state[p]["ema"], an exponential moving average of p (the module's text), beside exp_avg: a clone of p taken before
     the parameter's first update here - also where a loaded state has none (a torch.optim.Adam state, a run started without it; the
-    warm-up then goes on from the loaded step count).  It travels in state_dict(); torch.optim.Adam ignores the key and keeps it."""
+    warm-up then goes on from the loaded step count).  It travels in state_dict(); torch.optim.Adam ignores the key and keeps it.
+    names: (one unique name per parameter in group order, one per watched buffer) - the trainers' --tensor-stats.  With names every
+    step() is followed by lav_optim_blame on the same stream (blame(): which tensors made a step skip), and tensor_stats() may be called
+    behind a step for the per-tensor view of it.  Without names neither is launched and nothing is allocated for them."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, maximize=False, max_grad_norm=None,
-                 watch=(), ema_decay=None):
+                 watch=(), ema_decay=None, names=None):
         if not 0.0 <= lr or not 0.0 <= eps or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"FusedAdam: lr {lr}, eps {eps}, betas {betas}")
         if max_grad_norm is not None and not max_grad_norm > 0:
@@ -161,6 +261,13 @@ class FusedAdam(Optimizer):
             if not (isinstance(b, torch.Tensor) and b.dtype == torch.float32 and b.layout == torch.strided and b.is_contiguous()):
                 raise TypeError("FusedAdam: watch holds dense float32 tensors")
         self._check()
+        self.names = None
+        if names is not None:
+            self.names = (tuple(names[0]), tuple(names[1]))
+            if len(self.names[0]) != len(self._params()) or len(self.names[1]) != len(self.watch) or \
+                    len(set(self.names[0] + self.names[1])) != len(self.names[0]) + len(self.names[1]):
+                raise ValueError("FusedAdam: names holds one unique name per parameter and one per watched buffer")
+        self._blame = self._rows_out = self._last = None        # names alone: the blame block; the rows' device buffer; the CPU step's arrays
         self._words = None          # STATE_DTYPE rows, one per parameter in group order: a uint8 tensor on the parameters' device
         self._global = None         # GLOBAL_DTYPE, there too
         self._key = self._table = self._watch_table = self._shadow_table = self._host = None
@@ -257,6 +364,59 @@ class FusedAdam(Optimizer):
         out["grad_norm"] = math.sqrt(out["sumsq"])
         return out
 
+    def blame(self):
+        """Read together with health() (one more small device -> host read): the records the blame block still holds, oldest first, as
+        ([tensors], [watched buffers]) of dicts name, index, nonfinite, step (the ordinal applied + skipped of the skipped step, as
+        health() counts them) and ordinal (the record's number: a gap to the last one seen says how many the ring lost)."""
+        if self.names is None:
+            raise RuntimeError("FusedAdam.blame: an optimiser without names records none")
+        if self._blame is None:
+            return [], []
+        return blame_records(self._blame.cpu().numpy().view(BLAME_DTYPE), (self.names[0], self._watch_names()))
+
+    def watched_nonfinite(self):
+        """The watched buffers that hold values that are not finite, as blame()'s records (without a step): a look at each of them, for
+        the message of a run that ends."""
+        out = []
+        for name, b in zip(self.names[1], self.watch):
+            bad = int(b.numel() - int(torch.isfinite(b).sum()))
+            if bad:
+                out.append(dict(name=name, nonfinite=bad, global_it=None))
+        return out
+
+    def _watch_names(self):
+        return [name for name, b in zip(self.names[1], self.watch) if b.numel() > 0]
+
+    def tensor_stats(self):
+        """The per-tensor view of the step that has just run (its gradients must still be alive): on cuda parameters two launches over
+        the step's own tables (lav_optim_tensor_stats) and a non-blocking copy of the rows and the global words into a pinned slot of
+        their own - nothing waits; on CPU parameters tensor_stats_numpy.  Returns a PendingTensorStats; its result() waits for the copy."""
+        if self.names is None:
+            raise RuntimeError("FusedAdam.tensor_stats: an optimiser without names")
+        if self._words is None or (self._key is None and self._last is None):
+            raise RuntimeError("FusedAdam.tensor_stats: behind a step()")
+        device = self._words.device
+        wnames = self._watch_names()
+        if device.type != "cuda":
+            tensors, watch = self._last
+            rows, wrows = tensor_stats_numpy(tensors, self._words.numpy().view(STATE_DTYPE), watch)
+            names = [self.names[0][t["state"]] for t in tensors]
+            return PendingTensorStats(names, [t["p"].size for t in tensors], wnames, rows, wrows, self._global.numpy().view(GLOBAL_DTYPE)[0].copy())
+        from .. import ops
+        n, chunks, nw, wchunks = self._counts
+        sizes = (n * TENSOR_ROW_DTYPE.itemsize, nw * WATCH_ROW_DTYPE.itemsize, GLOBAL_DTYPE.itemsize)
+        if self._rows_out is None or self._rows_out.numel() != sum(sizes) or self._rows_out.device != device:
+            self._rows_out = torch.zeros(sum(sizes), dtype=torch.uint8, device=device)
+        out = self._rows_out
+        ops.optim_tensor_stats(self._table, n, chunks, self._watch_table, nw, wchunks, self._words, out[:sizes[0]], out[sizes[0]:sizes[0] + sizes[1]])
+        out[sizes[0] + sizes[1]:].copy_(self._global)
+        host = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=True)
+        host.copy_(out, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        key = self._key[0]
+        return PendingTensorStats([self.names[0][row[9]] for row in key], [row[4] for row in key], wnames, host, sizes, None, done)
+
     # ------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def step(self, closure=None):
@@ -316,8 +476,13 @@ class FusedAdam(Optimizer):
             if self.ema_decay is not None:
                 self._check_shadows([p], [st["ema"]])
                 tensors[-1]["e"] = st["ema"].view(-1).numpy()
-        fused_adam_numpy(tensors, rows, glob, self.max_grad_norm, [b.detach().view(-1).numpy() for b in self.watch if b.numel() > 0],
-                         ema_decay=self.ema_decay)
+        watch = [b.detach().view(-1).numpy() for b in self.watch if b.numel() > 0]
+        fused_adam_numpy(tensors, rows, glob, self.max_grad_norm, watch, ema_decay=self.ema_decay)
+        if self.names is not None:
+            if self._blame is None:
+                self._blame = torch.zeros(BLAME_DTYPE.itemsize, dtype=torch.uint8)
+            blame_numpy(tensors, glob, self._blame.numpy().view(BLAME_DTYPE), watch)
+            self._last = (tensors, watch)
 
     def _check_shadows(self, used, shadows):
         for p, e in zip(used, shadows):
@@ -354,15 +519,41 @@ class FusedAdam(Optimizer):
         if self.ema_decay is not None:
             ops.optim_adam_ema_step(self._table, n, chunks, self._watch_table, nw, wchunks, self._words, self._global, self._shadow_table,
                                     self.ema_decay, self.max_grad_norm)
-            return
-        ops.optim_adam_step(self._table, n, chunks, self._watch_table, nw, wchunks, self._words, self._global, self.max_grad_norm)
+        else:
+            ops.optim_adam_step(self._table, n, chunks, self._watch_table, nw, wchunks, self._words, self._global, self.max_grad_norm)
+        if self.names is not None:
+            if self._blame is None or self._blame.device != device:
+                self._blame = torch.zeros(BLAME_DTYPE.itemsize, dtype=torch.uint8, device=device)
+            ops.optim_blame(self._table, n, chunks, self._watch_table, nw, wchunks, self._global, self._blame)
 
 
-def make_adam(params, cfg, modules):
-    """The trainers' optimiser: torch.optim.Adam(params, lr=cfg.lr) as the reference has it, or - cfg.fused_optim, or a cfg.max_grad_norm
-    or a cfg.ema_decay, which imply it - FusedAdam over the same parameters and lr, watching the float buffers of the trained `modules`."""
+class PendingTensorStats:
+    """What FusedAdam.tensor_stats() returns: the rows of one step, possibly still on their way to the host.  result() waits for them
+    (an event, not the device) and returns (names, numels, TENSOR_ROW_DTYPE rows, watch names, WATCH_ROW_DTYPE rows, the GLOBAL_DTYPE
+    words of that step)."""
+
+    def __init__(self, names, numels, watch_names, rows, wrows, glob, done=None):
+        self.names, self.numels, self.watch_names = list(names), [int(n) for n in numels], list(watch_names)
+        self._rows, self._wrows, self._glob, self._done = rows, wrows, glob, done
+
+    def result(self):
+        if self._done is not None:
+            self._done.synchronize()
+            blob, (a, b, _) = self._rows.numpy(), self._wrows
+            self._rows, self._wrows = blob[:a].view(TENSOR_ROW_DTYPE).copy(), blob[a:a + b].view(WATCH_ROW_DTYPE).copy()
+            self._glob = blob[a + b:].view(GLOBAL_DTYPE)[0].copy()
+            self._done = None
+        return self.names, self.numels, self._rows, self.watch_names, self._wrows, self._glob
+
+
+def make_adam(params, cfg, modules, saved=None):
+    """The trainers' optimiser: torch.optim.Adam(params, lr=cfg.lr) as the reference has it, or - cfg.fused_optim, or a cfg.max_grad_norm,
+    a cfg.ema_decay or a cfg.tensor_stats, which imply it - FusedAdam over the same parameters and lr, watching the float buffers of the
+    trained `modules`.  saved: {stem: module} of the checkpoint files the trainer writes ({stem}_{epoch}.th = module.state_dict()); with
+    cfg.tensor_stats every parameter and watched buffer is named "{stem}/{state_dict key}" after the first of them that holds it."""
     params = list(params)
-    if not (getattr(cfg, "fused_optim", False) or getattr(cfg, "max_grad_norm", None) or getattr(cfg, "ema_decay", None)):
+    stats = int(getattr(cfg, "tensor_stats", 0) or 0)
+    if not (getattr(cfg, "fused_optim", False) or getattr(cfg, "max_grad_norm", None) or getattr(cfg, "ema_decay", None) or stats):
         return torch.optim.Adam(params, lr=cfg.lr)
     seen, watch = set(), []
     for m in modules:
@@ -370,8 +561,16 @@ def make_adam(params, cfg, modules):
             if b.dtype == torch.float32 and id(b) not in seen:
                 seen.add(id(b))
                 watch.append(b)
+    names = None
+    if stats:
+        known = {}
+        for stem, module in (saved or {}).items():
+            for key, t in module.state_dict(keep_vars=True).items():
+                known.setdefault(id(t), f"{stem}/{key}")
+        names = ([known.get(id(p), f"unsaved/parameter{i}") for i, p in enumerate(params)],
+                 [known.get(id(b), f"unsaved/buffer{i}") for i, b in enumerate(watch)])
     return FusedAdam(params, lr=cfg.lr, max_grad_norm=getattr(cfg, "max_grad_norm", None) or None, watch=watch,
-                     ema_decay=getattr(cfg, "ema_decay", None) or None)
+                     ema_decay=getattr(cfg, "ema_decay", None) or None, names=names)
 
 
 def ema_state_dict(module, optimizer):

@@ -11,7 +11,7 @@ from typing import Callable, Optional
 import torch
 import torch.distributed as dist
 
-from . import log_view, state as run_state
+from . import log_view, state as run_state, tensor_stats
 from .brake import BRA_LABELS, BrakeTrainer
 from .lav import LAV, TrainConfig
 from .optim import ema_state_dict
@@ -383,8 +383,9 @@ def main(what):
     --max-grad-norm / --max-skipped-steps (lav_amd.train.optim.FusedAdam: a step with a NaN / Inf gradient is skipped, a run that keeps
     skipping ends), --state-dir / --resume (lav_amd.train.state: everything a run needs to go on from an epoch boundary), --ema DECAY (a
     moving average of the weights inside the fused step, saved as {name}_ema_{epoch}.th beside {name}_{epoch}.th; buffers: live) and
-    --val-data-dir / --val-max (each file just written through the trainer's own evaluation tool, into SAVE_DIR/val.jsonl).  Without
-    these flags nothing changes, files written included."""
+    --val-data-dir / --val-max (each file just written through the trainer's own evaluation tool, into SAVE_DIR/val.jsonl) and
+    --tensor-stats N (lav_amd.train.tensor_stats: per-tensor gradient, weight and update statistics of every N-th step and the tensors
+    behind every skipped one, into SAVE_DIR/tensor_stats.jsonl).  Without these flags nothing changes, files written included."""
     t = {"seg": _SEG, "bra": _BRA}.get(what) or _lav(what)
     ap = argparse.ArgumentParser()
     for flag, kw in (
@@ -412,6 +413,14 @@ def main(what):
             ("--max-skipped-steps", dict(type=int, default=10, metavar="N",
                                          help="--fused-optim: end the run (non-zero exit) when more than N steps were skipped between two log "
                                               "iterations, or when a BatchNorm running statistic is not finite")),
+            ("--tensor-stats", dict(type=int, default=None, metavar="N",
+                                    help="where a run goes wrong: behind every N-th optimiser step one more pass over g, p, m, v "
+                                         "(lav_optim_tensor_stats) leaves per tensor the gradient's norm, largest element, zeros, values that are "
+                                         "not finite and a 64-bin histogram of its exponents, the weight's norm and the norm of the update just "
+                                         "applied; rank 0 appends them to SAVE_DIR/tensor_stats.jsonl (read it with python -m "
+                                         "lav_amd.train.tensor_stats) and prints a digest at log iterations.  Every skipped step is written with "
+                                         "the tensors that caused it, and the health stop names them.  The run's bits do not change; implies "
+                                         "--fused-optim")),
             ("--ema", dict(type=float, default=None, metavar="DECAY",
                            help="keep an exponential moving average of the trained weights inside the fused step (e += (1 - d) (p - e), d = "
                                 "min(DECAY, (1 + k) / (10 + k)) at the parameter's step count k; a skipped step leaves it alone) and write it as "
@@ -446,6 +455,10 @@ def main(what):
         if not 0.0 < args.ema < 1.0:
             raise SystemExit(f"--ema {args.ema}: a decay, 0 < DECAY < 1")
         args.fused_optim = True
+    if args.tensor_stats is not None:
+        if args.tensor_stats < 1:
+            raise SystemExit(f"--tensor-stats {args.tensor_stats}: every N-th iteration, N >= 1")
+        args.fused_optim = True
     if args.val_data_dir is not None:
         if args.device == "cpu":
             ap.error("--val-data-dir with --device cpu: the models have no CPU inference path")
@@ -465,7 +478,7 @@ def main(what):
     if args.device == "cpu":
         device = torch.device("cpu")
     cfg = load_config(args.config_path if have_cfg else None, lr=args.lr, seed=args.seed, fused_optim=args.fused_optim,
-                      max_grad_norm=args.max_grad_norm, ema_decay=args.ema, **t.overrides(args))
+                      max_grad_norm=args.max_grad_norm, ema_decay=args.ema, tensor_stats=args.tensor_stats, **t.overrides(args))
     if args.batch_size % world:
         raise SystemExit(f"global batch {args.batch_size} is not divisible by {world} ranks")
     per_rank = args.batch_size // world
@@ -511,6 +524,10 @@ def main(what):
     skipped_seen = health = None
     if args.fused_optim:
         skipped_seen = optimizer.health()["skipped"]
+    # --tensor-stats: every rank's optimiser carries the names and records who made a step skip (its own health stop names them); the
+    # per-tensor rows and the file are rank 0's - under data parallel all ranks see the same all-reduced gradients
+    stats_log = tensor_stats.TensorStatsLog(args.save_dir, args.tensor_stats, global_it) if args.tensor_stats and rank == 0 else None
+    it_first = global_it
     t0, it0 = time.perf_counter(), global_it
     val_failed = None
     for epoch in range(first_epoch, args.num_epoch):
@@ -521,6 +538,8 @@ def main(what):
             if drawn:
                 trainer.log_view = False
                 writer.add(log_view.render(log_view.build_frame(what, info.pop("view"), cfg)), global_it)
+            if stats_log is not None:
+                stats_log.after_step(optimizer, global_it)
             if global_it % args.num_per_log == 0:
                 shown = t.log(info) if rank == 0 else None
                 if args.fused_optim:
@@ -531,7 +550,19 @@ def main(what):
                         shown = dict(shown, grad_norm=round(health["grad_norm"], 4), skipped_steps=health["skipped"])
                 if rank == 0:
                     print(global_it, shown, flush=True)
-                if args.fused_optim:
+                if args.tensor_stats:
+                    blame = optimizer.blame()
+                    if stats_log is not None:
+                        digest = stats_log.digest()
+                        if digest is not None:
+                            print(digest, flush=True)
+                        blame = stats_log.blamed(blame)
+                    else:
+                        blame = tuple([dict(r, global_it=it_first + r["step"] - 1) for r in recs] for recs in blame)
+                    if health["watch_nonfinite"] and not blame[1]:     # (a step that was applied records none: look once, the run ends here)
+                        blame = (blame[0], optimizer.watched_nonfinite())
+                    skipped_seen = run_state.check_health(health, skipped_seen, args.max_skipped_steps, args.state_dir, blame)
+                elif args.fused_optim:
                     skipped_seen = run_state.check_health(health, skipped_seen, args.max_skipped_steps, args.state_dir)
             global_it += 1
         if scheduler is not None:
@@ -568,6 +599,9 @@ def main(what):
                 print(f"state in {run_state.write(st, args.state_dir)}", flush=True)
     if writer is not None:
         writer.close()
+    if stats_log is not None:
+        stats_log.blamed(optimizer.blame())
+        stats_log.close()
     if device.type == "cuda":
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0

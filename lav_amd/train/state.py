@@ -131,16 +131,25 @@ def load(path):
     return torch.load(path, map_location="cpu", weights_only=False)
 
 
-def check_health(health, skipped_at_last_log, max_skipped_steps, state_dir):
+def _blamed(records):
+    return ", ".join(f"{r['name']} ({r['nonfinite']}" + (f" at iteration {r['global_it']})" if r.get("global_it") is not None else ")") for r in records)
+
+
+def check_health(health, skipped_at_last_log, max_skipped_steps, state_dir, blame=None):
     """What the trainers' main asks on every log iteration: ends the run (SystemExit, a non-zero exit) when a watched buffer holds a
     value that is not finite, or when more than max_skipped_steps steps were skipped since the last log iteration; the message names the
-    newest state file to --resume from, or says that there is none.  Otherwise returns the skipped count to remember."""
+    newest state file to --resume from, or says that there is none.  Otherwise returns the skipped count to remember.
+    blame (--tensor-stats): ([tensors], [watched buffers]) of records name, nonfinite, global_it - the messages then name them."""
     why = None
     if health["watch_nonfinite"]:
         why = f"{health['watch_nonfinite']} values of the watched buffers (BatchNorm running statistics) are not finite"
+        if blame is not None and blame[1]:
+            why += f": {_blamed(blame[1])}"
     elif health["skipped"] - skipped_at_last_log > max_skipped_steps:
         why = (f"{health['skipped'] - skipped_at_last_log} optimiser steps were skipped for gradients that are not finite since the last log "
                f"iteration (--max-skipped-steps {max_skipped_steps})")
+        if blame is not None and blame[0]:
+            why += f": {_blamed(blame[0])}"
     if why is None:
         return health["skipped"]
     last = newest(state_dir)
