@@ -173,7 +173,11 @@ int lav_gru_plan(const float *embd, const float *nxp, const float *cast_locs, in
 size_t lav_gru_plan_workspace_bytes(int B, int H, int num_cmds, int T);
 /* A plan workspace must be ZERO before its first use and belongs to one stream.  Its first 512 bytes are a control block:
  * [0, 256) sticky counters {aborted persistent launches, persistent launches} since it was zero-filled, [256, 512) the status
- * and diagnosis words of the last persistent launch (cleared at every launch). */
+ * and diagnosis words of the last persistent launch (cleared at every launch).  Behind it, with R = B * (1 or num_cmds) state rows:
+ * the persistent launch keeps two buffers of R*H 8-byte granules; the step-per-launch path the state sequence [T][R][H] floats - with
+ * 512 + T*R*H*4 bytes it runs - and, from 16 rows on, the MFMA step's initial state [R][H] and inputs [R][T][4] (without room for
+ * them the rows run on the slower VALU step kernel).  lav_gru_plan_workspace_bytes covers every path: 512 + the largest of these,
+ * rounded up to 256. */
 /*
  * lav_gru_plan runs all iters*T dependent steps in ONE persistent launch when B*(1 or num_cmds) <= 6: its H/8 workgroups
  * exchange the hidden state through HBM and must be co-resident.  Every wait is bounded; a launch that times out (the chip

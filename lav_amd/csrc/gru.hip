@@ -8,27 +8,21 @@
 //         in registers (one row per thread) and the 20-step recurrence, the Linear(64->2) and the cumulative
 //         sum all run inside the workgroup.
 // plan  - W_hh is 1536x512 fp32 = 3.1 MB: it does not fit one CU, so a step is spread over H/8 workgroups
-//         (each owns 8 hidden units = 24 rows of W_hh, read coalesced from L2) and the time steps are
-//         separate launches on the stream (first version; see DESIGN.md for the persistent variant).
+//         (each owns 8 hidden units = 24 rows of W_hh).  Up to 6 state rows (the frame: 1 or 6) run all iters*T steps
+//         in ONE persistent launch (k_plan_wave); more rows, or lav_gru_plan_steps, run one launch per step: k_plan_step
+//         (the persistent kernel's bit-for-bit reference) below 16 rows, the MFMA step of gru_seq.hip from 16 rows on.
 //         Inputs are not autoregressive inside an iteration (uniplanner.py:264-270), so W_ih.u_t is formed on
 //         the fly (4 FMAs).  Command branches never interact: with cmd >= 0 only that branch is evaluated.
 //
-// Gate order r, z, n as in torch.nn.GRU;  h' = (1-z)*n + z*h;  precise expf/tanhf (no fast-math).
+// The cell itself (gate order, h' = (1-z)*n + z*h, the wave butterfly) is gru_cell.hpp.
 #include <cstdlib>
 
 #include "common.hpp"
+#include "gru_cell.hpp"
 #include "gru_seq.hpp"
 
 namespace {
 using namespace lav;
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 // Cross-lane sums without LDS hardware (__shfl_xor compiles to ds_bpermute_b32, a DS instruction): gfx950's v_permlane32_swap /
 // v_permlane16_swap exchange halves / rows of 16 lanes between two registers, DPP row rotations do the rest.
@@ -106,20 +100,17 @@ __global__ __launch_bounds__(CAST_THREADS) void k_gru_cast(const float *__restri
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc[j] = fmaf(wih[(long)(r0 + j) * embd_dim + k], ev, acc[j]);
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[j] += __shfl_xor(acc[j], d, 64);
+        wave_allsum(acc);
         if (lane == 0) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) gi[r0 + j] = acc[j] + b_ih[cmd * G + r0 + j];
         }
     }
     if (x.cmds_out && wid == 11) {   // this command's score: one more row on the last helper wave
-        float acc = 0.f;
-        for (int k = lane; k < embd_dim; k += 64) acc = fmaf(x.cmd_w[(long)cmd * embd_dim + k], e[k], acc);
-        acc = wave_sum(acc);
-        if (lane == 0) x.cmds_out[(long)b * num_cmds + cmd] = sigmoidf_(acc + x.cmd_b[cmd]);
+        float acc[1] = {0.f};
+        for (int k = lane; k < embd_dim; k += 64) acc[0] = fmaf(x.cmd_w[(long)cmd * embd_dim + k], e[k], acc[0]);
+        wave_allsum(acc);
+        if (lane == 0) x.cmds_out[(long)b * num_cmds + cmd] = gru_sigmoid(acc[0] + x.cmd_b[cmd]);
     }
     __syncthreads();  // gi[] complete and visible
     if (tid >= G) return;  // the nine helper waves are done (terminated waves drop out of later barriers)
@@ -148,15 +139,17 @@ __global__ __launch_bounds__(CAST_THREADS) void k_gru_cast(const float *__restri
         gh[tid] = acc;
         __syncthreads();
         if (tid < H) {
-            const float r = sigmoidf_(gi[tid] + gh[tid]);
-            const float z = sigmoidf_(gi[H + tid] + gh[H + tid]);
+            // gru_gates written out: through the helper the compiler fuses the other product of h' into the FMA here (last-bit differences)
+            const float r = gru_sigmoid(gi[tid] + gh[tid]);
+            const float z = gru_sigmoid(gi[H + tid] + gh[H + tid]);
             const float n = tanhf(gi[2 * H + tid] + r * gh[2 * H + tid]);
             const float hn = (1.f - z) * n + z * h[tid];
             h[tid] = hn;  // only this thread reads h[tid] in this phase; others read it after the barrier
-            const float s0 = wave_sum(m0 * hn), s1 = wave_sum(m1 * hn);
+            float s[2] = {m0 * hn, m1 * hn};
+            wave_allsum(s);
             if (tid == 0) {
-                run0 += s0 + mlp_b[cmd * 2 + 0];
-                run1 += s1 + mlp_b[cmd * 2 + 1];
+                run0 += s[0] + mlp_b[cmd * 2 + 0];
+                run1 += s[1] + mlp_b[cmd * 2 + 1];
                 o[t * 2 + 0] = xform ? (run0 * rc + run1 * -rs) + lx : run0;
                 o[t * 2 + 1] = xform ? (run0 * rs + run1 * rc) + ly : run1;
             }
@@ -184,6 +177,14 @@ __device__ __forceinline__ void row_decode(const PlanArgs &a, int r, int &b, int
     b = r / a.NC;
     ci = r - b * a.NC;
     c = a.cmd >= 0 ? a.cmd : ci;
+}
+
+// u_t = [target point in crop units (2), the previous iteration's waypoint t (2)]
+__device__ __forceinline__ float plan_target(const PlanArgs &a, int b, int k) { return a.nxp[b * 2 + k] * a.ppm / a.crop * 2.f - 1.f; }
+
+__device__ __forceinline__ const float *plan_prev(const PlanArgs &a, int it, int b, int ci, int c, int t) {   // iteration 0 refines the cast waypoints
+    return it == 0 ? a.cast_locs + (((long)b * a.num_cmds + c) * a.T + t) * 2
+                   : a.out + ((((long)b * a.iters + (it - 1)) * a.NC + ci) * a.T + t) * 2;
 }
 
 __global__ __launch_bounds__(256) void k_plan_step(PlanArgs a, int it, int t) {
@@ -227,22 +228,16 @@ __global__ __launch_bounds__(256) void k_plan_step(PlanArgs a, int it, int t) {
 #pragma unroll
                     for (int i = 0; i < PLAN_MAXK; ++i) acc[q] = fmaf(w[q][i], hv[rr][i], acc[q]);
                 }
-                // six independent butterfly reductions, interleaved so their shuffle latencies overlap
+                wave_allsum(acc);
+                if (lane == 0) {   // committed LDS stores (common.hpp: ds_write data hazards beside matrix-heavy neighbours)
+                    float gv[6];
 #pragma unroll
-                for (int d = 32; d >= 1; d >>= 1)
+                    for (int q = 0; q < 6; ++q) gv[q] = acc[q] + bh[q];
 #pragma unroll
-                    for (int q = 0; q < 6; ++q) acc[q] += __shfl_xor(acc[q], d, 64);
-                if (lane == 0) {
-                    {   // committed LDS stores (common.hpp: ds_write data hazards beside matrix-heavy neighbours)
-                            float gv[6];
+                    for (int q = 0; q < 6; ++q) { gh_s[wid * 6 + q][rr] = gv[q]; lav::lds_store_fence(); }
+                    lav::lds_commit();
 #pragma unroll
-                            for (int q = 0; q < 6; ++q) gv[q] = acc[q] + bh[q];
-#pragma unroll
-                            for (int q = 0; q < 6; ++q) { gh_s[wid * 6 + q][rr] = gv[q]; lav::lds_store_fence(); }
-                            lav::lds_commit();
-#pragma unroll
-                            for (int q = 0; q < 6; ++q) lav::lds_keep(gv[q]);
-                        }
+                    for (int q = 0; q < 6; ++q) lav::lds_keep(gv[q]);
                 }
             }
         }
@@ -253,28 +248,20 @@ __global__ __launch_bounds__(256) void k_plan_step(PlanArgs a, int it, int t) {
                 const int r = r0 + rr, j = j0 + u;
                 int b, ci, c;
                 row_decode(a, r, b, ci, c);
-                // u_t = [nxp*ppm/crop*2-1, previous iteration's waypoint]
-                const float *prev = it == 0 ? a.cast_locs + (((long)b * a.num_cmds + c) * a.T + t) * 2
-                                            : a.out + ((((long)b * a.iters + (it - 1)) * a.NC + ci) * a.T + t) * 2;
-                float uu[4];
-                uu[0] = a.nxp[b * 2 + 0] * a.ppm / a.crop * 2.f - 1.f;
-                uu[1] = a.nxp[b * 2 + 1] * a.ppm / a.crop * 2.f - 1.f;
-                uu[2] = prev[0];
-                uu[3] = prev[1];
+                const float *prev = plan_prev(a, it, b, ci, c, t);
+                const float uu[4] = {plan_target(a, b, 0), plan_target(a, b, 1), prev[0], prev[1]};
                 float gi[3];
 #pragma unroll
                 for (int g = 0; g < 3; ++g) {
                     const int row = g * H + j;
-                    float acc = 0.f;
+                    float acc = 0.f;   // W_ih . u_t, the chain k_plan_wave writes out too (a shared helper changes that kernel's one-row code)
 #pragma unroll
                     for (int k = 0; k < 4; ++k) acc = fmaf(a.w_ih[row * 4 + k], uu[k], acc);
                     gi[g] = acc + a.b_ih[row];
                 }
                 const float hp = t == 0 ? a.embd[(long)b * H + j] : h_prev_base[(long)r * H + j];
-                const float rg = sigmoidf_(gi[0] + gh_s[0 * PLAN_UNITS + u][rr]);
-                const float zg = sigmoidf_(gi[1] + gh_s[1 * PLAN_UNITS + u][rr]);
-                const float ng = tanhf(gi[2] + rg * gh_s[2 * PLAN_UNITS + u][rr]);
-                h_out[(long)r * H + j] = (1.f - zg) * ng + zg * hp;
+                h_out[(long)r * H + j] = gru_gates(gi[0], gi[1], gi[2], gh_s[0 * PLAN_UNITS + u][rr], gh_s[1 * PLAN_UNITS + u][rr],
+                                                   gh_s[2 * PLAN_UNITS + u][rr], hp).h;
             }
         }
         __syncthreads();
@@ -292,10 +279,8 @@ __global__ __launch_bounds__(256) void k_plan_inputs(PlanArgs a, int it, float *
         const int r = (int)(i / a.T), t = (int)(i - (long)r * a.T);
         int b, ci, c;
         row_decode(a, r, b, ci, c);
-        const float *prev = it == 0 ? a.cast_locs + (((long)b * a.num_cmds + c) * a.T + t) * 2
-                                    : a.out + ((((long)b * a.iters + (it - 1)) * a.NC + ci) * a.T + t) * 2;
-        *reinterpret_cast<float4 *>(u + i * 4) =
-            make_float4(a.nxp[b * 2 + 0] * a.ppm / a.crop * 2.f - 1.f, a.nxp[b * 2 + 1] * a.ppm / a.crop * 2.f - 1.f, prev[0], prev[1]);
+        const float *prev = plan_prev(a, it, b, ci, c, t);
+        *reinterpret_cast<float4 *>(u + i * 4) = make_float4(plan_target(a, b, 0), plan_target(a, b, 1), prev[0], prev[1]);
     }
     if (it == 0) {
         for (long k = i; k < (long)a.R * a.H; k += (long)gridDim.x * 256) {
@@ -315,20 +300,16 @@ __global__ __launch_bounds__(64 * OUT_WAVES) void k_plan_out(PlanArgs a, int it)
     row_decode(a, r, b, ci, c);
     for (int t = wid; t < a.T; t += OUT_WAVES) {
         const float *h = a.hseq + ((long)t * a.R + r) * H;
-        float s0 = 0.f, s1 = 0.f;
+        float s[2] = {0.f, 0.f};
         for (int k = lane; k < H; k += 64) {
             const float hv = h[k];
-            s0 = fmaf(a.mlp_w[k], hv, s0);
-            s1 = fmaf(a.mlp_w[H + k], hv, s1);
+            s[0] = fmaf(a.mlp_w[k], hv, s[0]);
+            s[1] = fmaf(a.mlp_w[H + k], hv, s[1]);
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            s0 += __shfl_xor(s0, d, 64);
-            s1 += __shfl_xor(s1, d, 64);
-        }
+        wave_allsum(s);
         if (lane == 0) {
-            wp[t][0] = s0 + a.mlp_b[0];
-            wp[t][1] = s1 + a.mlp_b[1];
+            wp[t][0] = s[0] + a.mlp_b[0];
+            wp[t][1] = s[1] + a.mlp_b[1];
         }
     }
     __syncthreads();
@@ -336,8 +317,7 @@ __global__ __launch_bounds__(64 * OUT_WAVES) void k_plan_out(PlanArgs a, int it)
         float run0 = 0.f, run1 = 0.f;
         float *o = a.out + ((((long)b * a.iters + it) * a.NC + ci) * a.T) * 2;
         for (int t = 0; t < a.T; ++t) {
-            const float *prev = it == 0 ? a.cast_locs + (((long)b * a.num_cmds + c) * a.T + t) * 2
-                                        : a.out + ((((long)b * a.iters + (it - 1)) * a.NC + ci) * a.T + t) * 2;
+            const float *prev = plan_prev(a, it, b, ci, c, t);
             run0 += wp[t][0];
             run1 += wp[t][1];
             o[t * 2 + 0] = run0 + prev[0];
@@ -361,10 +341,30 @@ __global__ __launch_bounds__(64 * OUT_WAVES) void k_plan_out(PlanArgs a, int it)
 // waypoints (no steering, no throttle, lav_agent_fast.py:325-328) applies, and lav_gru_plan_steps recomputes it without any
 // co-residency requirement.
 constexpr long long PLAN_SPIN_LIMIT = 1ll << 22;
-constexpr size_t PLAN_CTRL_BYTES = 512;   // head of a plan workspace: sticky counters + status / diagnosis words
 
-// sticky[0] / sticky[1]: aborted / all persistent launches on this workspace since the caller zero-filled it (outside
-// the range the per-launch memset clears) - a benchmark or a drive reads them once at its end (lav_gru_plan_diag words 10, 11).
+// The plan workspace, described once: lav_gru_plan_workspace_bytes, plan_launch, lav_gru_plan_status and lav_gru_plan_diag read it here.
+//   [STICKY_OFF, STATUS_OFF)  sticky[0] / sticky[1]: aborted / all persistent launches since the caller zero-filled the workspace.  Outside
+//                             the range a launch resets: a benchmark or a drive reads them once at its end (lav_gru_plan_diag words 10, 11)
+//   [STATUS_OFF, DATA_OFF)    the status word and the diagnosis words of the last persistent launch (listed below k_plan_poison)
+//   [DATA_OFF, ...)           persistent kernel: two granule buffers [R][H] of 8 bytes, reset with the status words at every launch;
+//                             step path: hseq [T][R][H] floats and, for the MFMA step only, h0 [R][H] and u [R][T][4] behind it
+// H is a multiple of 64 (plan_launch refuses any other), so every part starts on a 256-byte boundary without padding.
+struct PlanLayout {
+    static constexpr size_t STICKY_OFF = 0, STATUS_OFF = 256, DATA_OFF = 512;
+    static constexpr int STICKY_WORDS = 2, STATUS_WORDS = 10;
+    size_t hseq_floats, h0_floats, u_floats, gran_bytes;
+    PlanLayout(int R, int H, int T)
+        : hseq_floats((size_t)T * R * H), h0_floats((size_t)R * H), u_floats((size_t)R * T * 4), gran_bytes(2 * (size_t)R * H * sizeof(unsigned long long)) {}
+    // what each path needs of a workspace
+    size_t valu_bytes() const { return DATA_OFF + hseq_floats * sizeof(float); }
+    size_t mfma_bytes() const { return DATA_OFF + (hseq_floats + h0_floats + u_floats) * sizeof(float); }
+    size_t persistent_bytes() const { return DATA_OFF + gran_bytes; }
+    size_t reset_bytes() const { return DATA_OFF - STATUS_OFF + gran_bytes; }   // from STATUS_OFF on
+    static float *hseq(char *ws) { return reinterpret_cast<float *>(ws + DATA_OFF); }
+    float *h0(char *ws) const { return hseq(ws) + hseq_floats; }
+    float *u(char *ws) const { return h0(ws) + h0_floats; }
+};
+
 __global__ __launch_bounds__(256) void k_plan_reset(uint4 *__restrict__ p, unsigned n16) {
     const unsigned i = blockIdx.x * 256 + threadIdx.x;
     if (i < n16) p[i] = make_uint4(0u, 0u, 0u, 0u);
@@ -385,8 +385,7 @@ __global__ __launch_bounds__(256) void k_plan_poison(const int *__restrict__ sta
 // it was waiting for, [7] the tag it last saw there, [8] microseconds between its kernel entry and the abort, [9] workgroups
 // that ran to completion.  The words are cleared with the granule tags at every launch.
 
-// ------------------------------------------------------------------------------------------------- plan, persistent, LDS-free (round 5)
-// The persistent kernel since round 5 (rounds 2-4's four-wave LDS kernel: tools/probes/plan_persistent_r4.diff).
+// ------------------------------------------------------------------------------------------------- plan, persistent: the kernel
 // One WAVE per workgroup, H/8 workgroups: the wave holds all three gates of its 8 hidden units (24 rows of
 // W_hh + the two rows of Linear(H->2): 208 registers per lane), so that a unit's r / z / n pre-activations meet inside the wave and
 // nothing of the recurrence ever goes through LDS: no DS instruction (the cross-lane sums are v_permlane32_swap / v_permlane16_swap /
@@ -464,8 +463,8 @@ __global__ __launch_bounds__(64) void k_plan_wave(PlanArgs a, unsigned long long
     for (int rr = 0; rr < RC; ++rr) {
         int b, ci, c;
         row_decode(a, min(rr, R - 1), b, ci, c);
-        u0[rr] = a.nxp[b * 2 + 0] * a.ppm / a.crop * 2.f - 1.f;
-        u1[rr] = a.nxp[b * 2 + 1] * a.ppm / a.crop * 2.f - 1.f;
+        u0[rr] = plan_target(a, b, 0);
+        u1[rr] = plan_target(a, b, 1);
         const float *src = a.cast_locs + (((long)b * a.num_cmds + c) * T + min(lane, T - 1)) * 2;   // iteration 0 refines the cast waypoints
         locp0[rr] = src[0];
         locp1[rr] = src[1];
@@ -588,10 +587,7 @@ __global__ __launch_bounds__(64) void k_plan_wave(PlanArgs a, unsigned long long
                             gi[g] = acc + bih[g];
                             gh[g] = (odd ? z[3 + g] : z[g]) + bh[g];
                         }
-                        const float rg = sigmoidf_(gi[0] + gh[0]);
-                        const float zg = sigmoidf_(gi[1] + gh[1]);
-                        const float ng = tanhf(gi[2] + rg * gh[2]);
-                        hself[rr] = (1.f - zg) * ng + zg * hself[rr];
+                        hself[rr] = gru_gates(gi[0], gi[1], gi[2], gh[0], gh[1], gh[2], hself[rr]).h;
                         if (publisher) {
                             const unsigned long long x = ((unsigned long long)(epoch + 1) << 32) | __float_as_uint(hself[rr]);
                             __hip_atomic_store(gran + (long)(epoch & 1) * R * H + (long)rr * H + j0 + my_u, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -609,49 +605,46 @@ __global__ __launch_bounds__(64) void k_plan_wave(PlanArgs a, unsigned long long
 
 extern "C" size_t lav_gru_cast_workspace_bytes(int, int, int, int, int) { return 0; }
 
+namespace {
+// lav_gru_cast and lav_embed_cast: one launch; `entry` names the entry point that was called in every message
+int cast_launch(const char *entry, const float *embd, int B, int embd_dim, int H, int num_cmds, int T, const float *w_ih, const float *w_hh,
+                const float *b_ih, const float *b_hh, const float *mlp_w, const float *mlp_b, float *out, const CastExtra &x, void *stream) {
+    LAV_REQUIRE(B >= 0 && embd_dim > 0 && x.hw >= 1 && num_cmds > 0 && T > 0, "%s: bad sizes", entry);
+    LAV_REQUIRE(embd_dim <= 1024, "%s: embedding of %d > 1024 values", entry, embd_dim);
+    LAV_REQUIRE(H == CAST_H, "%s: hidden size %d not instantiated (%d)", entry, H, CAST_H);
+    LAV_REQUIRE(B <= 65535, "%s: B too large", entry);
+    if (B == 0) return LAV_OK;   // (before any pointer check: the buffers of an empty batch may all be null)
+    LAV_REQUIRE((x.cmd_w == nullptr) == (x.cmds_out == nullptr) && (x.cmd_w == nullptr) == (x.cmd_b == nullptr), "%s: cmd_w, cmd_b and cmds_out come together", entry);
+    LAV_REQUIRE(embd && w_ih && w_hh && b_ih && b_hh && mlp_w && mlp_b && out, "%s: null argument", entry);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int tok = timer_begin("gru_cast", st);
+    hipLaunchKernelGGL(k_gru_cast, dim3(num_cmds, B), dim3(CAST_THREADS), 0, st, embd, embd_dim, num_cmds, T, w_ih, w_hh, b_ih, b_hh, mlp_w, mlp_b, out,
+                       lav::batch_limit(), x);
+    timer_end(tok, st);
+    LAV_LAUNCH_CHECK();
+    return LAV_OK;
+}
+}  // namespace
+
 extern "C" int lav_gru_cast(const float *embd, int B, int embd_dim, int H, int num_cmds, int T, const float *w_ih,
                             const float *w_hh, const float *b_ih, const float *b_hh, const float *mlp_w,
                             const float *mlp_b, float *out, void *, size_t, void *stream) {
-    LAV_REQUIRE(B >= 0 && embd_dim > 0 && num_cmds > 0 && T > 0, "lav_gru_cast: bad sizes");
-    LAV_REQUIRE(H == CAST_H, "lav_gru_cast: hidden size %d not instantiated (%d)", H, CAST_H);
-    LAV_REQUIRE(B <= 65535, "lav_gru_cast: B too large");
-    if (B == 0) return LAV_OK;
-    LAV_REQUIRE(embd && w_ih && w_hh && b_ih && b_hh && mlp_w && mlp_b && out, "lav_gru_cast: null argument");
-    const int tok = timer_begin("gru_cast", static_cast<hipStream_t>(stream));
-    LAV_REQUIRE(embd_dim <= 1024, "lav_gru_cast: embedding of %d > 1024 values", embd_dim);
-    hipLaunchKernelGGL(k_gru_cast, dim3(num_cmds, B), dim3(CAST_THREADS), 0, static_cast<hipStream_t>(stream), embd, embd_dim,
-                       num_cmds, T, w_ih, w_hh, b_ih, b_hh, mlp_w, mlp_b, out, lav::batch_limit(), CastExtra{1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
-    timer_end(tok, static_cast<hipStream_t>(stream));
-    LAV_LAUNCH_CHECK();
-    return LAV_OK;
+    return cast_launch("lav_gru_cast", embd, B, embd_dim, H, num_cmds, T, w_ih, w_hh, b_ih, b_hh, mlp_w, mlp_b, out,
+                       CastExtra{1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, stream);
 }
 
 extern "C" int lav_embed_cast(const float *feat, int B, int embd_dim, int hw, float *embd_out, int H, int num_cmds, int T,
                               const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *mlp_w,
                               const float *mlp_b, const float *cmd_w, const float *cmd_b, float *cmds_out, const float *oris,
                               const float *locs, float *out, void *stream) {
-    LAV_REQUIRE(B >= 0 && embd_dim > 0 && embd_dim <= 1024 && hw >= 1 && num_cmds > 0 && T > 0, "lav_embed_cast: bad sizes");
-    LAV_REQUIRE(H == CAST_H, "lav_embed_cast: hidden size %d not instantiated (%d)", H, CAST_H);
-    LAV_REQUIRE(B <= 65535, "lav_embed_cast: B too large");
-    if (B == 0) return LAV_OK;   // (before any pointer check: the buffers of an empty batch may all be null)
-    LAV_REQUIRE((cmd_w == nullptr) == (cmds_out == nullptr) && (cmd_w == nullptr) == (cmd_b == nullptr), "lav_embed_cast: cmd_w, cmd_b and cmds_out come together");
-    LAV_REQUIRE(feat && w_ih && w_hh && b_ih && b_hh && mlp_w && mlp_b && out, "lav_embed_cast: null argument");
-    const int tok = timer_begin("gru_cast", static_cast<hipStream_t>(stream));
-    hipLaunchKernelGGL(k_gru_cast, dim3(num_cmds, B), dim3(CAST_THREADS), 0, static_cast<hipStream_t>(stream), feat, embd_dim,
-                       num_cmds, T, w_ih, w_hh, b_ih, b_hh, mlp_w, mlp_b, out, lav::batch_limit(), CastExtra{hw, embd_out, cmd_w, cmd_b, cmds_out, oris, locs});
-    timer_end(tok, static_cast<hipStream_t>(stream));
-    LAV_LAUNCH_CHECK();
-    return LAV_OK;
+    return cast_launch("lav_embed_cast", feat, B, embd_dim, H, num_cmds, T, w_ih, w_hh, b_ih, b_hh, mlp_w, mlp_b, out,
+                       CastExtra{hw, embd_out, cmd_w, cmd_b, cmds_out, oris, locs}, stream);
 }
 
 extern "C" size_t lav_gru_plan_workspace_bytes(int B, int H, int num_cmds, int T) {
-    // step-per-launch path: h sequence [T][R][H] floats; persistent path: 2 granule buffers [R][H] u64 + status word
-    // (+ many-row path: initial state [R][H] and inputs [R][T][4])
-    // Layout: [0, 256) sticky counters (launches / aborted launches since the caller zero-filled the workspace), [256, 512) the
-    // status + diagnosis words of the last persistent launch, from PLAN_CTRL_BYTES on the granules resp. the step path's buffers.
-    const size_t seq = ((size_t)T * B * num_cmds * H + (size_t)B * num_cmds * H + (size_t)B * num_cmds * T * 4) * sizeof(float) + 512;
-    const size_t gran = lav::align_up(2 * (size_t)PLAN_RC * H * sizeof(unsigned long long), 256);
-    return lav::align_up(seq > gran ? seq : gran, 256) + PLAN_CTRL_BYTES;
+    // every path of every call with these sizes: all B * num_cmds rows on the MFMA step path, or up to PLAN_RC rows in the persistent kernel
+    const size_t all = PlanLayout(B * num_cmds, H, T).mfma_bytes(), few = PlanLayout(PLAN_RC, H, T).persistent_bytes();
+    return lav::align_up(all > few ? all : few, 256);
 }
 
 namespace {
@@ -667,29 +660,29 @@ int plan_launch(bool allow_persistent, const float *embd, const float *nxp, cons
     PlanArgs a;
     a.embd = embd; a.nxp = nxp; a.cast_locs = cast_locs;
     a.w_ih = w_ih; a.w_hh = w_hh; a.b_ih = b_ih; a.b_hh = b_hh; a.mlp_w = mlp_w; a.mlp_b = mlp_b;
-    a.out = out; a.hseq = reinterpret_cast<float *>(static_cast<char *>(workspace) + PLAN_CTRL_BYTES);
+    char *ws = static_cast<char *>(workspace);
+    a.out = out; a.hseq = PlanLayout::hseq(ws);
     a.B = B; a.H = H; a.num_cmds = num_cmds; a.T = T; a.iters = iters; a.cmd = cmd;
     a.NC = cmd >= 0 ? 1 : num_cmds;
     a.R = B * a.NC;
     a.ppm = pixels_per_meter; a.crop = crop_size;
-    const size_t need = (size_t)T * a.R * H * sizeof(float) + PLAN_CTRL_BYTES;
-    if (!workspace || workspace_bytes < need) return lav::fail(LAV_EWORKSPACE, "lav_gru_plan: workspace %zu < %zu bytes", workspace_bytes, need);
+    const PlanLayout L(a.R, H, T);
+    if (!workspace || workspace_bytes < L.valu_bytes())
+        return lav::fail(LAV_EWORKSPACE, "lav_gru_plan: workspace %zu < %zu bytes", workspace_bytes, L.valu_bytes());
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int tok = timer_begin("gru_plan", st);
     const char *impl = getenv("LAV_PLAN_IMPL");   // A/B knob: steps = one launch per step; v (below); anything else: the persistent kernel
     if (allow_persistent && a.R <= PLAN_RC && !(impl && impl[0] == 's')) {
         // persistent kernel: its H/8 workgroups (64 of 256 CUs) must become co-resident while other streams' kernels hold the
         // chip - not guaranteed by HIP, hence the bounded spins, the status / diagnosis words and the NaN poisoning
-        const size_t gbytes = 2 * (size_t)a.R * H * sizeof(unsigned long long);
-        LAV_REQUIRE(workspace_bytes >= lav::align_up(gbytes, 256) + PLAN_CTRL_BYTES, "lav_gru_plan: workspace too small for the persistent kernel");
-        unsigned long long *gran = reinterpret_cast<unsigned long long *>(static_cast<char *>(workspace) + PLAN_CTRL_BYTES);
-        int *sticky = static_cast<int *>(workspace);
-        int *status = sticky + 64;
+        LAV_REQUIRE(workspace_bytes >= L.persistent_bytes(), "lav_gru_plan: workspace too small for the persistent kernel");
+        unsigned long long *gran = reinterpret_cast<unsigned long long *>(ws + PlanLayout::DATA_OFF);
+        int *sticky = reinterpret_cast<int *>(ws + PlanLayout::STICKY_OFF), *status = reinterpret_cast<int *>(ws + PlanLayout::STATUS_OFF);
         // status words and tags start at 0.  A kernel, not hipMemsetAsync: a memset node captured into a HIP graph replays with a
-        // garbage fill value on ROCm 7.2 (first replay fine, later ones wrote a pointer-like pattern: every graph-mode frame of
-        // round 3 read a non-zero status word and poisoned a plan that had in fact completed - tools/plan_timeout_probe.py)
-        const unsigned reset_words = (unsigned)((256 + lav::align_up(gbytes, 256)) / 4);
-        hipLaunchKernelGGL(k_plan_reset, dim3((reset_words / 4 + 255) / 256), dim3(256), 0, st, reinterpret_cast<uint4 *>(status), reset_words / 4);
+        // garbage fill value on ROCm 7.2 (first replay fine, later ones wrote a pointer-like pattern: graph-mode frames read a
+        // non-zero status word and poisoned a plan that had in fact completed - tools/plan_timeout_probe.py)
+        const unsigned reset16 = (unsigned)(L.reset_bytes() / sizeof(uint4));
+        hipLaunchKernelGGL(k_plan_reset, dim3((reset16 + 255) / 256), dim3(256), 0, st, reinterpret_cast<uint4 *>(status), reset16);
         const char *lim = getenv("LAV_PLAN_SPIN_LIMIT");   // test knob: 1 forces the time-out path
         const long long spin_limit = lim && atoll(lim) > 0 ? atoll(lim) : PLAN_SPIN_LIMIT;
         // k_plan_wave keeps nothing of its recurrence in LDS.  tests/test_gpu_paint_gru.py compares it with the step path, and
@@ -704,10 +697,9 @@ int plan_launch(bool allow_persistent, const float *embd, const float *nxp, cons
         LAV_LAUNCH_CHECK();
         return LAV_OK;
     }
-    const size_t seq_floats = lav::align_up((size_t)T * a.R * H, 64);
-    const bool many_rows = a.R >= PLAN_MFMA_MIN_ROWS && workspace_bytes >= (seq_floats + (size_t)a.R * H + 64 + (size_t)a.R * T * 4) * sizeof(float) + PLAN_CTRL_BYTES &&
+    const bool many_rows = a.R >= PLAN_MFMA_MIN_ROWS && workspace_bytes >= L.mfma_bytes() &&
                            !(impl && impl[0] == 'v');   // LAV_PLAN_IMPL=v: the VALU step kernel at any size (A/B knob)
-    float *h0 = a.hseq + seq_floats, *u = h0 + lav::align_up((size_t)a.R * H, 64);
+    float *h0 = L.h0(ws), *u = L.u(ws);
     for (int it = 0; it < iters; ++it) {
         if (many_rows) {
             hipLaunchKernelGGL(k_plan_inputs, dim3((unsigned)(((long)a.R * T + 255) / 256)), dim3(256), 0, st, a, it, u, h0);
@@ -754,9 +746,9 @@ extern "C" int lav_gru_plan_status(const void *workspace, size_t workspace_bytes
     const int R = B * (cmd >= 0 ? 1 : num_cmds);
     *h_status = 0;
     if (R > PLAN_RC) return LAV_OK;   // the step-per-launch path has no spin loops
-    LAV_REQUIRE(workspace_bytes >= PLAN_CTRL_BYTES, "lav_gru_plan_status: workspace too small");
+    LAV_REQUIRE(workspace_bytes >= PlanLayout::DATA_OFF, "lav_gru_plan_status: workspace too small");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    LAV_HIP(hipMemcpyAsync(h_status, static_cast<const char *>(workspace) + 256, sizeof(int), hipMemcpyDeviceToHost, st));
+    LAV_HIP(hipMemcpyAsync(h_status, static_cast<const char *>(workspace) + PlanLayout::STATUS_OFF, sizeof(int), hipMemcpyDeviceToHost, st));
     LAV_HIP(hipStreamSynchronize(st));
     return LAV_OK;
 }
@@ -766,10 +758,11 @@ extern "C" int lav_gru_plan_diag(const void *workspace, size_t workspace_bytes, 
     LAV_REQUIRE(workspace && h_words16, "lav_gru_plan_diag: null argument");
     LAV_REQUIRE(B >= 1 && H > 0 && num_cmds > 0 && cmd >= -1 && cmd < num_cmds, "lav_gru_plan_diag: bad sizes");
     for (int i = 0; i < 16; ++i) h_words16[i] = 0;
-    LAV_REQUIRE(workspace_bytes >= PLAN_CTRL_BYTES, "lav_gru_plan_diag: workspace too small");
+    LAV_REQUIRE(workspace_bytes >= PlanLayout::DATA_OFF, "lav_gru_plan_diag: workspace too small");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    LAV_HIP(hipMemcpyAsync(h_words16, static_cast<const char *>(workspace) + 256, 10 * sizeof(int), hipMemcpyDeviceToHost, st));
-    LAV_HIP(hipMemcpyAsync(h_words16 + 10, workspace, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    const char *ws = static_cast<const char *>(workspace);
+    LAV_HIP(hipMemcpyAsync(h_words16, ws + PlanLayout::STATUS_OFF, PlanLayout::STATUS_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));
+    LAV_HIP(hipMemcpyAsync(h_words16 + PlanLayout::STATUS_WORDS, ws + PlanLayout::STICKY_OFF, PlanLayout::STICKY_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));
     LAV_HIP(hipStreamSynchronize(st));
     return LAV_OK;
 }

@@ -21,14 +21,13 @@
 // are contiguous (lane (m, kg) holds k = kb + 4 kg + i for the i-th of four consecutive matrix instructions).
 // fp32 throughout; precise expf / tanhf.
 #include "common.hpp"
+#include "gru_cell.hpp"
 #include "gru_seq.hpp"
 
 namespace {
 using namespace lav;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
 // acc[i] += A[16 rows][k_lo, k_hi) . B_i[16 cols][k_lo, k_hi)^T for NB matrices B_i that share A.  a_row / b_row[i]: this
 // lane's row of A (m = lane & 15) and of B_i (n = lane & 15), both k-contiguous; the k range is a multiple of 16.
@@ -101,15 +100,13 @@ __global__ __launch_bounds__(256) void k_gru_fwd_step(FwdArgs a) {
         for (int g = 0; g < 3; ++g) xg[g] = xr[g * H + j];
     }
     const float hp = a.h_prev[(long)r * a.h_prev_stride + j];
-    const float rg = sigm(xg[0] + gh[0]);
-    const float zg = sigm(xg[1] + gh[1]);
-    const float ng = tanhf(xg[2] + rg * gh[2]);
-    a.h_out[(long)r * a.h_out_stride + j] = (1.f - zg) * ng + zg * hp;
+    const GruGates g = gru_gates(xg[0], xg[1], xg[2], gh[0], gh[1], gh[2], hp);
+    a.h_out[(long)r * a.h_out_stride + j] = g.h;
     if (a.tape) {
         float *tp = a.tape + (long)r * a.tape_stride;
-        tp[j] = rg;
-        tp[H + j] = zg;
-        tp[2 * H + j] = ng;
+        tp[j] = g.r;
+        tp[H + j] = g.z;
+        tp[2 * H + j] = g.n;
         tp[3 * H + j] = gh[2];
     }
 }

@@ -967,36 +967,32 @@ def gru_seq(x, h0, w_hh, b_hh, T: int):
     return _GruSeq.apply(x, h0, w_hh, b_hh, int(T))
 
 
+def _plan_workspace(device, stream):
+    """(the plan workspace of `stream` on `device` or None when gru_plan has not run there, the stream)"""
+    device, st = _device_and_stream(device, stream)
+    return _workspaces.get(("plan", device, st.cuda_stream)), st
+
+
 def gru_plan_status(B: int, H: int, num_cmds: int, cmd: int, device, stream=None) -> int:
     """Status word of the last gru_plan launch on `stream` (default: the current one) with these sizes: 0 = completed,
     1 = the persistent kernel gave up waiting for its peers and returned NaN.  Synchronises that stream."""
-    lib = _lib.load()
-    st = stream if stream is not None else torch.cuda.current_stream()
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    ws = _workspaces.get(("plan", device, st.cuda_stream))
+    ws, st = _plan_workspace(device, stream)
     if ws is None:
         return 0
     status = C.c_int(0)
-    check(lib.lav_gru_plan_status(_ptr(ws), ws.numel(), B, H, num_cmds, cmd, C.byref(status), st.cuda_stream), "lav_gru_plan_status")
+    check(_lib.load().lav_gru_plan_status(_ptr(ws), ws.numel(), B, H, num_cmds, cmd, C.byref(status), st.cuda_stream), "lav_gru_plan_status")
     return int(status.value)
 
 
 def gru_plan_diag(B: int, H: int, num_cmds: int, cmd: int, device, stream=None) -> dict:
     """The diagnosis words of the last persistent gru_plan launch on `stream` (include/lav_amd.h: lav_gru_plan_diag)."""
-    lib = _lib.load()
-    st = stream if stream is not None else torch.cuda.current_stream()
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    ws = _workspaces.get(("plan", device, st.cuda_stream))
+    ws, st = _plan_workspace(device, stream)
     names = ("status", "entered", "abort_wg_plus1", "abort_wave", "abort_epoch", "abort_spins", "missing_granule", "tag_seen",
              "abort_us", "completed", "aborted_launches", "launches")
     if ws is None:
         return dict.fromkeys(names, 0)
     words = (C.c_int * 16)()
-    check(lib.lav_gru_plan_diag(_ptr(ws), ws.numel(), B, H, num_cmds, cmd, words, st.cuda_stream), "lav_gru_plan_diag")
+    check(_lib.load().lav_gru_plan_diag(_ptr(ws), ws.numel(), B, H, num_cmds, cmd, words, st.cuda_stream), "lav_gru_plan_diag")
     return dict(zip(names, list(words)))
 
 

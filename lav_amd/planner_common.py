@@ -20,17 +20,14 @@ def _hip_train(what: str) -> bool:
 
 def stack_cast_weights(grus, mlps, device):
     """6 x nn.GRU(512,64) + 6 x nn.Linear(64,2) -> the stacked arrays lav_gru_cast takes."""
-    g = lambda n: torch.stack([getattr(m, n).detach() for m in grus]).float().contiguous().to(device)
-    return dict(w_ih=g("weight_ih_l0"), w_hh=g("weight_hh_l0"), b_ih=g("bias_ih_l0"), b_hh=g("bias_hh_l0"),
-                mlp_w=torch.stack([m.weight.detach() for m in mlps]).float().contiguous().to(device),
-                mlp_b=torch.stack([m.bias.detach() for m in mlps]).float().contiguous().to(device))
+    g = lambda mods, n: torch.stack([getattr(m, n).detach() for m in mods]).float().contiguous().to(device)
+    return dict(w_ih=g(grus, "weight_ih_l0"), w_hh=g(grus, "weight_hh_l0"), b_ih=g(grus, "bias_ih_l0"), b_hh=g(grus, "bias_hh_l0"),
+                mlp_w=g(mlps, "weight"), mlp_b=g(mlps, "bias"))
 
 
 def plan_weights(gru, mlp, device):
-    g = lambda n: getattr(gru, n).detach().float().contiguous().to(device)
-    return dict(w_ih=g("weight_ih_l0"), w_hh=g("weight_hh_l0"), b_ih=g("bias_ih_l0"), b_hh=g("bias_hh_l0"),
-                mlp_w=mlp.weight.detach().float().contiguous().to(device),
-                mlp_b=mlp.bias.detach().float().contiguous().to(device))
+    """The same arrays for the one plan GRU and its Linear, as lav_gru_plan takes them."""
+    return {k: v[0] for k, v in stack_cast_weights([gru], [mlp], device).items()}
 
 
 def crop_feature(features, rel_locs, rel_oris, pixels_per_meter, crop_size, offset_x, offset_y):

@@ -436,6 +436,23 @@ def test_plan_kernel_has_no_lds_instruction_and_no_barrier(tmp_path):
     assert found == 4, f"{found} k_plan_wave instantiations found (expected <1,8>, <1,0>, <6,8>, <6,0>)"
 
 
+@pytest.mark.parametrize("num_cmds", [1, 6])
+@pytest.mark.parametrize("H", [64, 192, 512])
+def test_plan_workspace_size_covers_every_path_and_no_more(H, num_cmds):
+    """lav_gru_plan_workspace_bytes (pure host code) is a multiple of 256 between what the paths read - the 512-byte control block,
+    then the larger of the MFMA step path's state sequence, initial state and inputs and the persistent kernel's two granule buffers
+    of 6 rows - and the size of the library before the workspace had one description, which carried 512 bytes nothing read."""
+    lib = _lib.load()
+    align = lambda v, a: (v + a - 1) // a * a
+    for B in (1, 2, 8, 64):
+        for T in (1, 20, 64):
+            R = B * num_cmds
+            got = lib.lav_gru_plan_workspace_bytes(B, H, num_cmds, T)
+            floor = 512 + max(4 * (T * R * H + R * H + 4 * R * T), 2 * 6 * H * 8)
+            before = align(max(4 * (T * R * H + R * H + 4 * R * T) + 512, align(2 * 6 * H * 8, 256)), 256) + 512
+            assert got % 256 == 0 and floor <= got <= before, f"B={B} H={H} num_cmds={num_cmds} T={T}: {floor} <= {got} <= {before}"
+
+
 def test_library_holds_no_packed_fp32_with_op_sel(tmp_path):
     """Round 5, the root cause of round 4's finite-but-wrong results (profiles/r05_coresidency.md): on gfx950 a packed
     fp32 instruction (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32) whose op_sel bit is set for a source - the LOW result takes the

@@ -74,14 +74,19 @@ _PLAN_RUNS = [(c, "auto") for c in U.PLAN_CASES] + [(c, "steps") for c in U.PLAN
 def test_plan_equals_float64_on_every_path(case, how, monkeypatch):
     """An MFMA row and the same row under LAV_PLAN_IMPL=v agree only within the bound, not bit for bit: the MFMA step sums the
     recurrent product in four quarters of the reduction dimension (one per wave, 16x16x4 blocks) that meet in LDS, the VALU kernel
-    in 8-term chains per lane and a 6-level butterfly; the input projection and the gates follow, on different partial sums."""
+    in 8-term chains per lane and a 6-level butterfly; the input projection and the gates follow, on different partial sums.
+    That they do differ is asserted: a default launch that silently fell back to the VALU kernel (16 or more state rows whose
+    workspace the library no longer takes for large enough) is inside every bound above, and only this tells it from the MFMA step."""
     if how == "valu_knob":
+        default = _plan(case).clone()
         monkeypatch.setenv("LAV_PLAN_IMPL", "v")
     got = _plan(case, impl="steps" if how == "steps" else "auto")
     path = case.path if how == "auto" else "valu"
     if path.startswith("persistent"):
         _completed(case)
     _within(got, U.plan_case(case), f"plan {path} {case.id}")
+    if how == "valu_knob":
+        assert not torch.equal(got, default), f"{case.id}: the default launch equals the VALU step kernel bit for bit: it did not run the MFMA step"
 
 
 # ------------------------------------------------------------------------------------------------ b. path identities
