@@ -260,7 +260,11 @@ typedef struct lav_conv {
                           fp32 operand split exactly into three bf16 pieces and the six leading partial products accumulated
                           in fp32 (error of an fp32 dot product, 2.4x the matrix rate; fp32 subnormal inputs are flushed; every
                           finite input up to FLT_MAX is split exactly; an Inf or NaN activation / weight gives NaN in the
-                          outputs it reaches, where LAV_CONV_F32 and the reference's cuDNN path propagate Inf as Inf);
+                          outputs it reaches, where LAV_CONV_F32 and the reference's cuDNN path propagate Inf as Inf - through
+                          the epilogue too: relu_pre / relu_post keep a NaN as torch.relu does (csrc/common.hpp relu_nan), in
+                          every kernel of the library with a ReLU or a 2x2 max-pool, the train-mode BatchNorm included;
+                          tests/test_gpu_nonfinite.py.  Not so where NaN has a meaning of its own: the pillar kernels (NaN =
+                          absent point) and lav_extract_peaks (a NaN is ignored inside every window), nor in backward kernels);
                           0 = the library default (environment LAV_CONV_PRECISION = f32 | bf16x6, default bf16x6).  The
                           packed weights of a layer depend on it: pack and run with the same descriptor.  Launch note: a
                           workgroup of the split-operand kernel asks for the LDS its tiles need and no more, so kernels of
@@ -282,7 +286,8 @@ typedef struct lav_conv {
                               within 2^-20 of their tensors' maxima keep the 2e-6 of sum|w||x| bar of BF16X6 (measured <= 2.6e-7);
                               at 2^-30 the error reached 2.8e-4 of sum|w||x|.  fp32 SUBNORMAL activations are not flushed (unlike
                               BF16X6): they are scaled like any value and count when the scaled value is above 2^-25, i.e. when the
-                              tensor's maximum is small; Inf / NaN make the outputs they reach non-finite and change no other bit.
+                              tensor's maximum is small; Inf / NaN make the outputs they reach non-finite - the epilogue's ReLUs keep them -
+                              and change no other bit (the scale hand-offs take the largest FINITE magnitude).
                               Magnitudes up to FLT_MAX are exact as in BF16X6: the epilogue applies s_x s_w as two balanced powers
                               of two, so neither it nor acc * s_x overflows where y does not.  The activations' magnitude comes from the launches that
                               wrote them (lav_conv2d_amax below) or, without that, from one measuring launch in front of the

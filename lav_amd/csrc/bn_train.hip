@@ -81,11 +81,11 @@ __global__ __launch_bounds__(256) void k_bn_stats(BnGeom g, const float *__restr
             float e[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const double t = (double)(relu_pre ? fmaxf(e[k], 0.f) : e[k]);
+                const double t = (double)(relu_pre ? lav::relu_nan(e[k]) : e[k]);
                 sum += t; sq += t * t;
             }
         } else {
-            const double t = (double)(relu_pre ? fmaxf(x[at], 0.f) : x[at]);
+            const double t = (double)(relu_pre ? lav::relu_nan(x[at]) : x[at]);
             sum += t; sq += t * t;
         }
     });
@@ -113,18 +113,19 @@ __global__ __launch_bounds__(256) void k_bn_apply(BnGeom g, const float *__restr
     double a, b;
     channel_sums(g, c, partial, a, b);
     const double mean_d = a / (double)g.N;
-    const double var_d = fmax(b / (double)g.N - mean_d * mean_d, 0.0);   // biased, as the normalisation uses it
+    const double dv = b / (double)g.N - mean_d * mean_d;
+    const double var_d = (dv > 0.0 || dv != dv) ? dv : 0.0;   // biased, as the normalisation uses it; a NaN channel keeps a NaN variance (fmax would give 0)
     const float mean = (float)mean_d, rstd = (float)(1.0 / sqrt(var_d + eps));
     if (s == 0 && threadIdx.x == 0) { save_mean[c] = mean; save_var[c] = (float)var_d; save_rstd[c] = rstd; }
     const float ga = gamma[c], be = beta[c];
     float am = 0.f;
     float m = 1.f;
     auto one = [&](float v, float r) {
-        const float t = relu_pre ? fmaxf(v, 0.f) : v;
+        const float t = relu_pre ? lav::relu_nan(v) : v;
         float o;
         if constexpr (MASK) o = m * fmaf((t - mean) * rstd, ga, be) + r;
         else o = fmaf((t - mean) * rstd, ga, be) + r;
-        o = relu_post ? fmaxf(o, 0.f) : o;
+        o = relu_post ? lav::relu_nan(o) : o;
         am = fmaxf(am, lav::finite_abs(o));
         return o;
     };
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_sums(BnGeom g, const float *__re
             const float xe[4] = {xv.x, xv.y, xv.z, xv.w}, ge[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float t = relu_pre ? fmaxf(xe[k], 0.f) : xe[k];
+                const float t = relu_pre ? lav::relu_nan(xe[k]) : xe[k];
                 sg += (double)ge[k];
                 sgx += (double)ge[k] * (double)((t - mean) * rstd);
             }
@@ -176,7 +177,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_sums(BnGeom g, const float *__re
             if (relu_post) gg = y[at] > 0.f ? gg : 0.f;
             if (dres) dres[at] = gg;
             if constexpr (MASK) gg *= m;
-            const float t = relu_pre ? fmaxf(x[at], 0.f) : x[at];
+            const float t = relu_pre ? lav::relu_nan(x[at]) : x[at];
             sg += (double)gg;
             sgx += (double)gg * (double)((t - mean) * rstd);
         }
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(BnGeom g, const float *__r
     auto one = [&](float xv, float gv, float yv) {
         if (mask_here) gv = yv > 0.f ? gv : 0.f;
         if constexpr (MASK) gv *= m;
-        const float t = relu_pre ? fmaxf(xv, 0.f) : xv;
+        const float t = relu_pre ? lav::relu_nan(xv) : xv;
         float o = k0 * (gv - mg - (t - mean) * rstd * mgx);
         o = (relu_pre && !(xv > 0.f)) ? 0.f : o;
         am = fmaxf(am, lav::finite_abs(o));

@@ -78,6 +78,17 @@ __device__ __forceinline__ float parts_absmax(const float *__restrict__ parts, i
     return wave_finite_absmax(m);
 }
 
+// ---- NaN through every epilogue (lav_amd.h: a non-finite value "gives NaN in the outputs it reaches"; tests/test_gpu_nonfinite.py)
+// IEEE 754-2019 maximum: a NaN operand gives NaN and -0 < +0.  On gfx950 it is ONE v_maximum3_f32, where fmaxf (maxNum: the NaN is
+// dropped) costs a canonicalising v_max_f32 and the v_max_f32 itself, and `(v > m || v != v) ? v : m` - k_maxpool3s2's idiom, the
+// same function but for the sign of a zero - a compare and a select.  Finite operands give the bits fmaxf gives.
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+// The ReLU as torch.relu: a NaN stays a NaN (`v > 0.f ? v : 0.f` and fmaxf(v, 0.f) both turn it into 0, finite garbage that no health
+// check counts).  -0 and every negative still give +0: finite data keeps its bits.
+__device__ __forceinline__ float relu_nan(float v) { return max_nan(v, 0.f); }
+// The 2x2 maximum as F.max_pool2d (two v_maximum3_f32)
+__device__ __forceinline__ float max_nan4(float a, float b, float c, float d) { return max_nan(max_nan(a, b), max_nan(c, d)); }
+
 #define LAV_HIP(expr)                                                                                      \
     do {                                                                                                   \
         hipError_t lav_e_ = (expr);                                                                        \

@@ -345,10 +345,10 @@ __global__ __launch_bounds__(256, 2) void k_conv(ConvArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 float v = acc[mc][mp][r] + bv[r];
-                if (a.relu_pre) v = v > 0.f ? v : 0.f;
+                if (a.relu_pre) v = relu_nan(v);
                 v = fmaf(v, sv[r], tv[r]);
                 v += rv[r];
-                if (a.relu_post) v = v > 0.f ? v : 0.f;
+                if (a.relu_post) v = relu_nan(v);
                 if (a.sigmoid && cov[r] >= a.sigmoid - 1) v = 1.f / (1.f + expf(-v));
                 if (pix_ok && cov[r] < a.cout) a.y[cbase + (long)cov[r] * a.OH * a.OW + pix] = v;
             }
@@ -378,11 +378,11 @@ __global__ __launch_bounds__(256) void k_conv_reduce(ConvArgs a, int batch, floa
         float v = 0.f;
         for (int ks = 0; ks < a.ksplit; ++ks) v += a.partial[(long)ks * total + e];
         if (a.bias) v += a.bias[co];
-        if (a.relu_pre) v = v > 0.f ? v : 0.f;
+        if (a.relu_pre) v = relu_nan(v);
         if (a.scale) v = fmaf(v, a.scale[co], a.shift[co]);
         const long idx = ((long)n * a.out_c_total + a.out_c_offset + co) * plane_o + pix;
         if (a.res) v += a.res[idx];
-        if (a.relu_post) v = v > 0.f ? v : 0.f;
+        if (a.relu_post) v = relu_nan(v);
         if (a.sigmoid && co >= a.sigmoid - 1) v = 1.f / (1.f + expf(-v));
         a.y[idx] = v;
         m = reduce_finite_abs(v);
@@ -743,11 +743,11 @@ __global__ __launch_bounds__(MC == 1 ? 1024 : 512) void k_conv_direct(DirectArgs
             continue;
         }
         if (a.bias) v += a.bias[co];
-        if (a.relu_pre) v = v > 0.f ? v : 0.f;
+        if (a.relu_pre) v = relu_nan(v);
         if (a.scale) v = fmaf(v, a.scale[co], a.shift[co]);
         const long idx = ((long)on * a.out_c_total + a.out_c_offset + co) * plane_o + opix;
         if (a.res) v += a.res[idx];
-        if (a.relu_post) v = v > 0.f ? v : 0.f;
+        if (a.relu_post) v = relu_nan(v);
         if (a.sigmoid && co >= a.sigmoid - 1) v = 1.f / (1.f + expf(-v));
         a.y[idx] = v;
         wmax = fmaxf(wmax, reduce_finite_abs(v));

@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair(PairArgs a) {
         for (int r = 0; r < 16; ++r) {
             const int co = cg * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
             const float v = acc[r] + bAv[r];
-            if (co < C) s_mid[co * WM + a.dB + px] = v > 0.f ? v : 0.f;
+            if (co < C) s_mid[co * WM + a.dB + px] = relu_nan(v);
         }
     }
     __syncthreads();
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair(PairArgs a) {
     for (int r = 0; r < 16; ++r) {
         const int co = cg * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
         float v = fmaf(acc[r] + bBv[r], sv[r], tv[r]) + rv[r];
-        if (a.relu_post) v = v > 0.f ? v : 0.f;
+        if (a.relu_post) v = relu_nan(v);
         if (co < C) a.y[base + co * plane] = v;
     }
     PAIR_STAMP(6);
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_split(PairSplitArgs a)
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const float v0 = acc[4 * g8 + 2 * e] + bAv[4 * g8 + 2 * e], v1 = acc[4 * g8 + 2 * e + 1] + bAv[4 * g8 + 2 * e + 1];
-                split3_pair(v0 > 0.f ? v0 : 0.f, v1 > 0.f ? v1 : 0.f, pk[0][e], pk[1][e], pk[2][e]);
+                split3_pair(relu_nan(v0), relu_nan(v1), pk[0][e], pk[1][e], pk[2][e]);
             }
             const int grp = cg * 4 + g8;   // 8-channel group = chunk * 2 + k half
             if (grp * 8 < C) {
@@ -456,7 +456,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_split(PairSplitArgs a)
         float v = acc[r] + bBv[r];
         if (a.scale) v = fmaf(v, sv[r], tv[r]);
         if (a.res) v += rv[r];
-        if (a.relu_post) v = v > 0.f ? v : 0.f;
+        if (a.relu_post) v = relu_nan(v);
         if (co < C) a.y[base + co * plane] = v;
     }
 }
@@ -697,7 +697,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_chain(PairChainArgs a)
                 for (int e = 0; e < 2; ++e) {
                     const int cch = min(cg * 32 + 8 * g8 + 4 * half + 2 * e, C - 2);
                     const float v0 = acc[4 * g8 + 2 * e] + s_epi[0][cch], v1 = acc[4 * g8 + 2 * e + 1] + s_epi[0][cch + 1];
-                    split3_pair(v0 > 0.f ? v0 : 0.f, v1 > 0.f ? v1 : 0.f, pk[0][e], pk[1][e], pk[2][e]);
+                    split3_pair(relu_nan(v0), relu_nan(v1), pk[0][e], pk[1][e], pk[2][e]);
                 }
                 const int grp = cg * 4 + g8;
                 if (grp * 8 < C) {
@@ -755,7 +755,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_chain(PairChainArgs a)
                 const int co_ = min(cg * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, C - 1);
                 float v = fmaf(acc[r] + s_epi[1][co_], s_epi[2][co_], s_epi[3][co_]);   // the single-pair kernel's arithmetic, bit for bit
                 if (a.res[p]) v += blk_in[r];
-                if (a.relu[p]) v = v > 0.f ? v : 0.f;
+                if (a.relu[p]) v = relu_nan(v);
                 vout[r] = v;
             }
             float *yo = a.out[p];
@@ -1103,7 +1103,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_chain_f16(PairChainF16
                 for (int e = 0; e < 2; ++e) {
                     const int cch = min(cg * 32 + 8 * g8 + 4 * half + 2 * e, C - 2);
                     const float v0 = fmaf(acc[4 * g8 + 2 * e], fA, s_epi[0][cch]), v1 = fmaf(acc[4 * g8 + 2 * e + 1], fA, s_epi[0][cch + 1]);
-                    split2h_pair((v0 > 0.f ? v0 : 0.f) * inv_mid, (v1 > 0.f ? v1 : 0.f) * inv_mid, pk[0][e], pk[1][e]);
+                    split2h_pair(relu_nan(v0) * inv_mid, relu_nan(v1) * inv_mid, pk[0][e], pk[1][e]);
                 }
                 const int grp = cg * 4 + g8;
                 if (grp * 8 < C) {
@@ -1161,7 +1161,7 @@ __global__ __launch_bounds__(256 * KS) void k_conv1d_pair_chain_f16(PairChainF16
                 const int co = cg * 32 + (r & 3) + 8 * (r >> 2) + 4 * half, co_ = min(co, C - 1);
                 float vv = fmaf(fmaf(acc[r], fB, s_epi[1][co_]), s_epi[2][co_], s_epi[3][co_]);
                 if (a.res[p]) vv += blk_in[r];
-                if (a.relu[p]) vv = vv > 0.f ? vv : 0.f;
+                if (a.relu[p]) vv = relu_nan(vv);
                 own[r] = co < C ? vv : 0.f;
                 lm = fmaxf(lm, finite_abs(own[r]));
             }

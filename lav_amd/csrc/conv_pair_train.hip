@@ -66,7 +66,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_pair_fwd(PairGeom g, const float
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
         const int c = c0 + j * CS;
-        const float v = fmaxf(acc[j], 0.f);
+        const float v = relu_nan(acc[j]);
         ts[c * W + w] = v;
         t[at(b, c, h, w, C, g.H, W)] = v;
         acc[j] = bb[c];

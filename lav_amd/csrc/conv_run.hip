@@ -267,7 +267,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_run_f16(RunArgs a) {
                 for (int r = 0; r < 16; ++r) {
                     const int co = cb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
                     float vv = tot[r] * out_sx * out_sw;
-                    vv = vv > 0.f ? vv : 0.f;
+                    vv = relu_nan(vv);
                     vv = fmaf(vv, s_epi[co], s_epi[128 + co]);
                     if (px < W) {
                         if (last) yo[co * plane] = vv;

@@ -164,11 +164,11 @@ __global__ __launch_bounds__(128 * CS) void k_conv_smallcin(SmallCinArgs a) {
             for (int p = 0; p < PPT; ++p) {
                 if (co >= a.cout || !pok[p]) continue;
                 float v = acc[p][cl >> 1][cl & 1] + bb[j];
-                if (a.relu_pre) v = v > 0.f ? v : 0.f;
+                if (a.relu_pre) v = relu_nan(v);
                 v = fmaf(v, ss[j], hh[j]);
                 const long idx = ((long)n * a.out_c_total + a.out_c_offset + co) * plane_o + pix[p];
                 if (a.res) v += a.res[idx];
-                if (a.relu_post) v = v > 0.f ? v : 0.f;
+                if (a.relu_post) v = relu_nan(v);
                 if (a.sigmoid && co >= a.sigmoid - 1) v = 1.f / (1.f + expf(-v));
                 a.y[idx] = v;
             }

@@ -494,10 +494,10 @@ __device__ __forceinline__ void split_body(const SplitArgs &a, unsigned char *sm
                 float v;
                 if constexpr (F16) v = fmaf(acc[mc][mp][r] * out_sx, out_sw, bv[r]);   // the accumulators are in units of (activation scale x weight scale)
                 else v = acc[mc][mp][r] + bv[r];
-                if (a.relu_pre) v = v > 0.f ? v : 0.f;
+                if (a.relu_pre) v = relu_nan(v);
                 v = fmaf(v, sv[r], tv[r]);
                 v += has_res ? rv[r] : 0.f;
-                if (a.relu_post) v = v > 0.f ? v : 0.f;
+                if (a.relu_post) v = relu_nan(v);
                 if (a.sigmoid && cov[r] >= a.sigmoid - 1) v = 1.f / (1.f + expf(-v));
                 if (pix_ok && cov[r] < a.cout) {
                     a.y[cbase + (long)cov[r] * a.OH * a.OW + pix] = v;

@@ -138,7 +138,7 @@ __device__ __forceinline__ float tile_layer(const TileArgs &a, const unsigned ch
         for (int r = 0; r < 16; ++r) {
             const int co = cbw * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
             float vv = acc[j][r] * out_sx * out_sw;
-            vv = vv > 0.f ? vv : 0.f;
+            vv = relu_nan(vv);
             vv = fmaf(vv, s_epi[co], s_epi[64 + co]);
             vv = inmap[j] ? vv : 0.f;
             if (LAST) {

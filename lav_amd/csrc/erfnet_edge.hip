@@ -140,13 +140,13 @@ __global__ __launch_bounds__(256) void k_erfnet_entry(EntryArgs a) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const float *q = in0 + (c * EN_PN + 1) * EN_IS + 1;
-                    v[c + 1] = fmaxf(fmaxf(q[0], q[1]), fmaxf(q[EN_IS], q[EN_IS + 1]));
+                    v[c + 1] = max_nan4(q[0], q[1], q[EN_IS], q[EN_IS + 1]);
                 }
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float t = fmaf(v[j], ss[j], hh[j]);
-                t = t > 0.f ? t : 0.f;
+                t = relu_nan(t);
                 s_b1[(c0 + j) * EN_CS + ry * EN_RS + rx] = inside ? t : 0.f;
             }
         }
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void k_erfnet_entry(EntryArgs a) {
                     const int co = 16 * nt + 4 * kq + j;      // D row = 4 (lane >> 4) + register
                     float v = acc[nt][j] + e_b[co];
                     v = fmaf(v, e_s[co], e_t[co]);
-                    yn[co * plane + (long)oy * OW + ox] = v > 0.f ? v : 0.f;
+                    yn[co * plane + (long)oy * OW + ox] = relu_nan(v);
                 }
         }
     }
@@ -192,10 +192,10 @@ __global__ __launch_bounds__(256) void k_erfnet_entry(EntryArgs a) {
         for (int i = 0; i < 4; ++i) {
             const int it = tid + 256 * i, px = it & 7, py = (it >> 3) & 7, c = it >> 6;
             const float *q = s_b1 + c * EN_CS + (2 * py + 1) * EN_RS + 2 * px + 1;
-            float v = fmaxf(fmaxf(q[0], q[1]), fmaxf(q[EN_RS], q[EN_RS + 1]));
+            float v = max_nan4(q[0], q[1], q[EN_RS], q[EN_RS + 1]);
             v = fmaf(v, e_s[c], e_t[c]);
             const int oy = oy0 + py, ox = ox0 + px;
-            if (oy < OH && ox < OW) yn[(EN_C2C + c) * plane + (long)oy * OW + ox] = v > 0.f ? v : 0.f;
+            if (oy < OH && ox < OW) yn[(EN_C2C + c) * plane + (long)oy * OW + ox] = relu_nan(v);
         }
     }
 }

@@ -303,9 +303,9 @@ __global__ __launch_bounds__(256) void k_pool_affine(const float *__restrict__ x
     const long n = e / ((long)OW * OH * C);
     const float2 *p = reinterpret_cast<const float2 *>(x + ((n * C + c) * H + 2 * oy) * (long)W + 2 * ox);
     const float2 r0 = p[0], r1 = p[W >> 1];
-    float v = fmaxf(fmaxf(r0.x, r0.y), fmaxf(r1.x, r1.y));
+    float v = max_nan4(r0.x, r0.y, r1.x, r1.y);
     v = fmaf(v, scale[c], shift[c]);
-    if (relu) v = v > 0.f ? v : 0.f;
+    if (relu) v = relu_nan(v);
     y[((n * out_c_total + out_c_offset + c) * OH + oy) * (long)OW + ox] = v;
 }
 }  // namespace

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(HP_THREADS) void k_heads_at_peaks(HeadsPeaksArgs a)
         const int j = tid >> 3, ch = 8 * (tid & 7) + (j >> 2), p = j & 3;
         const bool have = ch < hid;
         const float sc = a.scale[g][have ? ch : 0], sh = a.shift[g][have ? ch : 0];
-        s_hid[ch * 4 + p] = have ? fmaf(fmaxf(v, 0.f), sc, sh) : 0.f;   // ConvLayer's relu_pre order: ReLU, then the folded BatchNorm
+        s_hid[ch * 4 + p] = have ? fmaf(relu_nan(v), sc, sh) : 0.f;   // ConvLayer's relu_pre order: ReLU, then the folded BatchNorm
     }
     __syncthreads();
     // the transposed convolution's taps at this pixel: hidden pixel (py, px) of the 2 x 2 block through (ky, kx)

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void k_upconv_pointwise(UpArgs a) {
             for (int r = 0; r < 16; ++r) {
                 const int cl = j * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh, co = ct * 128 + cl;
                 float v = acc[j][r];
-                if (a.relu_pre) v = v > 0.f ? v : 0.f;
+                if (a.relu_pre) v = relu_nan(v);
                 v = fmaf(v, s_ss[0][cl], s_ss[1][cl]);
                 if (in_ok) {
                     yn[co * oplane + pix] = v;
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void k_upconv_pointwise(UpArgs a) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 v[j] = acc[j][r];
-                if (a.relu_pre) v[j] = v[j] > 0.f ? v[j] : 0.f;
+                if (a.relu_pre) v[j] = relu_nan(v[j]);
                 v[j] = fmaf(v[j], sc, sh);
                 if (row_ok && ox0 + j >= 0 && ox0 + j < a.OW) m = fmaxf(m, finite_abs(v[j]));
                 nx[j] = j < PAD ? __shfl_down(v[j], 1, 32) : 0.f;
